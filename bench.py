@@ -10,6 +10,11 @@ cross-entropy -> backward -> Adam, all on libclamd's HIP kernels.  Default workl
 (UNet(21,3,64) 256x256 bs16 fp32, single task); ``--dtype bf16`` selects configs[2]'s arithmetic.  With N > 1 every
 rank trains its own 16 images (weak scaling) and gradients are all-reduced over RCCL/xGMI, overlapped with backward.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline.  ``--full`` adds everything else the line
+can carry, each measured after the timed steps: per-launch kernel timing with the roofline and the sustained-MFMA
+calibration, the committed PMC traffic figures, the golden-logits parity forward, the further dtypes of ``--also`` and the
+CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -44,12 +49,22 @@ def parse():
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--conv-dim', type=int, default=64)
     ap.add_argument('--num-classes', type=int, default=21)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need (kernel timing + roofline, PMC traffic, parity, '
+                         '--also dtypes, CPU baseline); the --no-* switches and --also below apply to such a run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32, a fixed seeded sample of large arrays)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true', help='skip the per-launch HIP events')
     ap.add_argument('--no-parity', action='store_true', help='skip the extra golden-logits forward (profiling runs: keeps foreign launches out of the trace)')
     ap.add_argument('--also', default=None,
                     help="comma list of further dtypes measured after the main run and reported under 'also' ('' = none)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 def _spawn_ranks(n):
@@ -109,7 +124,40 @@ def golden_logits_error(model, device):
     return float(np.linalg.norm(sub - ref) / np.linalg.norm(ref))
 
 
-def run(args, dtype, rank, world, device, timing=True, dist_on=False):
+DUMP_SAMPLE = 1 << 22            # elements kept of a larger dumped array: 16 MB in float32
+
+
+def _dump_sample(flat, seed):
+    """A 1-D device tensor as float32 on the host: whole up to DUMP_SAMPLE elements, else the elements at a fixed seeded set of
+    positions (sorted; the same for every build, given the length)."""
+    import numpy as np
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.detach().float().cpu().numpy()
+
+
+def dump_outputs(path, model, out, loss):
+    """--dump-outputs: what one train step hands its caller, right after the last timed step -- the loss, the logits, the parameters
+    after Adam and their gradients (both flattened in named_parameters order and sampled at the same positions) and the BatchNorm
+    running statistics -- as float32 .npy files: three samples of at most 16 MB each and two small arrays."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = list(model.parameters())
+    arrays = {
+        'loss': loss.detach().float().cpu().numpy(),
+        'logits': _dump_sample(out.reshape(-1), 1),
+        'params': _dump_sample(torch.cat([p.detach().reshape(-1).float() for p in params]), 2),
+        'grads': _dump_sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params]), 2),
+        'bn_running_stats': _dump_sample(torch.cat([b.reshape(-1).float() for n, b in model.named_buffers()
+                                                    if n.endswith(('running_mean', 'running_var'))]), 3),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a, dtype=np.float32))
+
+
+def run(args, dtype, rank, world, device, timing=True, dist_on=False, dump=None):
     import continual_learning_amd as C
     from continual_learning_amd import unet as U
     torch.manual_seed(1234)
@@ -130,10 +178,10 @@ def run(args, dtype, rank, world, device, timing=True, dist_on=False):
         loss = crit(out, y)             # :174
         loss.backward()                 # :175
         opt.step()                      # :176
-        return loss
+        return out, loss
 
     for _ in range(args.warmup):
-        loss = step()
+        out, loss = step()
     torch.cuda.synchronize()
     if sync is not None:
         sync.exposed_ms()               # drop the warm-up's wait events
@@ -143,7 +191,7 @@ def run(args, dtype, rank, world, device, timing=True, dist_on=False):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        out, loss = step()
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -162,6 +210,9 @@ def run(args, dtype, rank, world, device, timing=True, dist_on=False):
                     wino_persist=model.tuning.wino_persist,
                     note='exposed = HIP-event time the compute stream waits in GradSync.wait() before Adam, max over ranks; '
                          'buckets = bytes on the wire per rank and launch offset from the start of the last backward pass (rank 0)')
+    if dump and rank == 0:
+        dump_outputs(dump, model, out, loss)        # before the instrumented steps below move the weights again
+    del out
     # Per-launch HIP-event timing of the MFMA kernels: a SEPARATE pass of 2 steps right after the timed region
     # (an event pair around each of ~54 launches per step costs ~5 ms of dispatch bubbles per fp32 step, which would
     # distort `value`); events are recorded on the stream the kernels are launched on.
@@ -184,7 +235,7 @@ def run(args, dtype, rank, world, device, timing=True, dist_on=False):
     kern['_deficit_per_image'] = eng.executed_flop_deficit() / args.batch
     kern['_forms'] = sorted({('F(4x4,3x3)' if u.f44 else ('F(2x4,3x3)' if u.w24 else 'F(2x2,3x3)')) for u in eng.convs if u.wino})
     kern['_pre'] = sum(int(u.pre_f) + int(u.pre_d) for u in eng.convs)
-    kern['_logits_err'] = golden_logits_error(model, device) if (rank == 0 and not args.no_parity and (args.size, args.batch, args.conv_dim, args.num_classes) == (256, 16, 64, 21)) else None
+    kern['_logits_err'] = golden_logits_error(model, device) if (rank == 0 and args.full and not args.no_parity and (args.size, args.batch, args.conv_dim, args.num_classes) == (256, 16, 64, 21)) else None
     return dt, float(loss.detach()), kern, comm
 
 
@@ -312,7 +363,8 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    dt, loss, kern, comm = run(args, args.dtype, rank, world, device, timing=not args.no_kernel_timing, dist_on=dist_on)
+    dt, loss, kern, comm = run(args, args.dtype, rank, world, device, timing=args.full and not args.no_kernel_timing, dist_on=dist_on,
+                               dump=args.dump_outputs)
     images = args.batch * world * args.steps
     value = images / dt
     scale = (args.size / 256.0) ** 2 * (args.conv_dim / 64.0) ** 2
@@ -347,9 +399,10 @@ def main():
     out['algorithmic_speedup'] = round(flop_img / exec_img, 4)
     if comm is not None:
         out['comm'] = comm
-    conv_alg = (kern.get('igemm_conv3x3', (0, 0, 0, 0, 0))[3] + kern.get('wgrad_conv3x3', (0, 0, 0, 0, 0))[3]) / 2 if kern else None
-    out.update(step_traffic(args.dtype, args.size, args.batch, args.conv_dim, conv_alg) or
-               {'l2_fabric_bytes_per_step': None, 'algorithmic_bytes_per_step': None, 'fabric_over_algorithmic': None})
+    if args.full:
+        conv_alg = (kern.get('igemm_conv3x3', (0, 0, 0, 0, 0))[3] + kern.get('wgrad_conv3x3', (0, 0, 0, 0, 0))[3]) / 2 if kern else None
+        out.update(step_traffic(args.dtype, args.size, args.batch, args.conv_dim, conv_alg) or
+                   {'l2_fabric_bytes_per_step': None, 'algorithmic_bytes_per_step': None, 'fabric_over_algorithmic': None})
     if kern:
         # dominant kernel = the 3x3 implicit-GEMM (forward + data-gradient launches share one kernel template)
         sec, flops, n, nbytes, xflops = kern.get('igemm_conv3x3', (0, 0, 0, 0, 0))
@@ -419,8 +472,8 @@ def main():
             if wino:
                 out['roofline_wgrad']['algorithmic_tflops'] = round(alg, 2)
                 out['roofline_wgrad']['algorithmic_speedup'] = round(flops / xflops, 4)
-    # further dtypes: by default on the single-GPU run only (the N-GPU scaling runs measure the headline dtype and nothing else)
-    also = args.also if args.also is not None else ('bf16x3,bf16' if not dist_on else '')
+    # further dtypes (--full only): by default on the single-GPU run only (the N-GPU scaling runs measure the headline dtype and nothing else)
+    also = (args.also if args.also is not None else ('bf16x3,bf16' if not dist_on else '')) if args.full else ''
     for other in [d for d in also.split(',') if d and d != args.dtype]:
         dt2, loss2, k2, _ = run(args, other, rank, world, device, timing=not args.no_kernel_timing)
         v2 = images / dt2
@@ -445,7 +498,7 @@ def main():
         if sec > 0:
             o['conv3x3_wgrad_tflops'] = round(flops / sec / 1e12, 1)
         out.setdefault('also', []).append(o)
-    if rank == 0 and not dist_on and not args.no_cpu_baseline:
+    if rank == 0 and not dist_on and args.full and not args.no_cpu_baseline:
         from oracle import torch_cpu as TC                       # the checker timed as the reported CPU baseline
         xb = x_cpu = None
         import continual_learning_amd as C

@@ -26,6 +26,28 @@ REF = '/root/reference'
 OUT = os.path.join(ROOT, 'tests', 'golden')
 
 
+PART_BYTES = 960 << 10      # no archive above this: a committed file stays under 1 MiB
+
+
+def save_golden(path, arrays):
+    """np.savez_compressed of `arrays`, split in key order into <stem>.npz, <stem>.part2.npz, ... whenever the compressed
+    archive would pass PART_BYTES (tests/conftest.py's `golden` fixture joins the parts again)."""
+    import zlib
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes())) + 256
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        dst = path if i == 0 else f'{path[:-len(".npz")]}.part{i + 1}.npz'
+        np.savez_compressed(dst, **p)
+        assert os.path.getsize(dst) < 1 << 20, dst
+
+
 def _load(name, path):
     spec = importlib.util.spec_from_file_location(name, path)
     mod = importlib.util.module_from_spec(spec)
@@ -71,7 +93,7 @@ def capture_forward_only(ref_unet, ref_metrics, synth, tag, num_classes, conv_di
            'metrics': np.array([float(oa), float(pc), float(miu), float(mx)], np.float32),
            'stats1': np.concatenate([v.numpy().reshape(-1) for k, v in model.state_dict().items()
                                      if k.endswith(('running_mean', 'running_var'))])}
-    np.savez_compressed(os.path.join(OUT, f'unet_{tag}.npz'), **out)
+    save_golden(os.path.join(OUT, f'unet_{tag}.npz'), out)
     print(tag, 'loss', float(loss), 'mIoU', float(miu))
 
 
@@ -201,7 +223,7 @@ def capture_model(ref_unet, ref_metrics, synth, tag, num_classes, conv_dim, batc
                     out[f'w{s + 1}/' + k] = v
     out['losses'] = np.array(losses, np.float64)
     out['param_norms_end'] = np.array([float(p.detach().double().norm()) for p in model.parameters()])
-    np.savez_compressed(os.path.join(OUT, f'unet_{tag}.npz'), **out)
+    save_golden(os.path.join(OUT, f'unet_{tag}.npz'), out)
     print(tag, 'losses', losses, 'mIoU', out['metrics'][2])
 
 

@@ -35,10 +35,27 @@ def _collect_garbage_between_gpu_tests(request):
         gc.collect()
 
 
+class _JoinedArchive(dict):
+    """The arrays of a golden archive stored in parts (<stem>.npz, <stem>.part2.npz, ...: oracle/gen_golden.save_golden keeps
+    every committed file under 1 MiB), with the `.files` list of an NpzFile."""
+    @property
+    def files(self):
+        return list(self)
+
+
 @pytest.fixture(scope='session')
 def golden():
     def load(name):
-        return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+        path = os.path.join(GOLDEN, name)
+        stem = path[:-len('.npz')]
+        if not os.path.exists(f'{stem}.part2.npz'):
+            return np.load(path, allow_pickle=False)
+        joined, i = _JoinedArchive(), 1
+        while os.path.exists(part := path if i == 1 else f'{stem}.part{i}.npz'):
+            with np.load(part, allow_pickle=False) as z:
+                joined.update((k, z[k]) for k in z.files)
+            i += 1
+        return joined
     return load
 
 

@@ -72,7 +72,7 @@ def test_bench_rccl_code_path_with_one_rank():
     env.pop('NCCL_MAX_NCHANNELS', None); env.pop('NCCL_MIN_NCHANNELS', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-           '--size', '128', '--batch', '4']
+           '--size', '128', '--batch', '4', '--full']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][0])
@@ -80,6 +80,41 @@ def test_bench_rccl_code_path_with_one_rank():
     assert c['backend'] == 'nccl' and c['rccl_ranks'] == 1 and c['NCCL_MAX_NCHANNELS'] == '8' and c['NCCL_MIN_NCHANNELS'] == '4'
     assert c['collectives_per_step'] >= 1 and c['exposed_comm_ms_per_step'] >= 0.0 and c['cu_reserve'] == 0
     assert 'roofline' in d and d['n_gpus'] == 1
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that needs runs, passes or files of its own; --dump-outputs writes
+    what the last timed step computed as float32 .npy files, identical from run to run for the same arguments."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'CLAMD_BENCH_BACKEND', 'CLAMD_BENCH_FORCE_DIST'):
+        env.pop(k, None)
+    lines = []
+    for i in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--size', '128', '--batch', '4',
+                              '--dump-outputs', str(tmp_path / f'run{i}')], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        (line,) = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        lines.append(json.loads(line))
+    d = lines[0]
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['n_gpus'] == 1 and d['dtype'] == 'f32' and d['unit'] == 'images/sec'
+    assert d['higher_is_better'] is True and d['ms_per_step'] > 0
+    assert d['value'] == pytest.approx(4 * 2 / (d['ms_per_step'] * 2 / 1e3), rel=1e-3, abs=0.006)
+    for k in ('roofline', 'roofline_wgrad', 'hbm_kernels', 'also', 'cpu_baseline', 'logits_rel_l2_vs_golden', 'l2_fabric_bytes_per_step'):
+        assert k not in d, k
+    names = ('loss', 'logits', 'params', 'grads', 'bn_running_stats')
+    assert sorted(os.listdir(tmp_path / 'run0')) == sorted(n + '.npy' for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / 'run0' / f'{n}.npy'), np.load(tmp_path / 'run1' / f'{n}.npy')
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / 'run0' / 'logits.npy').shape == (4 * 21 * 128 * 128,)         # small enough to be written whole
+    assert np.load(tmp_path / 'run0' / 'params.npy').shape == np.load(tmp_path / 'run0' / 'grads.npy').shape
+    assert float(np.load(tmp_path / 'run0' / 'loss.npy')) == pytest.approx(d['config']['final_loss'], abs=1e-5)
+    assert lines[1]['config']['final_loss'] == d['config']['final_loss']
 
 
 @pytest.mark.parametrize('dtype', ['bf16', 'fp32'])
@@ -129,7 +164,7 @@ def test_bench_single_gpu_line_carries_calibration_and_traffic_fields():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'CLAMD_BENCH_BACKEND', 'CLAMD_BENCH_FORCE_DIST'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--size', '128', '--batch', '4',
-                          '--no-cpu-baseline', '--also', 'bf16'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          '--full', '--no-cpu-baseline', '--also', 'bf16'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1

@@ -58,10 +58,10 @@ if os.path.exists(f'{G}/{src}_bench_config5_bf16.json'):
 b = last_json(f'{P}/{dst}_bench_default.json')
 L = []
 L.append(f'# profiles/ — round evidence `{dst}` (MI355X, ROCm 7.2, one GPU)\n')
-L.append('All files come from one `gpurun` box: `bash tools/profile_round.sh <tag>` then `python tools/make_profiles.py <tag> ' + dst + '`.\n')
+L.append('All files come from one MI355X machine: `bash tools/profile_round.sh <tag> <out>` then `python tools/make_profiles.py <tag> ' + dst + '`.\n')
 L.append('| file | what |\n|---|---|')
-L.append(f'| `{dst}_bench_default.json` | `python bench.py --steps 10 --warmup 3` (the driver\'s command): fp32 headline + `also` bf16x3 / bf16 + `cpu_baseline` |')
-L.append(f'| `{dst}_<dtype>_kernel_stats.csv` | `CLAMD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 6 --warmup 2 --dtype <dtype> --no-cpu-baseline --also ""` (8 steps + 2 instrumented steps).  One stream: the same kernels with the same arguments as the shipped two-stream step, but a kernel\'s begin-to-end time is its own, so the averages agree with the HIP-event timings `bench.py` takes live (its two instrumented steps are single-stream too) |')
+L.append(f'| `{dst}_bench_default.json` | `python bench.py --full --steps 10 --warmup 3`: fp32 headline + `also` bf16x3 / bf16 + `cpu_baseline` |')
+L.append(f'| `{dst}_<dtype>_kernel_stats.csv` | `CLAMD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 6 --warmup 2 --dtype <dtype> --no-cpu-baseline --also ""` (8 steps + 2 instrumented steps).  One stream: the same kernels with the same arguments as the shipped two-stream step, but a kernel\'s begin-to-end time is its own, so the averages agree with the HIP-event timings `bench.py` takes live (its two instrumented steps are single-stream too) |')
 if os.path.exists(f'{G}/{src}_prof_fp32_overlap/{src}_kernel_stats.csv'):
     shutil.copy(f'{G}/{src}_prof_fp32_overlap/{src}_kernel_stats.csv', f'{P}/{dst}_fp32_overlap_kernel_stats.csv')
     shutil.copy(f'{G}/{src}_bench_fp32_overlap_under_rocprof.json', f'{P}/{dst}_bench_fp32_overlap_under_rocprof.json')
