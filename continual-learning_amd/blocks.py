@@ -21,12 +21,13 @@ def _stream():
 
 
 class _BlockFn(torch.autograd.Function):
-    """forward(x, plan, *params): plan = (ops, dcode, training, buffers); ops = [('pool',), ('crb', k), ..., ('convT',) | ('head',)];
+    """forward(x, plan, *params): plan = (ops, dcode, buffers); ops = [('pool',), ('crb', k, training), ..., ('convT',) | ('head',)]
+    (`training`: that BatchNorm module's own mode -- batch statistics, or its running statistics and no update);
     params = (conv.weight, conv.bias, bn.weight, bn.bias) per 'crb' in order, then (weight, bias) of the tail."""
 
     @staticmethod
     def forward(ctx, x, plan, *params):
-        ops, dcode, training, buffers = plan
+        ops, dcode, buffers = plan
         T = TORCH_DT[dcode]
         dev = x.device
         s = _stream()
@@ -44,6 +45,7 @@ class _BlockFn(torch.autograd.Function):
             elif op[0] == 'crb':
                 w, b, gamma, beta = params[pi:pi + 4]
                 rm, rv, nbt = buffers[op[1]]
+                training = op[2]
                 pi += 4
                 cout, cin = w.shape[0], w.shape[1]
                 cin_p, cout_p = cur.shape[-1], cpad(cout)
@@ -64,7 +66,7 @@ class _BlockFn(torch.autograd.Function):
                      ptr(vec[2]), ptr(vec[3]), cout_p, cout, float(B * H * W), BN_MOMENTUM, BN_EPS, ptr(nbt) if training else None, s)
                 out = torch.empty_like(y)
                 call('clamd_bn_apply', ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(out), cout_p, None, 0, B, H, W, cout_p, dcode, s)
-                saved.append(('crb', cur, y, vec, wd, gamma.detach(), (cin, cin_p, cout, cout_p, H, W)))
+                saved.append(('crb', cur, y, vec, wd, gamma.detach(), training, (cin, cin_p, cout, cout_p, H, W)))
                 cur = out
             elif op[0] == 'convT':
                 w, b = params[pi:pi + 2]
@@ -98,7 +100,7 @@ class _BlockFn(torch.autograd.Function):
                 call('clamd_conv1x1_logits', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(logits), B, H, W, cin_p, kp, k, dcode, s)
                 saved.append(('head', cur, wd, (cin, cin_p, k, kp, H, W)))
                 cur = None
-        ctx.saved_ops, ctx.dcode, ctx.B, ctx.cin0, ctx.training = saved, dcode, B, C, training
+        ctx.saved_ops, ctx.dcode, ctx.B, ctx.cin0 = saved, dcode, B, C
         if cur is None:
             return logits
         last = ops[-1]
@@ -107,8 +109,6 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        if not ctx.training:
-            raise RuntimeError('block backward after an eval-mode forward is not supported (BatchNorm backward uses batch statistics)')
         dcode, B = ctx.dcode, ctx.B
         lib = _lib.load()
         T = TORCH_DT[dcode]
@@ -148,18 +148,28 @@ class _BlockFn(torch.autograd.Function):
                 grads = [dw, db] + grads
                 g = gx
             elif kind == 'crb':
-                _, x, y, vec, wd, gamma, (cin, cin_p, cout, cout_p, H, W) = rec
+                _, x, y, vec, wd, gamma, training, (cin, cin_p, cout, cout_p, H, W) = rec
                 ga = to_nhwc(gout, dcode, cp=cout_p) if g is None else g
-                rows = _lib.stat_rows(_lib.OP_BN_BWD_REDUCE, B, H, W, 0, cout_p, dcode)
-                sums = torch.empty(rows, lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float32, device=dev)
-                call('clamd_bn_bwd_reduce', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
-                     B, H, W, cout_p, dcode, None, s)
                 dgamma, dbeta, dbias = (torch.empty(cout, dtype=torch.float32, device=dev) for _ in range(3))
-                call('clamd_bn_bwd_finalize', ptr(sums), rows, ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma), ptr(dbeta),
-                     ptr(dbias), cout_p, cout, float(B * H * W), s)
                 gz = torch.empty(B, H, W, cout_p, dtype=T, device=dev)
-                call('clamd_bn_bwd_apply', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
-                     B, H, W, cout_p, dcode, s)
+                if training:
+                    rows = _lib.stat_rows(_lib.OP_BN_BWD_REDUCE, B, H, W, 0, cout_p, dcode)
+                    sums = torch.empty(rows, lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float32, device=dev)
+                    call('clamd_bn_bwd_reduce', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
+                         B, H, W, cout_p, dcode, None, s)
+                    call('clamd_bn_bwd_finalize', ptr(sums), rows, ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma), ptr(dbeta),
+                         ptr(dbias), cout_p, cout, float(B * H * W), s)
+                    call('clamd_bn_bwd_apply', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
+                         B, H, W, cout_p, dcode, s)
+                else:      # running statistics: one pass writes g_z and the rows of the parameter gradients
+                    rows = lib.clamd_bn_bwd_eval_rows(B, H, W, cout_p, 0)
+                    if rows <= 0:
+                        _lib.check(rows, 'clamd_bn_bwd_eval_rows')
+                    er = torch.empty(rows, 3, cout_p, dtype=torch.float32, device=dev)
+                    call('clamd_bn_bwd_eval', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(gz), cout_p, ptr(er), rows,
+                         B, H, W, cout_p, cout, dcode, s)
+                    call('clamd_bn_bwd_eval_finalize', ptr(er), rows, 3, ptr(vec[0]), ptr(vec[2]), ptr(vec[3]), None, ptr(dgamma), ptr(dbeta),
+                         ptr(dbias), cout_p, cout, s)
                 gx = torch.empty(B, H, W, cin_p, dtype=T, device=dev)
                 call('clamd_conv3x3', ptr(gz), cout_p, ptr(wd), None, ptr(gx), cin_p, None, None, None, 0, B, H, W, cout_p, cin_p, 0,
                      1 if 9 * cin_p > B * H * W else 0, dcode, None, s)
@@ -192,7 +202,7 @@ def run_block(seq, st, dcode, x):
         ops.append(('pool',))
     for ci, bi, cin, cout in st['convs']:
         conv, bn = seq[ci], seq[bi]
-        ops.append(('crb', len(buffers)))
+        ops.append(('crb', len(buffers), bool(bn.training)))
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
         buffers.append((bn.running_mean, bn.running_var, bn.num_batches_tracked))
     if st['tail'] is not None:
@@ -201,5 +211,4 @@ def run_block(seq, st, dcode, x):
         params += [seq[ti].weight, seq[ti].bias]
     if x.shape[1] != st['convs'][0][2]:
         raise ValueError(f'expected {st["convs"][0][2]} input channels, got {x.shape[1]}')
-    training = seq.training
-    return _BlockFn.apply(x, (ops, dcode, training, buffers), *params)
+    return _BlockFn.apply(x, (ops, dcode, buffers), *params)

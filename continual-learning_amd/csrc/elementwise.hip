@@ -442,6 +442,121 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_sums_kernel(const T* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Backward of [ReLU -> BatchNorm(eval)]: the BatchNorm normalised with its running statistics, u = scale*y + shift with scale / shift
+// constants (clamd_bn_finalize's eval branch), so
+//   g_z = [y>0] * scale * g_u                                          (no reduction in front of it)
+//   rows: r0 = sum g_u, r1 = sum g_u*y, r2 = sum g_z                    -> d beta, d gamma, d conv-bias (bn_bwd_eval_finalize_kernel)
+// ONE streaming pass (g and y read once, g_z written once) instead of reduce -> finalize -> apply.  Pooled: g_u gets gp at the first maximum
+// of scale*y + shift in its window (load_gu, as bn_bwd_apply_kernel).  Channels >= C of g_z are written as zero.  Thread layout of
+// bn_bwd_reduce_kernel (channel group cg = tid % G fixed per thread, 256 / G pixels per block trip); one partial row [3][Cp] per block,
+// the pixels of a block added in thread order through LDS: deterministic.
+constexpr int NSUM_EVAL = 3;
+
+template <typename T, bool POOL>
+__global__ void __launch_bounds__(256) bn_bwd_eval_kernel(const T* __restrict__ ga, int ga_ldc, const T* __restrict__ gp, int gp_ldc,
+                                                          const T* __restrict__ y, int y_ldc, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, T* __restrict__ gz, int gz_ldc, float* rows,
+                                                          int B, int H, int W, int Cp, int C) {
+    PASS_PRIO();
+    __shared__ float red[256 * 8];
+    const int G = Cp >> 3, tid = threadIdx.x;
+    const int cg = tid % G, prow = tid / G, per = 256 / G;
+    const int nlive = C - cg * 8;                   // channels cg*8 + j with j >= nlive are padding: g_z = 0 there
+    float sc[8], acc[NSUM_EVAL][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sc[j] = scale[cg * 8 + j];
+#pragma unroll
+        for (int s = 0; s < NSUM_EVAL; ++s) acc[s][j] = 0.f;
+    }
+    const long long npix = POOL ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
+    const long long stride = (long long)gridDim.x * per;
+    if constexpr (!POOL) {
+        // two pixels per trip, as bn_bwd_reduce_kernel: four 16-byte loads in flight per thread; the terms are added in pixel order
+        for (long long pix = (long long)blockIdx.x * per + prow; pix < npix; pix += 2 * stride) {
+            float g[2][8], v[2][8];
+            const bool two = pix + stride < npix;
+            const long long pix1 = two ? pix + stride : pix;
+            Vec8<T>::load(ga + pix * ga_ldc + cg * 8, g[0]);
+            Vec8<T>::load(y + pix * y_ldc + cg * 8, v[0]);
+            Vec8<T>::load(ga + pix1 * ga_ldc + cg * 8, g[1]);
+            Vec8<T>::load(y + pix1 * y_ldc + cg * 8, v[1]);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                if (u == 1 && !two) break;
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    o[j] = (v[u][j] > 0.f && j < nlive) ? sc[j] * g[u][j] : 0.f;
+                    acc[0][j] += g[u][j]; acc[1][j] += g[u][j] * v[u][j]; acc[2][j] += o[j];
+                }
+                Vec8<T>::store(gz + (u ? pix1 : pix) * gz_ldc + cg * 8, o);
+            }
+        }
+    } else {
+        float sh[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sh[j] = shift[cg * 8 + j];
+        const int w2 = W / 2, h2 = H / 2;
+        for (long long pix = (long long)blockIdx.x * per + prow; pix < npix; pix += stride) {
+            const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
+            float g[4][8], v[4][8];
+            load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, b, py, px, H, W, cg, g, v);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float o = (v[q][j] > 0.f && j < nlive) ? sc[j] * g[q][j] : 0.f;
+                    acc[0][j] += g[q][j]; acc[1][j] += g[q][j] * v[q][j]; acc[2][j] += o;
+                    g[q][j] = o;
+                }
+                Vec8<T>::store(gz + p * gz_ldc + cg * 8, g[q]);
+            }
+        }
+    }
+    float* dst = rows + (size_t)blockIdx.x * NSUM_EVAL * Cp;
+#pragma unroll
+    for (int s = 0; s < NSUM_EVAL; ++s) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[s][j];
+        __syncthreads();
+        for (int c = tid; c < Cp; c += 256) {       // channel c's contributions: red[(r*G + c/8)*8 + c%8], r = 0..per-1
+            const int g8 = c >> 3, j = c & 7;
+            float t = 0.f;
+            for (int r = 0; r < per; ++r) t += red[(r * G + g8) * 8 + j];
+            dst[s * Cp + c] = t;
+        }
+    }
+}
+
+// Partial rows of an eval-mode BatchNorm backward -> d gamma, d beta, d conv-bias (fixed-order fp64 row sums, sum_partial_rows).
+//   NK = 3: the rows of bn_bwd_eval_kernel (sum g, sum g y, sum g_z);
+//   NK = 5: the five sums of a producing data-gradient launch's epilogue (sum g, sum g y, sum g [y>0], ...): d conv-bias = scale * row 2,
+//           or not written (dbias == NULL: the two-sum form, whose rows 2-4 are NaN; the bias gradient then comes from the apply pass).
+// k012 (optional): k0 = scale, k1 = k2 = 0 -- the eval-mode coefficients for clamd_bn_bwd_apply / clamd_bn_bwd_apply_sums.
+template <int NK>
+__global__ void __launch_bounds__(FIN_THREADS) bn_bwd_eval_finalize_kernel(const float* __restrict__ rows, int nrows, const float* __restrict__ scale,
+                                                                           const float* __restrict__ save_mean, const float* __restrict__ save_istd,
+                                                                           float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C) {
+    PASS_PRIO();
+    __shared__ double red[FIN_THREADS], tot[NK * FIN_CH];
+    const int c0 = blockIdx.x * FIN_CH;
+    sum_partial_rows<NK>(rows, nrows, Cp, c0, red, tot);
+    if (threadIdx.x >= FIN_CH) return;
+    const int c = c0 + threadIdx.x;
+    const float sc = c < C ? scale[c] : 0.f;
+    if (k012) { k012[c] = sc; k012[Cp + c] = 0.f; k012[2 * Cp + c] = 0.f; }
+    if (c >= C) return;
+    const double s0 = tot[threadIdx.x], s1 = tot[FIN_CH + threadIdx.x], s2 = tot[2 * FIN_CH + threadIdx.x];
+    const double mu = save_mean[c], istd = save_istd[c];
+    dgamma[c] = (float)(istd * (s1 - mu * s0));
+    dbeta[c] = (float)s0;
+    if (dbias) dbias[c] = (float)(NK == NSUM_EVAL ? s2 : (double)sc * s2);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Per-channel sum of an NHWC tensor (bias gradients of convT / head): every block writes its partial row [Cp] into the
@@ -842,6 +957,62 @@ int clamd_bn_bwd_apply_sums(const void* ga, int ga_ldc, const void* y, int y_ldc
     else return clamd_fail("bn_bwd_apply_sums: bad dtype");
 #undef LAUNCH
     return clamd_check_launch("bn_bwd_apply_sums");
+}
+
+// rows of clamd_bn_bwd_eval: one per workgroup; the grid stops growing at ~1 MB of rows (the finalize adds them on the critical chain of
+// the fused-sum units and beside a weight gradient elsewhere) and at 2048 workgroups (8 per CU: the pass streams at full rate well below)
+static long long eval_rows(int B, int H, int W, int Cp, bool pooled) {
+    const int per = 256 / (Cp / 8);
+    const long long npix = pooled ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
+    const long long gb = (npix + per - 1) / per;
+    const long long cap = reduce_grid_cap(0, Cp, 256, 2048, 262144);
+    return gb > cap ? cap : (gb < 1 ? 1 : gb);
+}
+
+int clamd_bn_bwd_eval_rows(int B, int H, int W, int Cp, int pooled) {
+    if (B <= 0 || H <= 0 || W <= 0 || !pow2_channels(Cp)) return clamd_fail("bn_bwd_eval_rows: bad sizes");
+    if (pooled && ((H | W) & 1)) return clamd_fail("bn_bwd_eval_rows: pooling needs even H, W");
+    return (int)eval_rows(B, H, W, Cp, pooled != 0);
+}
+
+int clamd_bn_bwd_eval(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc, const float* scale, const float* shift,
+                      void* gz, int gz_ldc, float* rows, int nrows, int B, int H, int W, int Cp, int C, int dtype, void* stream) {
+    if (!pow2_channels(Cp) || C <= 0 || C > Cp) return clamd_fail("bn_bwd_eval: physical channels must be a power of two in [32,2048], 0 < C <= Cp");
+    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_eval: bad sizes");
+    if (!y || !scale || !gz || !rows || (!ga && !gp) || (gp && !shift)) return clamd_fail("bn_bwd_eval: null argument");
+    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_eval: pooling needs even H, W");
+    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp || gz_ldc < Cp) return clamd_fail("bn_bwd_eval: pitches must be >= Cp");
+    if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
+    if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
+    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
+    if (int e = clamd_check_split(dtype, gz, gz_ldc)) return e;
+    if (nrows != eval_rows(B, H, W, Cp, gp != nullptr)) return clamd_fail("bn_bwd_eval: nrows must be clamd_bn_bwd_eval_rows(B, H, W, Cp, gp != NULL)");
+    dim3 g((unsigned)nrows), b(256);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(T, P) hipLaunchKernelGGL((bn_bwd_eval_kernel<T, P>), g, b, 0, s, (const T*)ga, ga_ldc, (const T*)gp, gp_ldc, (const T*)y, y_ldc, \
+                                        scale, shift, (T*)gz, gz_ldc, rows, B, H, W, Cp, C)
+    if (dtype == CLAMD_BF16) { if (gp) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false); }
+    else if (dtype == CLAMD_F32) { if (gp) LAUNCH(float, true); else LAUNCH(float, false); }
+    else if (dtype == CLAMD_SPLIT) { if (gp) LAUNCH(split_t, true); else LAUNCH(split_t, false); }
+    else return clamd_fail("bn_bwd_eval: bad dtype");
+#undef LAUNCH
+    return clamd_check_launch("bn_bwd_eval");
+}
+
+int clamd_bn_bwd_eval_finalize(const float* rows, int nrows, int nsums, const float* scale, const float* save_mean, const float* save_istd,
+                               float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C, void* stream) {
+    if (Cp <= 0 || Cp % 8 || C <= 0 || C > Cp) return clamd_fail("bn_bwd_eval_finalize: bad channel counts");
+    if (!rows || nrows <= 0) return clamd_fail("bn_bwd_eval_finalize: nrows must be the row count the producing launch wrote");
+    if (!scale || !save_mean || !save_istd || !dgamma || !dbeta) return clamd_fail("bn_bwd_eval_finalize: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (nsums == NSUM_EVAL)
+        hipLaunchKernelGGL(bn_bwd_eval_finalize_kernel<NSUM_EVAL>, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, s, rows, nrows, scale, save_mean,
+                           save_istd, k012, dgamma, dbeta, dbias, Cp, C);
+    else if (nsums == NSUM)
+        hipLaunchKernelGGL(bn_bwd_eval_finalize_kernel<NSUM>, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, s, rows, nrows, scale, save_mean,
+                           save_istd, k012, dgamma, dbeta, dbias, Cp, C);
+    else return clamd_fail("bn_bwd_eval_finalize: nsums must be 3 (clamd_bn_bwd_eval rows) or 5 (clamd_bn_bwd_nsums rows)");
+    return clamd_check_launch("bn_bwd_eval_finalize");
 }
 
 int clamd_rows_sum(const float* rows, int nrows, float* out, int Cp, int C, void* stream) {

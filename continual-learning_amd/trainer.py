@@ -10,13 +10,15 @@ Same construction and ordering as the reference:
 Out of scope here: JPEG dumps, prints, checkpoint files; the every-10th-iteration statistics
 (trainer.py:177-189) are computed on the GPU by metrics.argmax_confusion instead of .cpu() round trips.
 Continual learning (config 4): ``begin_task2(c_old, ...)`` snapshots the model and switches the criterion to
-DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined).
+DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined); ``freeze_bn=True`` also trains task 2 with
+every BatchNorm in eval mode (running statistics, not updated).
 """
 import os
 import warnings
 from types import SimpleNamespace
 
 import torch
+import torch.nn as nn
 from torch.optim.lr_scheduler import LambdaLR
 
 from .loss import CrossEntropyLoss, DistillationCrossEntropy
@@ -53,8 +55,10 @@ class Trainer:
     def reset_grad(self):
         self.optim.zero_grad()
 
-    def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0):
-        """Freeze a snapshot of the current model (task 1) and regularise further training towards it."""
+    def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False):
+        """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
+        trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
+        still reach gamma and beta)."""
         # a fresh module with a CLONE of the state (not copy.deepcopy: that would duplicate the engine's multi-GB activation
         # buffers and, under data parallelism, the GradSync object with its process group and stream)
         m = self.model
@@ -66,6 +70,10 @@ class Trainer:
         self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
         if l2_lambda > 0:
             self.optim.set_l2_anchor([p.detach().clone() for p in self.old_model.parameters()], l2_lambda)
+        if freeze_bn:
+            for mod in m.modules():
+                if isinstance(mod, nn.BatchNorm2d):
+                    mod.eval()
 
     # ---- checkpoints: same file name and keys as trainer.py:68-102, but the model never leaves
     # the GPU: the reference does network.cpu() ... network.cuda() (a full D2H + H2D round trip of 124 MB every
@@ -134,8 +142,8 @@ class Trainer:
     def test(self, data_loader):
         """trainer.py:270-284: pixel accuracy (%) of the eval-mode model over a loader.  The arg-max of trainer.py:279 runs
         inside the head kernel (UNet.predict).  Unlike the reference (which never calls .train() again) the
-        model's mode is restored afterwards."""
-        was_training = self.model.training
+        mode of every module is restored afterwards, each its own (frozen BatchNorm layers stay frozen)."""
+        modes = [(mod, mod.training) for mod in self.model.modules()]
         self.model.eval()
         correct = torch.zeros((), dtype=torch.int64, device=self.device)
         total = 0
@@ -144,7 +152,8 @@ class Trainer:
             predicted = self.model.predict(images.to(self.device, non_blocking=True))
             total += labels.numel()
             correct += (predicted == labels).sum()
-        self.model.train(was_training)
+        for mod, mode in modes:
+            mod.training = mode
         return 100.0 * float(correct) / max(total, 1)
 
     def train_epoch(self, epoch):

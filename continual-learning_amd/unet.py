@@ -2,7 +2,8 @@
 
 Mirrors the reference module surface (models/unet.py:40-92): same constructor, the same 82 parameters in the same
 registration order, the same 136 ``state_dict`` keys ('enc1.0.weight', 'enc2.block.1.weight', 'dec1.block.6.weight',
-'last.6.bias', ...), fp32 NCHW in / fp32 NCHW logits out, ``.train()/.eval()`` BatchNorm semantics, autograd-attached.
+'last.6.bias', ...), fp32 NCHW in / fp32 NCHW logits out, ``.train()/.eval()`` BatchNorm semantics per BatchNorm module (frozen
+statistics: ``bn.eval()`` under ``model.train()``, backward included), autograd-attached.
 The child modules (nn.Conv2d, nn.BatchNorm2d, ...) are only PARAMETER CONTAINERS with torch's default init; their own
 ``forward`` is never called.  ``UNet.forward`` runs the whole network as ONE ``torch.autograd.Function`` whose forward
 and backward are fixed schedules of C-ABI kernel launches on NHWC activations (fp32 or bf16) kept in buffers owned by
@@ -287,7 +288,7 @@ class UNet(nn.Module):
     @torch.no_grad()
     def predict(self, x):
         """``torch.max(self(x), 1)[1]`` (trainer.py:279) without materialising the logits: the arg-max over classes runs
-        in the epilogue of the head kernel.  int64 [B,H,W]; BatchNorm follows ``self.training``."""
+        in the epilogue of the head kernel.  int64 [B,H,W]; every BatchNorm follows its own ``.training``."""
         if not x.is_cuda:
             raise RuntimeError('continual-learning_amd.UNet runs only on an MI355X GPU tensor: there is no CPU fallback')
         if x.dim() != 4 or x.shape[1] != self.in_dim:
@@ -313,7 +314,7 @@ def dlogits_sink(logits, B, K, H, W):
     if tag is None:
         return None
     eng, gen = tag[0](), tag[1]
-    if eng is None or eng.generation != gen or (eng.B, eng.K, eng.H, eng.W) != (B, K, H, W) or not eng.fwd_training or eng.dl.device != logits.device:
+    if eng is None or eng.generation != gen or (eng.B, eng.K, eng.H, eng.W) != (B, K, H, W) or not all(eng.fwd_modes) or eng.dl.device != logits.device:
         return None
     return eng
 
@@ -366,7 +367,7 @@ class _Engine:
         self.NS = lib.clamd_bn_bwd_nsums()
         self.generation = 0
         self.dl_src = None
-        self.fwd_training = False
+        self.fwd_modes = ()          # per conv unit: its BatchNorm's .training at the last forward (False = running statistics)
         self.esize = 2 if self.dcode == _lib.BF16 else 4      # activation element size in HBM (bf16x3 stores fp32)
         K, d = model.num_classes, model.conv_dim
         self.K, self.Kp = K, cpad(K)
@@ -378,6 +379,7 @@ class _Engine:
 
         named = dict(model.named_parameters())
         bufs = dict(model.named_buffers())
+        mods = dict(model.named_modules())
         self.param_names = [n for n, _ in model.named_parameters()]
         # flat gradient buffer in REVERSE registration order (= order gradients are produced): contiguous buckets
         sizes = [named[n].numel() for n in self.param_names]
@@ -408,6 +410,8 @@ class _Engine:
             u.gamma, u.beta = named[f'{prefix}.{bi}.weight'], named[f'{prefix}.{bi}.bias']
             u.rm, u.rv = bufs[f'{prefix}.{bi}.running_mean'], bufs[f'{prefix}.{bi}.running_var']
             u.nbt = bufs[f'{prefix}.{bi}.num_batches_tracked']
+            u.bn = mods[f'{prefix}.{bi}']                          # its .training is the unit's BatchNorm mode (read every forward)
+            u.bn_train = True
             u.keys = (f'{prefix}.{ci}.weight', f'{prefix}.{ci}.bias', f'{prefix}.{bi}.weight', f'{prefix}.{bi}.bias')
             u.level, u.h, u.w_ = level, H >> level, W >> level
             u.cin_segs = cin_segs                                  # [(logical, physical), ...] one or two segments
@@ -693,6 +697,19 @@ class _Engine:
                 u.sum_rows = rows(_lib.OP_BN_BWD_REDUCE, B, u.h, u.w_, 1 if u.g_src[2] is not None else 0, u.cout_p, dc, tuning=tn)
             sizes.append((u.stat_rows * 2 + u.sum_rows * self.NS + u.gz_nrows) * u.cout_p)
         self.stat_arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.dev)
+        # eval-mode BatchNorm backward (clamd_bn_bwd_eval): rows [n][3][Cout_p] of the units whose sums no producing launch accumulates;
+        # an arena of its own, so the train-mode buffers stay as they were
+        esz = []
+        for u in self.convs:
+            u.eval_nrows = 0 if u.fused_reduce else _lib.load().clamd_bn_bwd_eval_rows(B, u.h, u.w_, u.cout_p, 1 if u.g_src[2] is not None else 0)
+            if u.eval_nrows < 0:
+                _lib.check(u.eval_nrows, 'clamd_bn_bwd_eval_rows')
+            esz.append(u.eval_nrows * 3 * u.cout_p)
+        self.eval_arena = torch.empty(sum(esz), dtype=torch.float32, device=self.dev)
+        off = 0
+        for u, n in zip(self.convs, esz):
+            u.eval_rows = self.eval_arena[off:off + n] if n else None
+            off += n
         off = 0
         for u, n in zip(self.convs, sizes):
             k, k2 = u.stat_rows * 2 * u.cout_p, u.gz_nrows * u.cout_p
@@ -770,8 +787,10 @@ class _Engine:
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x, params, predict=False):
         m = self.model
-        training = m.training
-        self.fwd_training = training
+        # BatchNorm mode per unit, from its own nn.BatchNorm2d (torch's semantics: model.train() then bn.eval() freezes that layer's statistics)
+        for u in self.convs:
+            u.bn_train = bool(u.bn.training)
+        self.fwd_modes = tuple(u.bn_train for u in self.convs)
         self.generation += 1
         self.dl_src = None
         self._check_ptrs(params)
@@ -805,8 +824,8 @@ class _Engine:
             for u in st['convs']:
                 self._fwd_pre(u, s)
                 self._fwd_fold(u, s)
-                self._fwd_conv(u, training, s)
-                self._fwd_finalize(u, training, s)
+                self._fwd_conv(u, u.bn_train, s)
+                self._fwd_finalize(u, u.bn_train, s)
                 self._fwd_post(u, s)
             t = st.get('tail')
             if t is None:
@@ -1004,8 +1023,6 @@ class _Engine:
         self._yt_ev = [None, None]      # events of THIS backward pass only (the previous one was joined before it returned; a captured
         self._x3_ev = None              # graph must not wait on an event recorded outside the capture)
         B, H, W, dc = self.B, self.H, self.W, self.dcode
-        if not self.fwd_training:
-            raise RuntimeError('UNet.backward after an eval-mode forward is not supported (BatchNorm backward uses batch statistics)')
         if tuple(self.tuning.as_dict().values()) != self._tune_key:
             # the partial-row buffers were planned for the forward's kernel structure
             raise RuntimeError('model.tuning changed between forward and backward: change it between steps (before the forward)')
@@ -1108,22 +1125,38 @@ class _Engine:
         ga, ga_ldc, gp = u.g_src
         count = float(B * u.h * u.w_)
         g = self._gp
-        if not u.fused_reduce:     # otherwise the five sums were accumulated by the epilogue of the kernel that wrote `ga`
-            _hbm('bn_bwd', 0,                      # algorithmically free: one backward pass reads g and y once (the apply pass below is charged for it)
-                 'clamd_bn_bwd_reduce', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
-                 ptr(v[0]), ptr(v[1]), ptr(u.sums), u.sum_rows, B, u.h, u.w_, u.cout_p, dc, tp, s)
         two = u.fused_reduce and u.gz_nrows > 0      # the producing launch took sum g and sum g y only: d conv-bias = sum g_z, from the apply pass
-        call('clamd_bn_bwd_finalize', ptr(u.sums), u.sum_rows, ptr(u.gamma), ptr(v[2]), ptr(v[3]), ptr(v[4]), g[u.keys[2]],
-             g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, count, s)
-        if two:
-            assert gp is None
-            _hbm('bn_bwd', self.esize * B * u.h * u.w_ * u.cout * 3,
-                 'clamd_bn_bwd_apply_sums', ptr(ga), ga_ldc, ptr(u.y), u.y_ldc, ptr(v[4]), ptr(u.gz), u.cout_p, ptr(u.gz_rows), u.gz_nrows,
-                 B, u.h, u.w_, u.cout_p, dc, s)
-        else:
+        if not u.bn_train and not u.fused_reduce:
+            # eval-mode BatchNorm (running statistics): g_z = [y>0] scale g needs no reduction -- ONE pass writes it and the rows of
+            # sum g, sum g y, sum g_z; the parameter gradients are formed off the critical chain, on the second stream, where this unit's
+            # weight gradient and its fold fix-up (which read the conv-bias gradient) follow in stream order
             _hbm('bn_bwd', self.esize * B * u.h * u.w_ * u.cout * (13 if gp is not None else 12) // 4,
-                 'clamd_bn_bwd_apply', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
-                 ptr(v[0]), ptr(v[1]), ptr(v[4]), ptr(u.gz), u.cout_p, B, u.h, u.w_, u.cout_p, dc, s)
+                 'clamd_bn_bwd_eval', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
+                 ptr(v[0]), ptr(v[1]), ptr(u.gz), u.cout_p, ptr(u.eval_rows), u.eval_nrows, B, u.h, u.w_, u.cout_p, u.cout, dc, s)
+            call('clamd_bn_bwd_eval_finalize', ptr(u.eval_rows), u.eval_nrows, 3, ptr(v[0]), ptr(v[2]), ptr(v[3]), None,
+                 g[u.keys[2]], g[u.keys[3]], g[u.keys[1]], u.cout_p, u.cout, self._wg_stream_ptr())
+        else:
+            if not u.bn_train:
+                # eval mode where the producing data-gradient launch already accumulated the sums (DESIGN.md "Frozen BatchNorm"): the apply
+                # passes of train mode with k0 = scale, k1 = k2 = 0, which the eval finalize writes from the forward's scale
+                call('clamd_bn_bwd_eval_finalize', ptr(u.sums), u.sum_rows, self.NS, ptr(v[0]), ptr(v[2]), ptr(v[3]), ptr(v[4]),
+                     g[u.keys[2]], g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, s)
+            else:
+                if not u.fused_reduce:     # otherwise the five sums were accumulated by the epilogue of the kernel that wrote `ga`
+                    _hbm('bn_bwd', 0,                      # algorithmically free: one backward pass reads g and y once (the apply pass below is charged for it)
+                         'clamd_bn_bwd_reduce', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
+                         ptr(v[0]), ptr(v[1]), ptr(u.sums), u.sum_rows, B, u.h, u.w_, u.cout_p, dc, tp, s)
+                call('clamd_bn_bwd_finalize', ptr(u.sums), u.sum_rows, ptr(u.gamma), ptr(v[2]), ptr(v[3]), ptr(v[4]), g[u.keys[2]],
+                     g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, count, s)
+            if two:
+                assert gp is None
+                _hbm('bn_bwd', self.esize * B * u.h * u.w_ * u.cout * 3,
+                     'clamd_bn_bwd_apply_sums', ptr(ga), ga_ldc, ptr(u.y), u.y_ldc, ptr(v[4]), ptr(u.gz), u.cout_p, ptr(u.gz_rows), u.gz_nrows,
+                     B, u.h, u.w_, u.cout_p, dc, s)
+            else:
+                _hbm('bn_bwd', self.esize * B * u.h * u.w_ * u.cout * (13 if gp is not None else 12) // 4,
+                     'clamd_bn_bwd_apply', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
+                     ptr(v[0]), ptr(v[1]), ptr(v[4]), ptr(u.gz), u.cout_p, B, u.h, u.w_, u.cout_p, dc, s)
         if len(u.cin_segs) == 2:
             c_seg0, c_seg0p = u.cin_segs[0]
         else:

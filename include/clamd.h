@@ -300,6 +300,22 @@ int clamd_bn_bwd_apply_sums_rows(int B, int H, int W, int Cp);
 int clamd_bn_bwd_apply_sums(const void* ga, int ga_ldc, const void* y, int y_ldc, const float* k012, void* gz, int gz_ldc,
                             float* gz_rows, int nrows, int B, int H, int W, int Cp, int dtype, void* stream);
 int clamd_rows_sum(const float* rows, int nrows, float* out, int Cp, int C, void* stream);
+/* Eval-mode form (nn.BatchNorm2d.eval(): normalised with the running statistics, clamd_bn_finalize with stats == NULL): scale and shift
+ * are constants, so g_z = [y>0] * scale * g needs no reduction in front of it and the backward is ONE streaming pass.
+ * clamd_bn_bwd_eval reads ga (+ the pooled gradient gp, routed to the first maximum of scale * y + shift of its window, as
+ * clamd_bn_bwd_apply) and y, writes g_z (channels C..Cp-1 as zero) and partial rows rows[nrows][3][Cp] of sum g, sum g y and sum g_z
+ * (nrows = clamd_bn_bwd_eval_rows(B, H, W, Cp, gp != NULL), one row per workgroup, plain stores).
+ * clamd_bn_bwd_eval_finalize adds rows 0..nrows-1 in a fixed order in fp64: d gamma = save_istd * (sum g y - save_mean * sum g),
+ * d beta = sum g, d conv-bias = sum g_z.  nsums = 3: rows of clamd_bn_bwd_eval; nsums = 5: the five-sum rows of a producing launch
+ * (clamd_conv3x3 / clamd_conv1x1 / clamd_convT2x2_dgrad with bn_sums), d conv-bias = scale * sum g [y>0] -- dbias = NULL for the two-sum
+ * form, whose bias gradient comes from clamd_bn_bwd_apply_sums.  k012 (optional) = (scale, 0, 0): the coefficients with which
+ * clamd_bn_bwd_apply / clamd_bn_bwd_apply_sums form the eval-mode g_z from such rows.  save_mean / save_istd / scale: clamd_bn_finalize's
+ * outputs of the forward.  No atomics: two runs are bit-identical. */
+int clamd_bn_bwd_eval_rows(int B, int H, int W, int Cp, int pooled);
+int clamd_bn_bwd_eval(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc, const float* scale, const float* shift,
+                      void* gz, int gz_ldc, float* rows, int nrows, int B, int H, int W, int Cp, int C, int dtype, void* stream);
+int clamd_bn_bwd_eval_finalize(const float* rows, int nrows, int nsums, const float* scale, const float* save_mean, const float* save_istd,
+                               float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C, void* stream);
 /* nn.MaxPool2d(2,2) alone (models/unet.py:12: the first layer of a DownBlock run as a stand-alone block, blocks.py; inside the UNet step
  * the pool is part of clamd_bn_apply / clamd_bn_bwd_*): x [B,H,W,ldc] -> pooled [B,H/2,W/2,ldc]; backward: gx [B,H,W,ldc] = gp at the first
  * maximum of each window (the tie rule of clamd_bn_apply and of torch's CPU kernel), 0 elsewhere.
