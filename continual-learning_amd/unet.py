@@ -18,6 +18,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import call, ptr, tune_ptr
 from .ops import PackTable, WinoPackTable, cpad
+from .plan import ALGOS, Switches, plan_net
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 
@@ -41,7 +42,7 @@ WINOGRAD24_WGRAD = 'auto'
 # redone by every output-slab workgroup (8-16x per tile at 512/1024 channels) and costs 2-3.5 VALU per fp32 MFMA; the
 # transform-free K loop runs at 0.77-0.90 of the MFMA pipe instead of 0.57-0.66 (tools/wino24g_ab.py).  The transformed
 # input (3x the activation) is kept from the forward pass and is also the x-side operand of the weight-gradient GEMM.
-# 'auto' = where the transform pass pays for itself (see _Engine.unit); False = never.
+# 'auto' = where the transform pass pays for itself (see plan.py); False = never.
 PRETRANSFORM = os.environ.get('CLAMD_PRETRANSFORM', 'auto')
 PRETRANSFORM = {'0': False, 'false': False, '1': True, 'true': True}.get(str(PRETRANSFORM).lower(), 'auto')
 # ... and those pre-transformed layers by the 2-D F(4x4,3x3) (csrc/wino44g.hip: 2.25 instead of 3 multiply-adds per output, a transformed
@@ -95,33 +96,28 @@ PACK_LATE_AT = int(os.environ.get('CLAMD_PACK_LATE_AT', '2'))      # index of th
 KERNEL_TIMING = None
 
 
+def switches():
+    """The planning switches above (plan.Switches), read now: tests and tools/step_ab.py set them as module attributes."""
+    return Switches(*(globals()[k] for k in Switches._fields))
+
+
 _TIMED_UNIT = ['', 1.0]   # conv unit being launched and the fraction of its algorithmic FLOPs the kernel executes (Winograd:
 #                         # 16/36 or 24/72); only read while KERNEL_TIMING is set (bench.py, tools/layer_table.py)
 
 
-_SECOND_STREAM = {}
+_SIDE_STREAMS = {}
 
 
-def _second_stream(dev):
-    """ONE second stream per device and process, shared by every engine: HIP multiplexes streams onto a handful of hardware
-    queues (4 by default) in creation order, and a kernel queues behind whatever shares its hardware queue -- a stream per
-    engine would sooner or later land on the queue RCCL's kernels use."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _SECOND_STREAM:
+def _side_stream(dev, n):
+    """Side stream n (2: parameter gradients, 3: their input transforms): ONE per device and process, shared by every engine: HIP
+    multiplexes streams onto a handful of hardware queues (4 by default) in creation order, and a kernel queues behind whatever shares
+    its hardware queue -- a stream per engine would sooner or later land on the queue RCCL's kernels use."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), n)
+    if key not in _SIDE_STREAMS:
         # default priority: the device offers only (normal, high), and giving either stream the high one changed nothing
         # measurable (tools/cu_steal.py, base and held-CU cases within 0.5 %)
-        _SECOND_STREAM[key] = torch.cuda.Stream(device=dev)
-    return _SECOND_STREAM[key]
-
-
-_THIRD_STREAM = {}
-
-
-def _third_stream(dev):
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _THIRD_STREAM:
-        _THIRD_STREAM[key] = torch.cuda.Stream(device=dev)
-    return _THIRD_STREAM[key]
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
+    return _SIDE_STREAMS[key]
 
 
 def _timed(tag, flops, nbytes, name, *args):
@@ -268,7 +264,8 @@ class UNet(nn.Module):
         raise RuntimeError('continual-learning_amd.UNet cannot be replicated by nn.DataParallel across devices: run one process per '
                            'GPU (torch.distributed.run) with continual-learning_amd.ddp.init_rccl + ddp.GradSync(model, optimizer)')
 
-    def forward(self, x):
+    def _engine(self, x):
+        """The engine (kernel plan and buffers) of x's shape; built on first use, one shape at a time: activations are sized for it."""
         if not x.is_cuda:
             raise RuntimeError('continual-learning_amd.UNet runs only on an MI355X GPU tensor: there is no CPU fallback')
         if x.dim() != 4 or x.shape[1] != self.in_dim:
@@ -276,12 +273,13 @@ class UNet(nn.Module):
         B, _, H, W = x.shape
         assert H % 16 == 0 and W % 16 == 0, 'input size(H, W) must be a multiple of 16 (four 2x2 pools and matching skip concats)'
         key = (B, H, W, x.device.index)
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = _Engine(self, B, H, W, x.device)
-            self._engines = {key: eng}     # one shape at a time: activations are sized for it
-        params = [p for p in self.parameters()]
-        out = _UNetFn.apply(x.contiguous().float(), eng, *params)
+        if key not in self._engines:
+            self._engines = {key: _Engine(self, B, H, W, x.device)}
+        return self._engines[key]
+
+    def forward(self, x):
+        eng = self._engine(x)
+        out = _UNetFn.apply(x.contiguous().float(), eng, *self.parameters())
         out._clamd_engine = (weakref.ref(eng), eng.generation)      # lets this package's loss write d logits where the backward pass reads it
         return out
 
@@ -289,18 +287,7 @@ class UNet(nn.Module):
     def predict(self, x):
         """``torch.max(self(x), 1)[1]`` (trainer.py:279) without materialising the logits: the arg-max over classes runs
         in the epilogue of the head kernel.  int64 [B,H,W]; every BatchNorm follows its own ``.training``."""
-        if not x.is_cuda:
-            raise RuntimeError('continual-learning_amd.UNet runs only on an MI355X GPU tensor: there is no CPU fallback')
-        if x.dim() != 4 or x.shape[1] != self.in_dim:
-            raise ValueError(f'expected input [B,{self.in_dim},H,W], got {tuple(x.shape)}')
-        B, _, H, W = x.shape
-        assert H % 16 == 0 and W % 16 == 0, 'input size(H, W) must be a multiple of 16 (four 2x2 pools and matching skip concats)'
-        key = (B, H, W, x.device.index)
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = _Engine(self, B, H, W, x.device)
-            self._engines = {key: eng}
-        return eng.forward(x.contiguous().float(), [p for p in self.parameters()], predict=True)
+        return self._engine(x).forward(x.contiguous().float(), list(self.parameters()), predict=True)
 
     def extra_repr(self):
         return f'num_classes={self.num_classes}, in_dim={self.in_dim}, conv_dim={self.conv_dim}, compute={self.compute_dtype}'
@@ -345,9 +332,19 @@ class _FoldSource:
         self.y, self.cout_p, self.vec, self.apply_in_filters = y, pitch, [scale, shift], False
 
 
+def _sums_into(c):
+    """(y, sums, rows) arguments of a data-gradient launch that accumulates the BatchNorm-backward sums of unit c (plan.Unit.sums_by), or none."""
+    return (ptr(c.y), ptr(c.sums), c.sum_rows) if c is not None else (None, None, 0)
+
+
 class _Conv:
     """One Conv3x3 -> ReLU -> BatchNorm unit and everything it needs in both directions."""
-    pass
+    # read-only views of the plan that bench.py reads (nothing in this package uses them)
+    wino = property(lambda u: u.f.wino)
+    w24 = property(lambda u: u.plan.fwd in ('f24', 'f24_direct', 'f24_pre', 'f44_pre'))
+    f44 = property(lambda u: u.plan.fwd == 'f44_pre')
+    pre_f = property(lambda u: u.f.pre)
+    pre_d = property(lambda u: u.d is not None and u.d.pre)
 
 
 class _Engine:
@@ -361,7 +358,6 @@ class _Engine:
         #                                           multi-GB activation buffers to the cyclic garbage collector
         self.B, self.H, self.W, self.dev = B, H, W, device
         self.dcode, self.tdtype = _DTYPES[model.compute_dtype]
-        self.wino = bool(WINOGRAD) and self.dcode == _lib.F32
         self.pack_late_stream, self.pack_late_at = bool(PACK_LATE_STREAM), int(PACK_LATE_AT)
         self.tuning = model.tuning
         self.NS = lib.clamd_bn_bwd_nsums()
@@ -396,262 +392,143 @@ class _Engine:
 
         # ---- geometry: stages -> conv units ----------------------------------------------------------
         self.x_in = act(0, cpad(model.in_dim))
-        convs, self.stages = [], []
+        self.stages = []
         C = [d, 2 * d, 4 * d, 8 * d]                      # encoder output channels, levels 0..3
         self.cat = [act(l, 2 * cpad(C[l])) for l in range(4)]
         self.gcat = [act(l, 2 * cpad(C[l])) for l in range(4)]
         self.pool = [act(l + 1, cpad(C[l])) for l in range(4)]
         self.gpool = [act(l + 1, cpad(C[l])) for l in range(4)]
 
-        def unit(prefix, ci, bi, level, cin_segs, cout, xin, xin_ldc, first_of_net=False):
+        def unit(prefix, ci, bi, p, xin):
             u = _Conv()
-            u.name = f'{prefix}.{ci}'
+            u.plan, u.name = p, p.name
+            u.f, u.d, u.g = ALGOS[p.fwd], p.dgrad and ALGOS[p.dgrad], ALGOS[p.wgrad]      # kernel families of the three directions
             u.w, u.b = named[f'{prefix}.{ci}.weight'], named[f'{prefix}.{ci}.bias']
             u.gamma, u.beta = named[f'{prefix}.{bi}.weight'], named[f'{prefix}.{bi}.bias']
             u.rm, u.rv = bufs[f'{prefix}.{bi}.running_mean'], bufs[f'{prefix}.{bi}.running_var']
             u.nbt = bufs[f'{prefix}.{bi}.num_batches_tracked']
-            u.bn = mods[f'{prefix}.{bi}']                          # its .training is the unit's BatchNorm mode (read every forward)
-            u.bn_train = True
+            u.bn, u.bn_train = mods[f'{prefix}.{bi}'], True         # its .training is the unit's BatchNorm mode (read every forward)
             u.keys = (f'{prefix}.{ci}.weight', f'{prefix}.{ci}.bias', f'{prefix}.{bi}.weight', f'{prefix}.{bi}.bias')
-            u.level, u.h, u.w_ = level, H >> level, W >> level
-            u.cin_segs = cin_segs                                  # [(logical, physical), ...] one or two segments
-            u.cin = sum(s[0] for s in cin_segs)
-            u.cin_p = sum(s[1] for s in cin_segs)
-            u.cout, u.cout_p = cout, cpad(cout)
-            u.xin, u.xin_ldc = xin, xin_ldc
-            u.first = first_of_net
-            # first conv (Cin = 3): 3x3 neighbourhood folded into 27 (->32) channels, conv runs as a pointwise GEMM
-            u.im2col = first_of_net and 9 * u.cin <= cpad(9 * u.cin) == u.cin_p
-            u.y = act(level, u.cout_p)
-            u.gz = act(level, u.cout_p)
-            # Winograd tiles are 2x2 outputs inside 8x16 / 16x16-pixel workgroup tiles: nothing to gain below 8x8 images
-            u.wino = self.wino and not u.im2col and (u.h | u.w_) % 2 == 0 and min(u.h, u.w_) >= 8
-            u.w24 = u.wino and bool(WINOGRAD24) and u.w_ % 4 == 0          # forward / data gradient by F(2x4,3x3)
-            u.w24g = u.w24 and (min(u.h, u.w_) >= 64 if WINOGRAD24_WGRAD == 'auto' else bool(WINOGRAD24_WGRAD))   # ... weight gradient
-            # ... data gradient: F(2x4) tiles are 256 pixels x 64 (input) channels; a launch with at most half a chip of them runs
-            # the F(2x2) kernel instead, whose 128-pixel tiles give twice the work items (1024 -> 512 @16x16, the data gradient of
-            # dec1.block.0: 128 items, 238 us against 160 us, tools/wino24_ab.py)
-            items24 = B * ((u.h + 7) // 8 * ((u.w_ + 31) // 32) if u.w_ >= 32 else (u.h + 15) // 16 * ((u.w_ + 15) // 16)) * ((u.cin_p + 63) // 64)
-            u.w24d = u.w24 and not (2 * items24 <= (torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == 'cuda' else 256))
-            # pre-transformed operands (wino24g.hip).  Weight gradient: both channel counts multiples of 256 (a wave owns a 128 x 128
-            # block, a workgroup 256 x 256).  Forward: >= 256 input channels, and either the image is needed by the weight gradient
-            # anyway or there are enough output channels to amortise the transform pass (its cost grows with Cin, the kernel's gain
-            # with Cin x Cout: 512 -> 256 @64x64 loses 6 %, 256 -> 128 @128x128 26 %, tools/wino24g_ab.py).  Data gradient: the
-            # same with the roles of the channel counts exchanged; the transformed gradient is used once and not kept.
-            pt = PRETRANSFORM
-            # F(4x4,3x3) applies where the launch fills the chip with (16x32-pixel tile block, 64-channel slab) work items (WINOGRAD44)
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == 'cuda' else 256
-            blocks44 = B * u.h * u.w_ // 512                       # FULL tile blocks (a 16x16 image fills half of a 32x16 block)
-            ok44 = lambda slab_ch, in_ch: (bool(WINOGRAD44) and u.h % 4 == 0 and u.w_ % 4 == 0 and slab_ch % 64 == 0
-                                           and (WINOGRAD44 is True or blocks44 * (slab_ch // 64) >= ncu)
-                                           and lib.clamd_winograd44_input_elems(B, u.h, u.w_, in_ch) * 4 < (1 << 32))
-            u.pre_w = bool(pt) and u.w24 and u.cin_p % 256 == 0 and u.cout_p % 256 == 0
-            u.pre_f = bool(pt) and u.w24 and u.cin_p >= 64 and u.cout_p % 64 == 0 and (
-                pt is True or (u.cin_p >= 256 and (u.pre_w or 2 * u.cout_p > u.cin_p)) or (u.cin_p >= 128 and u.cout_p >= 2 * u.cin_p))
-            # one buffer descriptor spans a whole transformed tensor: below 2^32 bytes (config 2: <= 0.4 GB; 512 x 512 bs32 fp32: 3.2 GB)
-            fits = lambda c: lib.clamd_winograd24_input_elems(B, u.h, u.w_, c) * 4 < (1 << 32)
-            u.pre_f = u.pre_f and fits(u.cin_p)
-            u.pre_w = u.pre_w and u.pre_f and lib.clamd_wgrad_winograd24_pre_operand_elems(B, u.h, u.w_, u.cout_p) * 4 // 24 < (1 << 32)
-            u.pre_d = bool(pt) and u.w24d and not first_of_net and u.cout_p >= 64 and u.cin_p % 64 == 0 and fits(u.cout_p) and (
-                pt is True or (u.cout_p >= 256 and (2 * u.cin_p > u.cout_p or (2 * u.cin_p == u.cout_p and u.cin_p >= 256))))
-            # ... the 128-channel layers too (round 5: enc2.block.4, enc3.block.1, dec4 at config 2): their weight gradients ran the
-            # in-kernel-transform kernel at 0.42-0.50 of the pipe; with channel counts that are multiples of 128 the plane GEMM runs them as
-            # 128 x 128 wave tiles (wave-level stream-K) on the forward image, so forward AND weight gradient go pre-transformed F(4x4) and the
-            # BatchNorm in front is applied by the transform (FOLD_BN_INTO_TRANSFORM) instead of by folded filters and a border-class table
-            if (pt == 'auto' and WINOGRAD44 and u.w24 and not (u.pre_f and u.pre_w) and min(u.cin_p, u.cout_p) >= 128
-                    and u.cin_p % 128 == 0 and u.cout_p % 128 == 0 and ok44(u.cout_p, u.cin_p) and NARROW_PRE_WGRAD):
-                u.pre_f = u.pre_w = True
-            u.f44 = u.pre_f and ok44(u.cout_p, u.cin_p)            # forward (and, with pre_w, the weight gradient: it reads the forward image)
-            # ... and the data gradients of the NARROW layers whose launch has at least 128 output (= this unit's input) channels: transform of
-            # the gradient + transform-free F(4x4) loop against the in-kernel-transform F(2x4) kernel, tools/wino44_narrow_ab.py: 64 -> 128
-            # @256x256 1.07x, 128 -> 128 @128x128 1.08x, 128 -> 256 @128x128 1.26x, 256 -> 128 @64x64 1.21x (128 -> 64 and 64 -> 64: 0.83-0.85x)
-            if (pt == 'auto' and not u.pre_d and u.w24d and not first_of_net and u.cin_p >= 128 and u.cout_p >= 64 and u.cin_p % 64 == 0
-                    and WINOGRAD44 and ok44(u.cin_p, u.cout_p)):
-                u.pre_d = True
-            u.d44 = u.pre_d and ok44(u.cin_p, u.cout_p)            # data gradient
-            if u.f44 and u.pre_w:
-                u.pre_w = lib.clamd_wgrad_winograd44_pre_operand_elems(B, u.h, u.w_, u.cout_p) * 4 // 36 < (1 << 32)
-            u.vx = torch.empty((lib.clamd_winograd44_input_elems if u.f44 else lib.clamd_winograd24_input_elems)(B, u.h, u.w_, u.cin_p),
-                               dtype=torch.float32, device=dev) if u.pre_f else None
-            # 64 input channels (8 chunks per tile): the in-kernel-transform kernel with the filters loaded straight into the operand
-            # registers (wino24h_kernel) is 4-6 % faster there and 1-4 % slower on longer K loops (tools/wino24h_ab.py)
-            u.direct_f = NARROW_DIRECT and u.w24 and not u.pre_f and u.cin_p == 64 and u.cout_p % 64 == 0
-            u.direct_d = NARROW_DIRECT and u.w24d and not u.pre_d and not first_of_net and u.cout_p == 64 and u.cin_p % 64 == 0
-            ntap = 1 if u.im2col else ((36 if u.f44 else (24 if u.w24 else 16)) if u.wino else 9)   # Winograd: [Cin_p/8][16|24|36][Cout_p][8] transformed filters
-            ntap_d = (36 if u.d44 else (24 if u.w24d else 16)) if u.wino else ntap
-            u.wf = torch.zeros(ntap * u.cout_p * u.cin_p, dtype=T, device=dev)
-            u.wd = None if first_of_net else torch.zeros(ntap_d * u.cin_p * u.cout_p, dtype=T, device=dev)
+            u.level, u.h, u.w_, u.cin_p, u.cout, u.cout_p = p.level, p.h, p.w, p.cin_p, p.cout, p.cout_p
+            u.cin_segs, u.cin = list(p.cin_segs), sum(s[0] for s in p.cin_segs)      # [(logical, physical), ...] one or two segments
+            u.xin, u.xin_ldc = xin, xin.shape[-1]
+            u.y, u.gz = act(p.level, u.cout_p), act(p.level, u.cout_p)
+            u.vx = torch.empty(getattr(lib, u.f.x_elems)(B, u.h, u.w_, u.cin_p), dtype=torch.float32, device=dev) if u.f.pre else None
+            u.wf = torch.zeros(u.f.taps * u.cout_p * u.cin_p, dtype=T, device=dev)      # Winograd: [Cin_p/8][16|24|36][Cout_p][8] transformed
+            u.wd = None if u.d is None else torch.zeros(u.d.taps * u.cin_p * u.cout_p, dtype=T, device=dev)
             u.bias_p = torch.zeros(u.cout_p, dtype=torch.float32, device=dev)
             u.vec = torch.zeros(7, u.cout_p, dtype=torch.float32, device=dev)   # scale, shift, mean, istd, k0, k1, k2
-            u.m_fastest = 1 if 9 * u.cout_p > B * u.h * u.w_ else 0
-            convs.append(u)
+            u.m_fastest, u.y_ldc = (1 if 9 * u.cout_p > B * u.h * u.w_ else 0), u.cout_p
+            u.consumer = u.sum_src = u.fold_src = u.fold_a = None             # BatchNorm placement: wired from the plan below
+            u.fused_reduce = p.sums_by is not None
+            u.apply_folded = u.apply_in_filters = u.fold_on = u.pool_fold = False
             return u
 
-        table = model._table
-        prev = (self.x_in, self.x_in.shape[-1], [(model.in_dim, cpad(model.in_dim))])
-        for k in range(4):                                         # encoders
-            st = table[k]
+        ncu = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == 'cuda' else 256
+        self.plan = plan_net(model._table, B, H, W, self.dcode, switches(), ncu)
+        plans = iter(self.plan)
+        tails = {}
+        xin, g_in = self.x_in, None                                # the first convolution's input (and, at enc1, no input gradient)
+        for i, st in enumerate(model._table):
             pre = st['name'] + ('.block' if st['wrapped'] else '')
-            (c0, b0, cin, cout), (c1, b1, _, _) = st['convs']
-            ua = act(k, cpad(cout))
-            a = unit(pre, c0, b0, k, prev[2], cout, prev[0], prev[1], first_of_net=(k == 0))
-            a.out, a.out_ldc, a.pooled, a.g_out, a.g_out_ldc, a.g_pool = ua, ua.shape[-1], None, None, None, None
-            b = unit(pre, c1, b1, k, [(cout, cpad(cout))], cout, ua, ua.shape[-1])
-            b.out, b.out_ldc, b.pooled = self.cat[k], self.cat[k].shape[-1], self.pool[k]
-            a.g_in = None if k == 0 else self.gpool[k - 1]           # dgrad target of conv a (grad w.r.t. pooled input)
-            b.g_in = act(k, cpad(cout))                             # grad w.r.t. ua
-            a.g_src = (b.g_in, b.g_in.shape[-1], None)               # where conv a's BN-output gradient comes from
-            b.g_src = (self.gcat[k], self.gcat[k].shape[-1], self.gpool[k])
-            b.consumer, a.fused_reduce = (a, True) if self._fuse_sums(b) else (None, False)
-            a.consumer, b.fused_reduce = None, False                # a's dgrad feeds a pooled / concat gradient: separate reduce
-            self.stages.append(dict(kind='enc', convs=(a, b)))
-            prev = (self.pool[k], self.pool[k].shape[-1], [(cout, cpad(cout))])
-        spec = [(8 * d, 16 * d, 8 * d), (16 * d, 8 * d, 4 * d), (8 * d, 4 * d, 2 * d), (4 * d, 2 * d, d), (2 * d, d, None)]
-        for j in range(5):                                         # decoders + last
-            st = table[4 + j]
-            pre = st['name'] + ('.block' if st['wrapped'] else '')
-            level = 4 - j
-            (c0, b0, cin, mid), (c1, b1, _, _) = st['convs']
-            if j == 0:
-                xin, segs, g_in_a = self.pool[3], [(8 * d, cpad(8 * d))], self.gpool[3]
-            else:
-                half = C[level]
-                xin, segs, g_in_a = self.cat[level], [(half, cpad(half)), (half, cpad(half))], self.gcat[level]
-            ua, ub = act(level, cpad(mid)), act(level, cpad(mid))
-            a = unit(pre, c0, b0, level, segs, mid, xin, xin.shape[-1])
-            a.out, a.out_ldc, a.pooled = ua, ua.shape[-1], None
-            b = unit(pre, c1, b1, level, [(mid, cpad(mid))], mid, ua, ua.shape[-1])
-            b.out, b.out_ldc, b.pooled = ub, ub.shape[-1], None
-            a.g_in, b.g_in = g_in_a, act(level, cpad(mid))
-            g_ub = act(level, cpad(mid))
-            a.g_src = (b.g_in, b.g_in.shape[-1], None)
+            (c0, b0, _, mid), (c1, b1, _, _) = st['convs']
+            pa, pb = next(plans), next(plans)
+            k = pa.level
+            if i > 4:                                              # behind dec1: the concat [skip | up-convolution] of this level
+                xin, g_in = self.cat[k], self.gcat[k]
+            ua = act(k, cpad(mid))
+            a, b = unit(pre, c0, b0, pa, xin), unit(pre, c1, b1, pb, ua)
+            a.out, a.pooled, a.g_in = ua, None, g_in              # g_in: dgrad target of conv a
+            b.g_in = act(k, cpad(mid))                            # grad w.r.t. ua
+            a.g_src = (b.g_in, b.g_in.shape[-1], None)            # where conv a's BN-output gradient comes from
+            if st['tail'] is None:     # encoder: the block output goes to the skip half of the concat buffer and, pooled, to the next stage
+                b.out, b.pooled = self.cat[k], self.pool[k]
+                b.g_src = (self.gcat[k], self.gcat[k].shape[-1], self.gpool[k])
+                a.out_ldc, b.out_ldc = a.out.shape[-1], b.out.shape[-1]
+                xin, g_in = self.pool[k], self.gpool[k]
+                self.stages.append(dict(kind='enc', convs=(a, b)))
+                continue
+            b.out, b.pooled, g_ub = act(k, cpad(mid)), None, act(k, cpad(mid))
             b.g_src = (g_ub, g_ub.shape[-1], None)
-            b.consumer, a.fused_reduce = (a, True) if self._fuse_sums(b) else (None, False)
-            a.consumer, b.fused_reduce = None, FUSE_BN_SUMS is True  # b's gradient comes from the tail's data-gradient kernel
+            a.out_ldc, b.out_ldc = a.out.shape[-1], b.out.shape[-1]
             kind, ti, tcin, tcout = st['tail']
-            tail = _Conv()
-            tail.kind = kind
+            tail = tails[f'{pre}.{ti}'] = _Conv()
             tail.w, tail.b = named[f'{pre}.{ti}.weight'], named[f'{pre}.{ti}.bias']
             tail.keys = (f'{pre}.{ti}.weight', f'{pre}.{ti}.bias')
-            tail.cin, tail.cin_p, tail.cout = tcin, cpad(tcin), tcout
-            tail.x, tail.g_x, tail.level = ub, g_ub, level
-            tail.consumer = b if FUSE_BN_SUMS is True else None
+            tail.cin, tail.cin_p, tail.cout, tail.cout_p = tcin, cpad(tcin), tcout, cpad(tcout)
+            tail.kind, tail.x, tail.g_x, tail.level = kind, b.out, g_ub, k
+            tail.consumer, tail.fold_b = None, None
+            taps = 4 if kind == 'convT' else 1                     # ConvTranspose2d 2x2 / the 1x1 head
+            tail.wf = torch.zeros(taps * tail.cout_p * tail.cin_p, dtype=T, device=dev)
+            tail.wd = torch.zeros(tail.cin_p * taps * tail.cout_p, dtype=T, device=dev)
             if kind == 'convT':
-                tail.cout_p = cpad(tcout)
-                tail.wf = torch.zeros(4 * tail.cout_p * tail.cin_p, dtype=T, device=dev)
-                tail.wd = torch.zeros(tail.cin_p * 4 * tail.cout_p, dtype=T, device=dev)
-                up = self.cat[level - 1]
+                up = self.cat[k - 1]
                 tail.y_slice = up[..., tail.cout_p:]               # second half of the concat buffer one level up
-                tail.gy_slice = self.gcat[level - 1][..., tail.cout_p:]
+                tail.gy_slice = self.gcat[k - 1][..., tail.cout_p:]
                 tail.y_ldc = up.shape[-1]
             else:
-                tail.cout_p = self.Kp
-                tail.wf = torch.zeros(tail.cout_p * tail.cin_p, dtype=T, device=dev)
-                tail.wd = torch.zeros(tail.cin_p * tail.cout_p, dtype=T, device=dev)
                 self.dl = act(0, self.Kp)
             tail.bias_p = torch.zeros(tail.cout_p, dtype=torch.float32, device=dev)
             self.stages.append(dict(kind='dec', convs=(a, b), tail=tail))
-        self.convs = convs
+        self.convs = convs = [u for st in self.stages for u in st['convs']]
+        self.tails = list(tails.values())                          # ConvTranspose2d x 4, the 1x1 head
+        # ---- BatchNorm placement (plan.Unit): one direction only -- a cycle between units would keep the engine's buffers alive until the
+        # garbage collector runs
+        by = {u.name: u for u in convs}
         for u in convs:
-            u.apply_folded, u.fold_src = False, None
-        for st in self.stages:
-            a, b = st['convs']
-            # a's BatchNorm output `ua` is read by b's convolution (forward) and by b's weight gradient only: when both run on b's
-            # transformed input, the affine is applied by the transform itself and a's bn_apply pass (and `ua`) disappears
-            if FOLD_BN_INTO_TRANSFORM and b.pre_f and b.pre_w and a.pooled is None and b.xin is a.out:
-                a.apply_folded, b.fold_src = True, a
-        for st in self.stages:
-            a, b = st['convs']
-            # ... and where b transforms inside its kernel (or is a bf16 direct kernel): the algebraic fold of bnfold.hip
-            b.fold_a, a.fold_a, a.fold_on, b.fold_on, a.apply_in_filters, b.apply_in_filters = None, None, False, False, False, False
-            if (FOLD_BN_INTO_FILTERS
-                    and not a.apply_folded and not b.pre_f and a.pooled is None and b.xin is a.out and len(b.cin_segs) == 1
-                    and min(b.h, b.w_) >= 2 and b.cin_p <= FOLD_FILTERS_MAX_CHANNELS):
-                b.fold_a = a      # one direction only: a cycle between units would keep the engine's buffers alive until the garbage collector runs
-                b.cb = torch.zeros(9, b.cout_p, dtype=torch.float32, device=dev)
-        for u in convs:
-            u.pool_fold, u.y_ldc = False, u.cout_p
-        for k in range(3):
-            # ... and the output of an encoder block with two narrow F(2x4) readers (FOLD_POOLED): static (fp32 Winograd kernels take the
-            # border-class table under every tuning), because the raw tensor then lives where the normalised one would
-            b, nxt = self.stages[k]['convs'][1], self.stages[k + 1]['convs'][0]
-            dec = next((st_['convs'][0] for st_ in self.stages if st_['kind'] == 'dec' and st_['convs'][0].xin is self.cat[k]), None)
-            ok = (FOLD_POOLED and FOLD_BN_INTO_FILTERS and self.dcode == _lib.F32 and dec is not None and nxt.xin is self.pool[k]
-                  and all(c.w24 and not c.pre_f and c.fold_a is None and c.cin_p <= FOLD_FILTERS_MAX_CHANNELS and min(c.h, c.w_) >= 2
-                          and all(lg == ph for lg, ph in c.cin_segs) for c in (nxt, dec))
-                  and b.w24 and not b.pre_f and b.cout == b.cout_p and len(dec.cin_segs) == 2
-                  and dec.cin_segs[0] == (b.cout, b.cout_p))
-            if not ok:
-                continue
-            b.pool_fold, b.apply_in_filters = True, True
-            b.y, b.y_ldc = self.cat[k], self.cat[k].shape[-1]               # conv+ReLU output straight into the skip half of the concat buffer
-            comp = torch.zeros(2, dec.cin_p, dtype=torch.float32, device=dev)  # scale / shift over the decoder conv's input: [block | up-conv]
-            comp[0, b.cout_p:] = 1.0
-            vec = b.vec
-            b.vec = [comp[0, :b.cout_p], comp[1, :b.cout_p]] + [vec[i] for i in range(2, 7)]     # rows 4-6 (k0, k1, k2) stay contiguous
-            nxt.fold_a = _FoldSource(self.pool[k], self.pool[k].shape[-1], b.vec[0], b.vec[1])
-            dec.fold_a = _FoldSource(self.cat[k], self.cat[k].shape[-1], comp[0], comp[1])
-            for c in (nxt, dec):
-                c.cb = torch.zeros(9, c.cout_p, dtype=torch.float32, device=dev)
-        for st in self.stages:
-            t = st.get('tail')
-            if t is None:
-                continue
-            # ... and the 1x1 head behind the last BatchNorm: pointwise, no border classes -- in every compute dtype
-            t.fold_b = None
-            b = st['convs'][1]
-            if (FOLD_BN_INTO_FILTERS and t.kind == 'head' and b.pooled is None and t.x is b.out
-                    and b.cout_p <= FOLD_FILTERS_MAX_CHANNELS):
-                t.fold_b = b
-                b.apply_in_filters = True
+            p = u.plan
+            if p.sums_by is not None:      # that launch's epilogue accumulates u's five BatchNorm-backward sums
+                u.sum_src = by.get(p.sums_by) or tails[p.sums_by]
+                u.sum_src.consumer = u
+            if p.fold_src is not None:     # u's input transform applies the BatchNorm in front: its bn_apply pass (and output) disappear
+                u.fold_src = by[p.fold_src]
+                u.fold_src.apply_folded = True
+            if p.fold_a is not None:       # the BatchNorm in front lives in u's filters and border-class bias table (bnfold.hip)
+                u.fold_a = by[p.fold_a]
+            if p.pool_fold is not None:    # an encoder block's output: conv+ReLU straight into the skip half of the concat buffer
+                k, (nxt, dec) = u.level, (by[n] for n in p.pool_fold)
+                u.pool_fold, u.apply_in_filters, u.y, u.y_ldc = True, True, self.cat[k], self.cat[k].shape[-1]
+                comp = torch.zeros(2, dec.cin_p, dtype=torch.float32, device=dev)  # scale / shift over the decoder conv's input: [block | up-conv]
+                comp[0, u.cout_p:] = 1.0
+                u.vec = [comp[0, :u.cout_p], comp[1, :u.cout_p]] + list(u.vec[2:])     # rows 4-6 (k0, k1, k2) stay contiguous
+                nxt.fold_a = _FoldSource(self.pool[k], self.pool[k].shape[-1], u.vec[0], u.vec[1])
+                dec.fold_a = _FoldSource(self.cat[k], self.cat[k].shape[-1], comp[0], comp[1])
+            if p.head_fold:                # the 1x1 head behind the last BatchNorm takes it in its filters and bias
+                t = self.stages[-1]['tail']
+                t.fold_b, u.apply_in_filters = u, True
                 t.bias_fold = torch.zeros(t.cout_p, dtype=torch.float32, device=dev)
+        for u in [c for c in convs if c.fold_a is not None]:      # a fold reader: the border-class bias table of its epilogue
+            u.cb = torch.zeros(9, u.cout_p, dtype=torch.float32, device=dev)
         nfw = max([lib.clamd_bn_fold_wgrad_workspace_bytes(B, u.cout_p) // 4 for u in convs if u.fold_a is not None] + [0])
         self.fold_ws = torch.empty(nfw, dtype=torch.float32, device=dev) if nfw else None
-        for s in self.stages:
-            t = s.get('tail')
-            if t is not None and t.consumer is not None:
-                t.consumer.sum_src = t          # that unit's five BN-backward sums come from the tail's data-gradient launch
         self._tune_key = None
         self._plan_stat_rows()
-        self.nbts = [u.nbt for u in convs]
-        # split-K slabs of the weight-gradient kernels
         ws = 0
-        for u in convs:
-            ws = max(ws, lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_CONV3, B, u.h, u.w_, u.cout_p, u.cin_p, self.dcode))
-            ws = max(ws, lib.clamd_channel_sum_workspace_bytes(u.cout_p))
-            if u.wino:
-                ws = max(ws, lib.clamd_wgrad_winograd_workspace_bytes(u.cout_p, u.cin_p))
-            if u.w24g:
-                ws = max(ws, lib.clamd_wgrad_winograd24_workspace_bytes(u.cout_p, u.cin_p))
-            if u.pre_w:
-                ws = max(ws, (lib.clamd_wgrad_winograd44_pre_workspace_bytes if u.f44 else lib.clamd_wgrad_winograd24_pre_workspace_bytes)(
-                    B, u.h, u.w_, u.cout_p, u.cin_p))
-        for s in self.stages:
-            t = s.get('tail')
-            if t is not None:
-                mode = _lib.WGRAD_UP2 if t.kind == 'convT' else _lib.WGRAD_PW
-                rp, cp_ = (t.cin_p, t.cout_p) if t.kind == 'convT' else (t.cout_p, t.cin_p)
-                ws = max(ws, lib.clamd_wgrad_workspace_bytes(mode, B, H >> t.level, W >> t.level, rp, cp_, self.dcode))
+        for u in convs:      # split-K slabs of the weight-gradient kernels: at least the direct kernel's for every unit, whatever the plan
+            ws = max(ws, lib.clamd_channel_sum_workspace_bytes(u.cout_p), u.g.wg_ws(lib, B, u.h, u.w_, u.cout_p, u.cin_p, self.dcode),
+                     ALGOS['igemm'].wg_ws(lib, B, u.h, u.w_, u.cout_p, u.cin_p, self.dcode))
+        for t in self.tails:
+            mode = _lib.WGRAD_UP2 if t.kind == 'convT' else _lib.WGRAD_PW
+            rp, cp_ = (t.cin_p, t.cout_p) if t.kind == 'convT' else (t.cout_p, t.cin_p)
+            ws = max(ws, lib.clamd_wgrad_workspace_bytes(mode, B, H >> t.level, W >> t.level, rp, cp_, self.dcode))
         self.ws = torch.empty(ws // 4 + 16, dtype=torch.float32, device=dev)
         # scratch of the pre-transformed kernels: the transformed gradient of the data-gradient launch (main stream) and the
         # gradient-side operand of the weight-gradient GEMM (second stream); launches on one stream are serialised, so one each
-        nvg = max([(lib.clamd_winograd44_input_elems if u.d44 else lib.clamd_winograd24_input_elems)(B, u.h, u.w_, u.cout_p) for u in convs if u.pre_d] + [0])
-        nyt = max([(lib.clamd_wgrad_winograd44_pre_operand_elems if u.f44 else lib.clamd_wgrad_winograd24_pre_operand_elems)(B, u.h, u.w_, u.cout_p)
-                   for u in convs if u.pre_w] + [0])
+        nvg = max([getattr(lib, u.d.x_elems)(B, u.h, u.w_, u.cout_p) for u in convs if u.d is not None and u.d.pre] + [0])
+        nyt = max([getattr(lib, u.g.wg_elems)(B, u.h, u.w_, u.cout_p) for u in convs if u.g.pre] + [0])
         self.vg = torch.empty(nvg, dtype=torch.float32, device=dev) if nvg else None
         self.yt = torch.empty(nyt, dtype=torch.float32, device=dev) if nyt else None
         # third stream + a second operand buffer: the transform of unit u runs while the GEMM of unit u+1 still reads the other buffer
-        self.x3_stream = (_third_stream(dev) if (WGRAD_XFORM_STREAM and WGRAD_STREAM and dev.type == 'cuda' and (nyt or nfw)) else None)
+        self.x3_stream = (_side_stream(dev, 3) if (WGRAD_XFORM_STREAM and WGRAD_STREAM and dev.type == 'cuda' and (nyt or nfw)) else None)
         self.yt2 = torch.empty(nyt, dtype=torch.float32, device=dev) if (nyt and self.x3_stream is not None) else None
         self._yt_flip = 0
         self._yt_ev = [None, None]
         self._x3_ev = None
-        self.wg_stream = _second_stream(dev) if (WGRAD_STREAM and dev.type == 'cuda') else None
+        self.wg_stream = _side_stream(dev, 2) if (WGRAD_STREAM and dev.type == 'cuda') else None
         self._wg_used = False
         self._pack_pending = 0
         self.ws_bytes = ws
         self._build_pack_table()
-        self._ptrs = None
 
     # ------------------------------------------------------------------------------------------ statistics rows
     def _plan_stat_rows(self):
@@ -662,61 +539,47 @@ class _Engine:
         if key == self._tune_key:
             return
         self._tune_key = key
-        B, dc, tn = self.B, self.dcode, self.tuning
+        B, dc, tn, lib = self.B, self.dcode, self.tuning, _lib.load()
         rows = _lib.stat_rows
-        sizes = []
-        for u in self.convs:      # which kernel runs a fold candidate depends on the tuning: F(2x4) Winograd / the persistent direct kernel take the table
-            u.fold_on = u.fold_a is not None and (u.w24 if u.wino else
-                                                  bool(_lib.load().clamd_conv3x3_border_bias_ok(B, u.h, u.w_, u.cin_p, u.cout_p, dc, tune_ptr(tn))))
+        sizes, esz = [], []
+        for u in self.convs:
+            # which kernel runs a fold candidate depends on the tuning: F(2x4) Winograd / the persistent direct kernel take the table
+            bb = u.f.border_bias
+            u.fold_on = u.fold_a is not None and (bool(lib.clamd_conv3x3_border_bias_ok(B, u.h, u.w_, u.cin_p, u.cout_p, dc, tune_ptr(tn)))
+                                                  if bb is None else bb)
             if u.fold_a is not None:
                 u.fold_a.apply_in_filters = u.fold_on      # the producer's bn_apply pass is skipped
-        for u in self.convs:
             u.gz_nrows = 0
-            if u.im2col:
-                r = rows(_lib.OP_CONV1X1, B, u.h, u.w_, u.cin_p, u.cout_p, dc)
-            elif u.wino:
-                r = rows(_lib.OP_CONV3X3_WINOGRAD44 if u.f44 else (_lib.OP_CONV3X3_WINOGRAD24 if u.w24 else _lib.OP_CONV3X3_WINOGRAD),
-                         B, u.h, u.w_, u.cin_p, u.cout_p, dc, tuning=tn)
-            else:
-                r = rows(_lib.OP_CONV3X3, B, u.h, u.w_, u.cin_p, u.cout_p, dc, tuning=tn)
-            u.stat_rows_launch = r
-            u.stat_rows = r
-            if u.fused_reduce:
-                src = getattr(u, 'sum_src', None)
-                if src is None:       # the 3x3 data-gradient launch of the next conv of this stage (K = its output channels)
-                    b = next(c for c in self.convs if c.consumer is u)
-                    u.sum_rows = rows(_lib.OP_CONV3X3, B, b.h, b.w_, b.cout_p, b.cin_p, dc, fused_bn=True, tuning=tn)
-                    # the persistent bf16 kernel takes sum g and sum g y only: the conv-bias gradient then comes from the apply pass
-                    if _lib.load().clamd_conv3x3_bn_sums(B, b.h, b.w_, b.cout_p, b.cin_p, dc, tune_ptr(tn)) == 2:
-                        u.gz_nrows = _lib.load().clamd_bn_bwd_apply_sums_rows(B, u.h, u.w_, u.cout_p)
-                elif src.kind == 'head':
-                    u.sum_rows = rows(_lib.OP_CONV1X1, B, u.h, u.w_, src.cout_p, src.cin_p, dc, fused_bn=True)
-                else:                 # ConvTranspose2d data gradient: the launch runs on the convT INPUT grid (= this unit's)
-                    u.sum_rows = rows(_lib.OP_CONVT2X2_DGRAD, B, u.h, u.w_, src.cin_p, src.cout_p, dc, fused_bn=True)
-            else:
+            u.stat_rows = rows(u.f.stat_op, B, u.h, u.w_, u.cin_p, u.cout_p, dc, tuning=tn)
+            src = u.sum_src
+            if src is None:
                 u.sum_rows = rows(_lib.OP_BN_BWD_REDUCE, B, u.h, u.w_, 1 if u.g_src[2] is not None else 0, u.cout_p, dc, tuning=tn)
+            elif not hasattr(src, 'kind'):     # the 3x3 data-gradient launch of the next conv of this stage (K = its output channels)
+                u.sum_rows = rows(src.d.stat_op, B, src.h, src.w_, src.cout_p, src.cin_p, dc, fused_bn=True, tuning=tn)
+                # the persistent bf16 kernel takes sum g and sum g y only: the conv-bias gradient then comes from the apply pass
+                if lib.clamd_conv3x3_bn_sums(B, src.h, src.w_, src.cout_p, src.cin_p, dc, tune_ptr(tn)) == 2:
+                    u.gz_nrows = lib.clamd_bn_bwd_apply_sums_rows(B, u.h, u.w_, u.cout_p)
+            elif src.kind == 'head':
+                u.sum_rows = rows(_lib.OP_CONV1X1, B, u.h, u.w_, src.cout_p, src.cin_p, dc, fused_bn=True)
+            else:                 # ConvTranspose2d data gradient: the launch runs on the convT INPUT grid (= this unit's)
+                u.sum_rows = rows(_lib.OP_CONVT2X2_DGRAD, B, u.h, u.w_, src.cin_p, src.cout_p, dc, fused_bn=True)
             sizes.append((u.stat_rows * 2 + u.sum_rows * self.NS + u.gz_nrows) * u.cout_p)
-        self.stat_arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.dev)
-        # eval-mode BatchNorm backward (clamd_bn_bwd_eval): rows [n][3][Cout_p] of the units whose sums no producing launch accumulates;
-        # an arena of its own, so the train-mode buffers stay as they were
-        esz = []
-        for u in self.convs:
-            u.eval_nrows = 0 if u.fused_reduce else _lib.load().clamd_bn_bwd_eval_rows(B, u.h, u.w_, u.cout_p, 1 if u.g_src[2] is not None else 0)
+            # eval-mode BatchNorm backward (clamd_bn_bwd_eval): rows [n][3][Cout_p] of the units whose sums no producing launch accumulates;
+            # an arena of its own, so the train-mode buffers stay as they were
+            u.eval_nrows = 0 if u.fused_reduce else lib.clamd_bn_bwd_eval_rows(B, u.h, u.w_, u.cout_p, 1 if u.g_src[2] is not None else 0)
             if u.eval_nrows < 0:
                 _lib.check(u.eval_nrows, 'clamd_bn_bwd_eval_rows')
             esz.append(u.eval_nrows * 3 * u.cout_p)
+        self.stat_arena = torch.empty(sum(sizes), dtype=torch.float32, device=self.dev)
         self.eval_arena = torch.empty(sum(esz), dtype=torch.float32, device=self.dev)
-        off = 0
-        for u, n in zip(self.convs, esz):
-            u.eval_rows = self.eval_arena[off:off + n] if n else None
-            off += n
-        off = 0
-        for u, n in zip(self.convs, sizes):
+        off = eoff = 0
+        for u, n, e in zip(self.convs, sizes, esz):
             k, k2 = u.stat_rows * 2 * u.cout_p, u.gz_nrows * u.cout_p
             u.stats = self.stat_arena[off:off + k]
             u.sums = self.stat_arena[off + k:off + n - k2]
             u.gz_rows = self.stat_arena[off + n - k2:off + n] if k2 else None
-            off += n
+            u.eval_rows = self.eval_arena[eoff:eoff + e] if e else None
+            off, eoff = off + n, eoff + e
 
     # ------------------------------------------------------------------------------------------ pack table
     def _build_pack_table(self):
@@ -731,28 +594,24 @@ class _Engine:
         wtab = {(pl, late): WinoPackTable(pl) for pl in (16, 24, 36) for late in (False, True)}
         for i, u in enumerate(self.convs):
             u.pack_late = i >= 6                                 # units 0-5 = enc1, enc2, enc3
-            if u.im2col:
-                tab.head(u.w, u.wf, None, 9 * u.cin, u.cout)     # [Cout][Cin*9] is already the (c*9 + tap) K order
-            elif u.wino:
+            if u.f.taps == 1:
+                tab.head(u.w, u.wf, None, 9 * u.cin, u.cout)     # im2col: [Cout][Cin*9] is already the (c*9 + tap) K order
+            elif u.f.wino:
                 if u.fold_a is None:
-                    wtab[(36 if u.f44 else (24 if u.w24 else 16), u.pack_late)].conv3x3(u.w, u.wf, None, u.cin_segs, u.cout)
+                    wtab[(u.f.taps, u.pack_late)].conv3x3(u.w, u.wf, None, u.cin_segs, u.cout)
                 if u.wd is not None:
-                    wtab[(36 if u.d44 else (24 if u.w24d else 16), u.pack_late)].conv3x3(u.w, None, u.wd, u.cin_segs, u.cout)
+                    wtab[(u.d.taps, u.pack_late)].conv3x3(u.w, None, u.wd, u.cin_segs, u.cout)
             else:
                 (late if u.pack_late else tab).conv3x3(u.w, None if u.fold_a is not None else u.wf, u.wd, u.cin_segs, u.cout)
             tab.vector(u.b, u.bias_p, u.cout)
             if u.fold_a is not None:
                 # the forward filters of a fold candidate are packed inside the step, behind the producer's bn_finalize: with its scale
                 # (fold on) or plain (a tuning that runs a kernel without the border-class epilogue)
-                u.fold_table, u.plain_table = [
-                    (WinoPackTable(24 if u.w24 else 16) if u.wino else PackTable(self.dcode)) for _ in range(2)]
+                u.fold_table, u.plain_table = [(WinoPackTable(u.f.taps) if u.f.wino else PackTable(self.dcode)) for _ in range(2)]
                 u.fold_table.conv3x3(u.w, u.wf, None, u.cin_segs, u.cout, kscale=u.fold_a.vec[0])
                 u.plain_table.conv3x3(u.w, u.wf, None, u.cin_segs, u.cout)
                 u.fold_table.finalize(self.dev); u.plain_table.finalize(self.dev)
-        for s in self.stages:
-            t = s.get('tail')
-            if t is None:
-                continue
+        for t in self.tails:
             if t.kind == 'convT':
                 late.convT(t.w, t.wf, t.wd, t.cin, t.cout)
             elif t.fold_b is not None:      # forward filters inside the step, with the last BatchNorm's scale (see _fwd_fold)
@@ -778,10 +637,8 @@ class _Engine:
             named = dict(zip(self.param_names, params))
             for u in self.convs:
                 u.w, u.b, u.gamma, u.beta = (named[k] for k in u.keys)
-            for s in self.stages:
-                t = s.get('tail')
-                if t is not None:
-                    t.w, t.b = named[t.keys[0]], named[t.keys[1]]
+            for t in self.tails:
+                t.w, t.b = named[t.keys[0]], named[t.keys[1]]
             self._build_pack_table()
 
     # ------------------------------------------------------------------------------------------ forward
@@ -814,7 +671,7 @@ class _Engine:
                 t.run(sp)
         self._ev_pack_late = None
         self._pack_late_pending = self.pack_late is not None      # released beside convolution PACK_LATE_AT (see _release_pack_late)
-        if self.convs[0].im2col:
+        if self.convs[0].f.taps == 1:        # im2col
             _hbm('enc1.0', B * H * W * (4 * m.in_dim + self.esize * self.x_in.shape[-1]),
                  'clamd_nchw_im2col3', ptr(x), ptr(self.x_in), self.x_in.shape[-1], B, m.in_dim, H, W, self.x_in.shape[-1], dc, s)
         else:
@@ -867,11 +724,8 @@ class _Engine:
     @staticmethod
     def executed_fraction(u, direction):
         """Multiply-adds the kernel executes per algorithmic (direct-convolution) multiply-add of unit u."""
-        if not u.wino:
-            return 1.0
-        if {'wgrad': u.pre_w and u.f44, 'dgrad': u.d44}.get(direction, u.f44):
-            return 36.0 / 144.0                                   # F(4x4,3x3): 36 per 16 outputs x 9 taps
-        return 24.0 / 72.0 if {'wgrad': u.w24g or u.pre_w, 'dgrad': u.w24d}.get(direction, u.w24) else 16.0 / 36.0
+        a = getattr(u.plan, direction)
+        return ALGOS[a].frac if a else 1.0
 
     def executed_flop_deficit(self):
         """Algorithmic minus executed FLOPs of one train step (3x3 convolutions by Winograd), for bench.py."""
@@ -889,14 +743,13 @@ class _Engine:
 
     def _fwd_pre(self, u, s):
         """Input transform of a pre-transformed convolution (wino24g.hip)."""
-        if not u.pre_f:
+        if not u.f.pre:
             return
         # the BatchNorm of the unit in front folded into the transform where nothing else reads its output (u.fold_src)
         f = u.fold_src
         xsrc, xldc, fs, fh = (f.y, f.cout_p, f.vec[0], f.vec[1]) if f is not None else (u.xin, u.xin_ldc, None, None)
         _TIMED_UNIT[:] = [u.name + ' fwd', self.executed_fraction(u, 'fwd')]
-        _timed('wino_transform', 0.0, (13 if u.f44 else 16) * self.B * u.h * u.w_ * u.cin_p,   # reads the activation once, writes 3x (F(4x4): 2.25x) its size
-               'clamd_winograd44_transform_input' if u.f44 else 'clamd_winograd24_transform_input', ptr(xsrc), xldc, ptr(fs), ptr(fh), ptr(u.vx),
+        _timed('wino_transform', 0.0, u.f.x_bytes * self.B * u.h * u.w_ * u.cin_p, u.f.xform, ptr(xsrc), xldc, ptr(fs), ptr(fh), ptr(u.vx),
                self.B, u.h, u.w_, u.cin_p, s)
 
     def _fwd_fold(self, u, s):
@@ -906,11 +759,10 @@ class _Engine:
         if a is None:
             return
         if not u.fold_on:
-            t = u.plain_table
-            t.run(s) if u.wino else t.run(self.dcode, s)
+            u.plain_table.run(stream=s)
             return
         t = u.fold_table        # one launch: the filters times the producer's scale, and the bias table from its shift
-        call('clamd_bn_fold_pack', (24 if u.w24 else 16) if u.wino else 0, ptr(t.dev_table), len(t.jobs), t.nblocks, self.dcode,
+        call('clamd_bn_fold_pack', u.f.taps if u.f.wino else 0, ptr(t.dev_table), len(t.jobs), t.nblocks, self.dcode,
              ptr(u.w), 9, ptr(a.vec[1]), ptr(u.b), ptr(u.cb), u.cout, u.cin, u.cout_p, s)
 
     def _release_pack_late(self):
@@ -947,19 +799,17 @@ class _Engine:
             self._release_pack_late()
         Bl = self.B
         _TIMED_UNIT[:] = [u.name + ' fwd', self.executed_fraction(u, 'fwd')]
-        rows = u.stat_rows_launch
-        st = u.stats if training else None
-        xin, y = u.xin, u.y
-        xin_ldc, bias, relu = u.xin_ldc, u.bias_p, 1
+        rows, st, y = u.stat_rows, (u.stats if training else None), u.y
+        xin, xin_ldc, bias, relu = u.xin, u.xin_ldc, u.bias_p, 1
         if u.fold_on:      # reads the producer's conv+ReLU output; its BatchNorm lives in the filters and in the bias table
             xin, xin_ldc, bias, relu = u.fold_a.y, u.fold_a.cout_p, u.cb, 3
         flops = 2.0 * Bl * u.h * u.w_ * 9 * u.cin * u.cout
-        nbytes = self.esize * (Bl * u.h * u.w_ * (u.cin + u.cout) + 9 * u.cin * u.cout)
-        if u.im2col:
+        nbytes = self._conv_bytes(u)
+        if u.f.taps == 1:     # im2col
             _hbm('enc1.0', self.esize * Bl * u.h * u.w_ * (u.cin_p + u.cout),
                  'clamd_conv1x1', ptr(xin), u.xin_ldc, ptr(u.wf), ptr(u.bias_p), ptr(y), u.cout_p,
                  ptr(st), None, None, rows, Bl, u.h, u.w_, u.cin_p, u.cout_p, 1, dc, s)
-        elif u.wino:
+        elif u.f.wino:
             if self._pack_pending == 2 and (u.level >= 1 or u.pack_late):
                 # the late transforms (HBM-bound, 0.3 ms) start here, under this MFMA-bound convolution, instead of beside the
                 # HBM-bound first-layer kernels -- and, round 5, behind enc1's pooling pass (level >= 1): started under enc1's second
@@ -972,16 +822,14 @@ class _Engine:
             if self._pack_pending == 1 and u.pack_late:
                 torch.cuda.current_stream().wait_stream(self.wg_stream)
                 self._pack_pending = 0
-            if u.pre_f:
-                _timed('igemm_conv3x3', flops, nbytes, 'clamd_conv3x3_winograd44_pre' if u.f44 else 'clamd_conv3x3_winograd24_pre',
-                       ptr(u.vx), ptr(u.wf), ptr(u.bias_p), ptr(y), u.cout_p,
+            if u.f.pre:
+                _timed('igemm_conv3x3', flops, nbytes, u.f.conv, ptr(u.vx), ptr(u.wf), ptr(u.bias_p), ptr(y), u.cout_p,
                        ptr(st), rows, Bl, u.h, u.w_, u.cin_p, u.cout_p, 1, tp, s)
             else:
-                name = ('clamd_conv3x3_winograd24_direct_filters' if u.direct_f else 'clamd_conv3x3_winograd24') if u.w24 else 'clamd_conv3x3_winograd'
-                _timed('igemm_conv3x3', flops, nbytes, name, ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.y_ldc, ptr(st), rows,
+                _timed('igemm_conv3x3', flops, nbytes, u.f.conv, ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.y_ldc, ptr(st), rows,
                        Bl, u.h, u.w_, u.cin_p, u.cout_p, relu, tp, s)
         else:
-            _timed('igemm_conv3x3', flops, nbytes, 'clamd_conv3x3', ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.cout_p,
+            _timed('igemm_conv3x3', flops, nbytes, u.f.conv, ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.cout_p,
                    ptr(st), None, None, rows, Bl, u.h, u.w_, u.cin_p, u.cout_p, relu, u.m_fastest, dc, tp, s)
 
     def _fwd_finalize(self, u, training, s):
@@ -1057,8 +905,7 @@ class _Engine:
                     self.dl_src = None
                     _hbm('head', self.esize * B * h * w * (self.Kp + t.cin),
                          'clamd_conv1x1', ptr(self.dl), self.Kp, ptr(t.wd), None, ptr(t.g_x), t.g_x.shape[-1], None,
-                         ptr(t.consumer.y) if t.consumer else None, ptr(t.consumer.sums) if t.consumer else None,
-                         t.consumer.sum_rows if t.consumer else 0, B, h, w, t.cout_p, t.cin_p, 0, dc, s)
+                         *_sums_into(t.consumer), B, h, w, t.cout_p, t.cin_p, 0, dc, s)
                     sw = self._wg_stream_ptr()      # parameter gradients on the second stream, behind the data gradient (see _conv_bwd)
                     fb = t.fold_b
                     tx, tx_ldc = (fb.y, fb.cout_p) if fb is not None else (t.x, t.x.shape[-1])
@@ -1075,8 +922,7 @@ class _Engine:
                     ctb = self.esize * (B * h * w * (t.cin + 4 * t.cout) + 4 * t.cin * t.cout)
                     _hbm('convT', ctb,
                          'clamd_convT2x2_dgrad', ptr(t.gy_slice), t.y_ldc, ptr(t.wd), ptr(t.g_x), t.g_x.shape[-1],
-                         ptr(t.consumer.y) if t.consumer else None, ptr(t.consumer.sums) if t.consumer else None,
-                         t.consumer.sum_rows if t.consumer else 0, B, h, w, t.cin_p, t.cout_p, dc, s)
+                         *_sums_into(t.consumer), B, h, w, t.cin_p, t.cout_p, dc, s)
                     sw = self._wg_stream_ptr()
                     _hbm('convT', ctb,
                          'clamd_wgrad', _lib.WGRAD_UP2, ptr(t.x), t.x.shape[-1], ptr(t.gy_slice), t.y_ldc, ptr(self.ws),
@@ -1105,19 +951,14 @@ class _Engine:
         the second and third streams, GradSync's stream and RCCL's: five -- so under ddp.GradSync the third stream needs at least eight queues
         (two rounds of the assignment apart).  The count is MEASURED (ddp.hw_queues: spin kernels on eight streams), not read from
         GPU_MAX_HW_QUEUES -- the runtime reads that variable once, when it starts."""
-        if self.model.grad_sync is None:
-            return True
-        from . import ddp
-        return ddp.hw_queues(self.dev) >= 8
-
-    def _fuse_sums(self, b):
-        """Does the data-gradient launch of conv `b` (3x3, K = b.cout_p gradient channels) also reduce the BN-backward sums
-        of the unit in front of it?"""
-        if b.wino:                     # the Winograd data-gradient kernels have no such epilogue (round 4: built with two sums in the statistics
-            return False               # registers, measured 21.06 -> 21.11 ms per step, removed: the reduce passes it replaces run beside a weight gradient)
-        if FUSE_BN_SUMS == 'auto':     # persistent bf16 kernel: <= 256 input channels, K-steps in pairs (64 channels)
-            return self.dcode == _lib.BF16 and b.cout_p <= 256 and b.cout_p % 64 == 0
-        return bool(FUSE_BN_SUMS)
+        if self.x3_stream is None or self.wg_stream is None or KERNEL_TIMING is not None:
+            return False
+        if self.model.grad_sync is not None:
+            from . import ddp
+            if ddp.hw_queues(self.dev) < 8:
+                return False
+        # hipStreamEndCapture crashes on this three-stream pattern (ROCm 7.2): a captured step keeps the transforms on the second stream
+        return not torch.cuda.is_current_stream_capturing()
 
     def _conv_bwd(self, u, s):
         B, dc, tp = self.B, self.dcode, tune_ptr(self.tuning)
@@ -1163,9 +1004,7 @@ class _Engine:
             c_seg0, c_seg0p = u.cin, u.cin_p
         flops = 2.0 * B * u.h * u.w_ * 9 * u.cin * u.cout
         self._x3_ev = None
-        if (u.pre_w and self.x3_stream is not None and self.wg_stream is not None and KERNEL_TIMING is None and self._x3_allowed()
-                and not torch.cuda.is_current_stream_capturing()):      # hipStreamEndCapture crashes on this three-stream pattern (ROCm 7.2):
-            #                                                            a captured step keeps the transform on the second stream
+        if u.g.pre and self._x3_allowed():
             # gz is complete on the current stream: its weight-gradient transform goes to the third stream NOW (it runs beside whatever
             # weight-gradient GEMM the second stream is in), into the operand buffer the previous GEMM is not reading
             self._yt_flip ^= 1
@@ -1174,29 +1013,24 @@ class _Engine:
             x3.wait_stream(torch.cuda.current_stream())
             if self._yt_ev[self._yt_flip] is not None:      # the GEMM that read this buffer last (two pre-transformed units back)
                 x3.wait_event(self._yt_ev[self._yt_flip])
-            call('clamd_wgrad_winograd44_pre_transform' if u.f44 else 'clamd_wgrad_winograd24_pre_transform', ptr(u.gz), u.cout_p, ptr(self._x3_buf),
+            call(u.g.wg_xform, ptr(u.gz), u.cout_p, ptr(self._x3_buf),
                  B, u.h, u.w_, u.cout_p, x3.cuda_stream)
             self._x3_ev = torch.cuda.Event(); self._x3_ev.record(x3)
         def dgrad():
             _TIMED_UNIT[:] = [u.name + ' dgrad', self.executed_fraction(u, 'dgrad')]
-            if u.g_in is not None and u.pre_d:
-                _timed('wino_transform', 0.0, (13 if u.d44 else 16) * B * u.h * u.w_ * u.cout_p,      # reads the gradient once, writes 3x (F(4x4): 2.25x) its size
-                       'clamd_winograd44_transform_input' if u.d44 else 'clamd_winograd24_transform_input', ptr(u.gz), u.cout_p, None, None, ptr(self.vg),
+            if u.d is None:
+                return
+            if u.d.pre:
+                _timed('wino_transform', 0.0, u.d.x_bytes * B * u.h * u.w_ * u.cout_p, u.d.xform, ptr(u.gz), u.cout_p, None, None, ptr(self.vg),
                        B, u.h, u.w_, u.cout_p, s)
-                _timed('igemm_conv3x3', flops, self._conv_bytes(u),
-                       'clamd_conv3x3_winograd44_pre' if u.d44 else 'clamd_conv3x3_winograd24_pre', ptr(self.vg), ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None, 0,
+                _timed('igemm_conv3x3', flops, self._conv_bytes(u), u.d.conv, ptr(self.vg), ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None, 0,
                        B, u.h, u.w_, u.cout_p, u.cin_p, 0, tp, s)
-            elif u.g_in is not None and u.wino:
-                name = 'clamd_conv3x3_winograd24_direct_filters' if u.direct_d else ('clamd_conv3x3_winograd24' if u.w24d else 'clamd_conv3x3_winograd')
-                _timed('igemm_conv3x3', flops, self._conv_bytes(u), name, ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None, 0,
+            elif u.d.wino:
+                _timed('igemm_conv3x3', flops, self._conv_bytes(u), u.d.conv, ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None, 0,
                        B, u.h, u.w_, u.cout_p, u.cin_p, 0, tp, s)
-            elif u.g_in is not None:
-                _timed('igemm_conv3x3', flops, self._conv_bytes(u),
-                       'clamd_conv3x3', ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None,
-                       ptr(u.consumer.y) if u.consumer is not None else None,
-                       ptr(u.consumer.sums) if u.consumer is not None else None,
-                       u.consumer.sum_rows if u.consumer is not None else 0,
-                       B, u.h, u.w_, u.cout_p, u.cin_p, 0, 1 if 9 * u.cin_p > B * u.h * u.w_ else 0, dc, tp, s)
+            else:
+                _timed('igemm_conv3x3', flops, self._conv_bytes(u), u.d.conv, ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(u.g_in), u.g_in.shape[-1], None,
+                       *_sums_into(u.consumer), B, u.h, u.w_, u.cout_p, u.cin_p, 0, 1 if 9 * u.cin_p > B * u.h * u.w_ else 0, dc, tp, s)
 
         # The weight gradient may start once the data gradient of the same unit has FINISHED (the second stream's wait is
         # recorded behind it).  Started together, the dispatcher interleaves the workgroups of the two kernels, they end together
@@ -1214,41 +1048,37 @@ class _Engine:
             sw = self._wg_stream_ptr()
         if two:      # off the critical chain: the fixed-order sum of the apply pass's rows, in front of this unit's weight gradient
             call('clamd_rows_sum', ptr(u.gz_rows), u.gz_nrows, g[u.keys[1]], u.cout_p, u.cout, sw)
-        if u.im2col:
+        if u.g.taps == 1:     # im2col: a pointwise weight gradient
             _hbm('enc1.0', self.esize * B * u.h * u.w_ * (u.cout + u.cin_p),
-                 'clamd_wgrad', _lib.WGRAD_PW, ptr(u.gz), u.cout_p, ptr(u.xin), u.xin_ldc, ptr(self.ws), self.ws_bytes,
+                 u.g.wgrad, _lib.WGRAD_PW, ptr(u.gz), u.cout_p, ptr(u.xin), u.xin_ldc, ptr(self.ws), self.ws_bytes,
                  g[u.keys[0]], B, u.h, u.w_, u.cout_p, u.cin_p, u.cout, 9 * u.cin, u.cout, u.cout_p, 9 * u.cin, u.cin_p, dc, tp, sw)
             return
         _TIMED_UNIT[:] = [u.name + ' wgrad', self.executed_fraction(u, 'wgrad')]
-        if u.pre_w and self._x3_ev is not None:
+        xin, xin_ldc = (u.fold_a.y, u.fold_a.cout_p) if u.fold_on else (u.xin, u.xin_ldc)      # a fold candidate reads the raw tensor
+        if u.g.pre and self._x3_ev is not None:
             # the gradient-side operand was transformed on the third stream (enqueued when gz became ready, see below)
             self.wg_stream.wait_event(self._x3_ev)
-            call('clamd_wgrad_winograd44_pre' if u.f44 else 'clamd_wgrad_winograd24_pre', None, u.cout_p, ptr(u.vx), ptr(self._x3_buf), ptr(self.ws), self.ws_bytes,
+            call(u.g.wgrad, None, u.cout_p, ptr(u.vx), ptr(self._x3_buf), ptr(self.ws), self.ws_bytes,
                  g[u.keys[0]], B, u.h, u.w_, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, tp, sw)
             ev = torch.cuda.Event(); ev.record(self.wg_stream)
             self._yt_ev[self._yt_flip] = ev
             self._x3_ev = None
-        elif u.pre_w:
-            _timed('wgrad_conv3x3', flops, self._conv_bytes(u),
-                   'clamd_wgrad_winograd44_pre' if u.f44 else 'clamd_wgrad_winograd24_pre', ptr(u.gz), u.cout_p, ptr(u.vx), ptr(self.yt), ptr(self.ws), self.ws_bytes,
+        elif u.g.pre:
+            _timed('wgrad_conv3x3', flops, self._conv_bytes(u), u.g.wgrad, ptr(u.gz), u.cout_p, ptr(u.vx), ptr(self.yt), ptr(self.ws), self.ws_bytes,
                    g[u.keys[0]], B, u.h, u.w_, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, tp, sw)
-        elif u.wino:
-            xin, xin_ldc = (u.fold_a.y, u.fold_a.cout_p) if u.fold_on else (u.xin, u.xin_ldc)
-            _timed('wgrad_conv3x3', flops, self._conv_bytes(u),
-                   'clamd_wgrad_winograd24' if u.w24g else 'clamd_wgrad_winograd', ptr(u.gz), u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
+        elif u.g.wino:
+            _timed('wgrad_conv3x3', flops, self._conv_bytes(u), u.g.wgrad, ptr(u.gz), u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
                    g[u.keys[0]], B, u.h, u.w_, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, tp, sw)
         else:
-            xin, xin_ldc = (u.fold_a.y, u.fold_a.cout_p) if u.fold_on else (u.xin, u.xin_ldc)
             _timed('wgrad_conv3x3', flops, self._conv_bytes(u),
-                   'clamd_wgrad', _lib.WGRAD_CONV3, ptr(u.gz), u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
+                   u.g.wgrad, _lib.WGRAD_CONV3, ptr(u.gz), u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
                    g[u.keys[0]], B, u.h, u.w_, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, dc, tp, sw)
         if u.fold_on:
             # the weight gradient ran on the producer's conv+ReLU output r instead of x = scale * r + shift: dW = scale * dWr + shift * S, S from
             # the border sums of gz and the conv-bias gradient bn_bwd_finalize wrote above (bnfold.hip); same stream, in place
             a = u.fold_a
             fs = sw
-            if (self.x3_stream is not None and self.wg_stream is not None and KERNEL_TIMING is None and self._x3_allowed()
-                    and not torch.cuda.is_current_stream_capturing()):
+            if self._x3_allowed():
                 # two latency-bound launches of a few microseconds: on the third stream they run beside the next unit's weight gradient
                 # instead of in front of it (the second stream is the longer one at the end of the bf16 backward pass)
                 ev = torch.cuda.Event(); ev.record(self.wg_stream)

@@ -154,9 +154,10 @@ def test_engine_geometry_and_pack_table(C):
     # wf + wd + bias per conv (no wd for enc1.0), 3 per tail; on the fp32 path the filters of the Winograd units
     # (3x3, even images of at least 8x8: every unit here except enc1.0 (im2col) and the two 4x4 centre convs) are
     # transformed by the Winograd pack table instead
-    wino_units = [u for u in e.convs if u.wino]
+    wino = lambda u: u.plan.fwd not in ('im2col', 'igemm')    # the unit's forward runs a Winograd form (plan.ALGOS)
+    wino_units = [u for u in e.convs if wino(u)]
     assert len(wino_units) == 15 and all(min(u.h, u.w_) >= 8 for u in wino_units)
-    w24 = [u for u in wino_units if u.w24]
+    w24 = [u for u in wino_units if u.plan.fwd != 'f22']
     assert len(w24) == 15                                   # every width here (64 ... 8) is a multiple of 4: F(2x4,3x3)
     nw = sum(len(t.jobs) for t in e.wino_early + e.wino_late)          # two launches per form: enc1-enc3 first, the rest behind
     # the second convolution of every block here (<= 128 channels) is a candidate for the algebraic BatchNorm fold (bnfold.hip): its
@@ -168,16 +169,16 @@ def test_engine_geometry_and_pack_table(C):
     assert [u.name for u in pooled] == ['enc3.block.4'] and pooled[0].y is e.cat[2] and pooled[0].y_ldc == 64
     assert sorted(u.name for u in fold if not hasattr(u.fold_a, 'name')) == ['dec3.block.0', 'enc4.block.1']
     assert len(fold) == 11 and all(u.fold_a.apply_in_filters and len(u.fold_table.jobs) == 1 and len(u.plain_table.jobs) == 1 for u in fold)
-    ks = lambda u, t: t.jobs[0][-1 if u.wino else -2]       # kscale: the last field of a Winograd pack job, the one before dst_t of a plain one
+    ks = lambda u, t: t.jobs[0][-1 if wino(u) else -2]       # kscale: the last field of a Winograd pack job, the one before dst_t of a plain one
     assert all(ks(u, u.fold_table) == u.fold_a.vec[0].data_ptr() and ks(u, u.plain_table) == 0 for u in fold)
     assert sum(len(t.jobs) for t in e.wino_early) == sum(2 - (u.fold_a is not None) for u in wino_units if not u.pack_late)
-    assert nw == 2 * len(wino_units) - sum(1 for u in fold if u.wino)
+    assert nw == 2 * len(wino_units) - sum(1 for u in fold if wino(u))
     head = e.stages[-1]['tail']
     assert head.kind == 'head' and head.fold_b is e.convs[-1] and len(head.fold_table.jobs) == 1      # the 1x1 head folds the last BatchNorm
     # a plain (non-Winograd) 3x3 unit whose forward AND data-gradient filters come from the table is ONE job (PackJob::dst_t: both layouts from one
     # read of the source tile)
     merged = [j for j in jobs if j[2] == 9 and j[-1] != 0]
-    assert len(merged) == sum(1 for u in e.convs if not u.wino and not u.im2col and u.fold_a is None and u.wd is not None)
+    assert len(merged) == sum(1 for u in e.convs if not wino(u) and u.plan.fwd != 'im2col' and u.fold_a is None and u.wd is not None)
     assert len(jobs) + len(merged) + nw + len(fold) + 1 == 18 * 3 - 1 + 5 * 3
     assert e.pack_table.nblocks + e.pack_late.nblocks == sum(((j[3] + 31) // 32) * ((j[4] + 31) // 32) for j in jobs)
     assert C.cpad(3) == 32 and C.cpad(21) == 32 and C.cpad(1024) == 1024

@@ -812,7 +812,7 @@ def test_batchnorm_folded_into_the_next_convolutions_filters(C, dtype, cd, size,
     eng = next(iter(one[3]._engines.values()))
     folded = [u.name for u in eng.convs if u.fold_on]
     assert len(folded) >= 4, folded
-    assert all(u.fold_a.apply_in_filters and not u.pre_f for u in eng.convs if u.fold_on)
+    assert all(u.fold_a.apply_in_filters and u.plan.fwd not in ('f24_pre', 'f44_pre') for u in eng.convs if u.fold_on)
     lt, gt = {'fp32': (2e-6, 1e-2), 'bf16x3': (2e-5, 4e-2), 'bf16': (5e-3, 0.2)}[dtype]
     assert abs(float(one[0]) - float(ref[0])) < lt * abs(float(ref[0])), (float(one[0]), float(ref[0]))
     assert float((one[1] - ref[1]).norm() / ref[1].norm()) < gt, float((one[1] - ref[1]).norm() / ref[1].norm())
@@ -880,13 +880,13 @@ def test_winograd44_engine_paths_agree(C, monkeypatch):
     monkeypatch.setattr(U, 'WINOGRAD44', False)
     ref = _one_step(C, 'fp32', nc, cd, B, size)
     e0 = next(iter(ref[3]._engines.values()))
-    assert not any(u.f44 or u.d44 for u in e0.convs) and any(u.pre_f for u in e0.convs)
+    assert not any('f44_pre' in (u.plan.fwd, u.plan.dgrad) for u in e0.convs) and any(u.plan.fwd in ('f24_pre', 'f44_pre') for u in e0.convs)
     monkeypatch.setattr(U, 'WINOGRAD44', True)
     one = _one_step(C, 'fp32', nc, cd, B, size)
     eng = next(iter(one[3]._engines.values()))
     # (at this size every data gradient has too few F(2x4) work items and runs F(2x2): the F(4x4) data gradients are exercised by the
     # full-size golden tests and, kernel by kernel, by tests/test_wino44_gpu.py)
-    assert sum(u.f44 for u in eng.convs) >= 4 and any(u.f44 and u.pre_w for u in eng.convs), [(u.name, u.f44, u.d44, u.pre_w) for u in eng.convs]
+    assert sum(u.plan.fwd == 'f44_pre' for u in eng.convs) >= 4 and any(u.plan.wgrad == 'f44_pre' for u in eng.convs), [u.plan for u in eng.convs]
     assert any(u.apply_folded for u in eng.convs)                  # a BatchNorm applied by the F(4x4) input transform
     assert abs(float(one[0]) - float(ref[0])) < 2e-6 * abs(float(ref[0])), (float(one[0]), float(ref[0]))
     assert float((one[1] - ref[1]).norm() / ref[1].norm()) < 1e-2
@@ -1003,7 +1003,8 @@ def test_graphed_step_matches_eager(C, dtype, cd, size):
     step = GraphedStep(m2, o2, c2, x, y, warmup=3)       # 3 eager steps, then the capture (not executed)
     if cd == 64:
         eng = next(iter(m2._engines.values()))
-        assert any(u.pre_f for u in eng.convs) and any(u.pre_w for u in eng.convs) and any(u.apply_folded for u in eng.convs)
+        pre = ('f24_pre', 'f44_pre')
+        assert any(u.plan.fwd in pre for u in eng.convs) and any(u.plan.wgrad in pre for u in eng.convs) and any(u.apply_folded for u in eng.convs)
     got = [float(l) for l in step.eager_losses]
     flat = lambda m: torch.cat([p.detach().reshape(-1) for p in m.parameters()]).clone()
     moved = []

@@ -61,7 +61,7 @@ for unit, (sec, flops, n, ex) in acc.items():
         tt[0] += t
         continue
     tf = flops / t / 1e12
-    pre = {'fwd': u.pre_f, 'dgrad': u.pre_d, 'wgrad': u.pre_w}.get(unit.split()[-1], False)
+    pre = getattr(u.plan, unit.split()[-1], None) in ('f24_pre', 'f44_pre')
     print(f'{unit:22s} {t * 1e6:8.1f} {tf:9.1f} {tf * ex / PEAK:8.3f}   {u.cin}->{u.cout} @{u.h}x{u.w_}{"  pre-transformed" if pre else ""}')
     d = unit.split()[-1]
     tt = tot.setdefault(d, [0.0, 0.0])
