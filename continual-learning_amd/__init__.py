@@ -9,7 +9,7 @@ from .loss import CrossEntropyLoss, DistillationCrossEntropy  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .metrics import argmax_confusion, eval_metrics, metrics_from_confusion  # noqa: F401
 from .trainer import Trainer, default_config  # noqa: F401
-from . import data, ddp  # noqa: F401
+from . import data, ddp, syncbn  # noqa: F401
 
 __all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'FusedAdam', 'Trainer', 'default_config',
            'argmax_confusion', 'eval_metrics', 'metrics_from_confusion', 'data', 'ddp', 'synth']

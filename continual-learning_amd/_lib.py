@@ -85,6 +85,9 @@ SIGNATURES = {
     'clamd_bn_bwd_eval_rows': (_I, [_I, _I, _I, _I, _I]),
     'clamd_bn_bwd_eval': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'clamd_bn_bwd_eval_finalize': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'clamd_bn_rows_total': (_I, [_P, _I, _I, _I, _D, _P, _P, _P]),
+    'clamd_bn_finalize_total': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _P, _P]),
+    'clamd_bn_bwd_finalize_total': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     'clamd_channel_sum_workspace_bytes': (_SZ, [_I]),
     'clamd_channel_sum': (_I, [_P, _I, _P, _LL, _I, _I, _I, _P, _SZ, _P, _P]),
     'clamd_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _D, _I, _P]),

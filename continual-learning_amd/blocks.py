@@ -9,7 +9,7 @@ No stock-torch operator is involved and there is no CPU path.
 """
 import torch
 
-from . import _lib
+from . import _lib, syncbn
 from ._lib import call, ptr
 from .ops import PackTable, TORCH_DT, cpad, from_nhwc, to_nhwc
 
@@ -21,13 +21,14 @@ def _stream():
 
 
 class _BlockFn(torch.autograd.Function):
-    """forward(x, plan, *params): plan = (ops, dcode, buffers); ops = [('pool',), ('crb', k, training), ..., ('convT',) | ('head',)]
-    (`training`: that BatchNorm module's own mode -- batch statistics, or its running statistics and no update);
+    """forward(x, plan, *params): plan = (ops, dcode, buffers, group); ops = [('pool',), ('crb', k, training, sync), ..., ('convT',) | ('head',)]
+    (`training`: that BatchNorm module's own mode -- batch statistics, or its running statistics and no update; `sync`: a train-mode
+    nn.SyncBatchNorm whose sums are all-reduced over `group`, syncbn.py);
     params = (conv.weight, conv.bias, bn.weight, bn.bias) per 'crb' in order, then (weight, bias) of the tail."""
 
     @staticmethod
     def forward(ctx, x, plan, *params):
-        ops, dcode, buffers = plan
+        ops, dcode, buffers, group = plan
         T = TORCH_DT[dcode]
         dev = x.device
         s = _stream()
@@ -45,7 +46,7 @@ class _BlockFn(torch.autograd.Function):
             elif op[0] == 'crb':
                 w, b, gamma, beta = params[pi:pi + 4]
                 rm, rv, nbt = buffers[op[1]]
-                training = op[2]
+                training, sync = op[2], op[3]
                 pi += 4
                 cout, cin = w.shape[0], w.shape[1]
                 cin_p, cout_p = cur.shape[-1], cpad(cout)
@@ -62,11 +63,18 @@ class _BlockFn(torch.autograd.Function):
                 call('clamd_conv3x3', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(y), cout_p, ptr(stats), None, None, rows, B, H, W,
                      cin_p, cout_p, 1, 1 if 9 * cout_p > B * H * W else 0, dcode, None, s)
                 vec = torch.zeros(7, cout_p, dtype=torch.float32, device=dev)       # scale, shift, mean, istd, k0, k1, k2
-                call('clamd_bn_finalize', ptr(stats), rows, ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), ptr(vec[0]), ptr(vec[1]),
-                     ptr(vec[2]), ptr(vec[3]), cout_p, cout, float(B * H * W), BN_MOMENTUM, BN_EPS, ptr(nbt) if training else None, s)
+                if sync:       # the statistics of the global batch (as in the UNet engine)
+                    red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev)
+                    call('clamd_bn_rows_total', ptr(stats), rows, 2, cout_p, float(B * H * W), None, ptr(red), s)
+                    syncbn.all_reduce(red, group)
+                    call('clamd_bn_finalize_total', ptr(red), ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), ptr(vec[0]), ptr(vec[1]),
+                         ptr(vec[2]), ptr(vec[3]), cout_p, cout, BN_MOMENTUM, BN_EPS, ptr(nbt), s)
+                else:
+                    call('clamd_bn_finalize', ptr(stats), rows, ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), ptr(vec[0]), ptr(vec[1]),
+                         ptr(vec[2]), ptr(vec[3]), cout_p, cout, float(B * H * W), BN_MOMENTUM, BN_EPS, ptr(nbt) if training else None, s)
                 out = torch.empty_like(y)
                 call('clamd_bn_apply', ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(out), cout_p, None, 0, B, H, W, cout_p, dcode, s)
-                saved.append(('crb', cur, y, vec, wd, gamma.detach(), training, (cin, cin_p, cout, cout_p, H, W)))
+                saved.append(('crb', cur, y, vec, wd, gamma.detach(), training, sync, (cin, cin_p, cout, cout_p, H, W)))
                 cur = out
             elif op[0] == 'convT':
                 w, b = params[pi:pi + 2]
@@ -100,7 +108,7 @@ class _BlockFn(torch.autograd.Function):
                 call('clamd_conv1x1_logits', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(logits), B, H, W, cin_p, kp, k, dcode, s)
                 saved.append(('head', cur, wd, (cin, cin_p, k, kp, H, W)))
                 cur = None
-        ctx.saved_ops, ctx.dcode, ctx.B, ctx.cin0 = saved, dcode, B, C
+        ctx.saved_ops, ctx.dcode, ctx.B, ctx.cin0, ctx.group = saved, dcode, B, C, group
         if cur is None:
             return logits
         last = ops[-1]
@@ -148,7 +156,7 @@ class _BlockFn(torch.autograd.Function):
                 grads = [dw, db] + grads
                 g = gx
             elif kind == 'crb':
-                _, x, y, vec, wd, gamma, training, (cin, cin_p, cout, cout_p, H, W) = rec
+                _, x, y, vec, wd, gamma, training, sync, (cin, cin_p, cout, cout_p, H, W) = rec
                 ga = to_nhwc(gout, dcode, cp=cout_p) if g is None else g
                 dgamma, dbeta, dbias = (torch.empty(cout, dtype=torch.float32, device=dev) for _ in range(3))
                 gz = torch.empty(B, H, W, cout_p, dtype=T, device=dev)
@@ -157,8 +165,16 @@ class _BlockFn(torch.autograd.Function):
                     sums = torch.empty(rows, lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float32, device=dev)
                     call('clamd_bn_bwd_reduce', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
                          B, H, W, cout_p, dcode, None, s)
-                    call('clamd_bn_bwd_finalize', ptr(sums), rows, ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma), ptr(dbeta),
-                         ptr(dbias), cout_p, cout, float(B * H * W), s)
+                    if sync:   # g_z from the sums of the global batch; d gamma, d beta, d conv-bias from this rank's own (as torch)
+                        red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev)
+                        tot = torch.empty(lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float64, device=dev)
+                        call('clamd_bn_rows_total', ptr(sums), rows, lib.clamd_bn_bwd_nsums(), cout_p, float(B * H * W), ptr(tot), ptr(red), s)
+                        syncbn.all_reduce(red, ctx.group)
+                        call('clamd_bn_bwd_finalize_total', ptr(tot), ptr(red), ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma),
+                             ptr(dbeta), ptr(dbias), cout_p, cout, s)
+                    else:
+                        call('clamd_bn_bwd_finalize', ptr(sums), rows, ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma), ptr(dbeta),
+                             ptr(dbias), cout_p, cout, float(B * H * W), s)
                     call('clamd_bn_bwd_apply', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
                          B, H, W, cout_p, dcode, s)
                 else:      # running statistics: one pass writes g_z and the rows of the parameter gradients
@@ -200,9 +216,10 @@ def run_block(seq, st, dcode, x):
     ops, params, buffers = [], [], []
     if st['pool']:
         ops.append(('pool',))
-    for ci, bi, cin, cout in st['convs']:
+    group, sync = syncbn.resolve([(str(bi), seq[bi]) for _, bi, _, _ in st['convs']])
+    for (ci, bi, cin, cout), sy in zip(st['convs'], sync):
         conv, bn = seq[ci], seq[bi]
-        ops.append(('crb', len(buffers), bool(bn.training)))
+        ops.append(('crb', len(buffers), bool(bn.training), sy))
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
         buffers.append((bn.running_mean, bn.running_var, bn.num_batches_tracked))
     if st['tail'] is not None:
@@ -211,4 +228,4 @@ def run_block(seq, st, dcode, x):
         params += [seq[ti].weight, seq[ti].bias]
     if x.shape[1] != st['convs'][0][2]:
         raise ValueError(f'expected {st["convs"][0][2]} input channels, got {x.shape[1]}')
-    return _BlockFn.apply(x, (ops, dcode, buffers), *params)
+    return _BlockFn.apply(x, (ops, dcode, buffers, group), *params)

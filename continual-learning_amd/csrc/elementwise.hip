@@ -49,26 +49,20 @@ __device__ inline void sum_partial_rows(const float* __restrict__ rows, int nrow
     __syncthreads();
 }
 
-// BN finalise: partial rows of (sum, sumsq) -> mean / invstd / scale / shift, running-stat update.  One block per FIN_CH channels.
+// One channel of the BN finalise: totals (sum x, sum x^2) over `count` pixels -> mean / invstd / scale / shift, running-stat update.
 // Reference: nn.BatchNorm2d train mode, models/unet.py:15 (momentum 0.1, eps 1e-5, unbiased running var).
-// Mean and variance are formed in fp64 from the fp64 row sums (E[x^2] - mean^2 cancels in fp32 on low-variance channels).
-__global__ void __launch_bounds__(FIN_THREADS) bn_finalize_kernel(const float* __restrict__ stats, int nrows, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float* running_mean, float* running_var,
-                                   float* scale, float* shift, float* save_mean, float* save_istd,
-                                   int Cp, int C, double count, double momentum, double eps, long long* num_batches_tracked) {
-    PASS_PRIO();
-    __shared__ double red[FIN_THREADS], tot[2 * FIN_CH];
-    const int c0 = blockIdx.x * FIN_CH;
-    if (stats) sum_partial_rows<2>(stats, nrows, Cp, c0, red, tot);
-    if (threadIdx.x >= FIN_CH) return;
-    if (num_batches_tracked && stats && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;      // nn.BatchNorm2d's counter (train mode)
-    const int c = c0 + threadIdx.x;
+// Mean and variance are formed in fp64 from the fp64 totals (E[x^2] - mean^2 cancels in fp32 on low-variance channels).
+// stats == false: eval mode (trainer.py:271), normalise with the running statistics, update nothing.  Shared by the finalize of the
+// partial rows and the finalize of all-reduced totals (synchronised BatchNorm): equal totals give equal bits.
+__device__ inline void bn_finalize_channel(bool stats, double s0, double s1, double count, int c, int C, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, float* running_mean, float* running_var, float* scale,
+                                           float* shift, float* save_mean, float* save_istd, double momentum, double eps) {
     double mean, var;
     if (stats) {
-        mean = tot[threadIdx.x] / count;
-        var = tot[FIN_CH + threadIdx.x] / count - mean * mean;
+        mean = s0 / count;
+        var = s1 / count - mean * mean;
         var = var > 0. ? var : 0.;
-    } else {   // eval mode (trainer.py:271): normalise with the running statistics, update nothing
+    } else {
         mean = c < C ? (double)running_mean[c] : 0.;
         var = c < C ? (double)running_var[c] : 1.;
     }
@@ -84,6 +78,57 @@ __global__ void __launch_bounds__(FIN_THREADS) bn_finalize_kernel(const float* _
         running_mean[c] = (float)((1. - momentum) * (double)running_mean[c] + momentum * mean);
         running_var[c] = (float)((1. - momentum) * (double)running_var[c] + momentum * unb);
     }
+}
+
+// BN finalise: partial rows of (sum, sumsq) -> bn_finalize_channel.  One block per FIN_CH channels.
+__global__ void __launch_bounds__(FIN_THREADS) bn_finalize_kernel(const float* __restrict__ stats, int nrows, const float* __restrict__ gamma,
+                                   const float* __restrict__ beta, float* running_mean, float* running_var,
+                                   float* scale, float* shift, float* save_mean, float* save_istd,
+                                   int Cp, int C, double count, double momentum, double eps, long long* num_batches_tracked) {
+    PASS_PRIO();
+    __shared__ double red[FIN_THREADS], tot[2 * FIN_CH];
+    const int c0 = blockIdx.x * FIN_CH;
+    if (stats) sum_partial_rows<2>(stats, nrows, Cp, c0, red, tot);
+    if (threadIdx.x >= FIN_CH) return;
+    if (num_batches_tracked && stats && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;      // nn.BatchNorm2d's counter (train mode)
+    const int c = c0 + threadIdx.x;
+    bn_finalize_channel(stats != nullptr, stats ? tot[threadIdx.x] : 0., stats ? tot[FIN_CH + threadIdx.x] : 0., count, c, C, gamma, beta,
+                        running_mean, running_var, scale, shift, save_mean, save_istd, momentum, eps);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Synchronised BatchNorm (nn.SyncBatchNorm): the partial rows are first added into fp64 totals (bn_rows_total_kernel: the same
+// sum_partial_rows<NK> with the same geometry, so the totals are the very doubles the finalize kernels form internally), the caller
+// all-reduces the [2][Cp] totals of sum x, sum x^2 (forward) or sum g, sum g y (backward) and the pixel count behind them across ranks,
+// and the *_total finalize kernels below read the result.  One rank: the all-reduce is the identity and the outputs are those of
+// bn_finalize_kernel / bn_bwd_finalize_kernel bit for bit (shared per-channel helpers).
+//   rows [nrows][NK][Cp] -> totals[NK][Cp] (optional) and reduce[0..2Cp) = the k = 0, 1 totals, reduce[2Cp] = count (optional)
+template <int NK>
+__global__ void __launch_bounds__(FIN_THREADS) bn_rows_total_kernel(const float* __restrict__ rows, int nrows, int Cp, double count,
+                                                                    double* totals, double* reduce) {
+    PASS_PRIO();
+    __shared__ double red[FIN_THREADS], tot[NK * FIN_CH];
+    const int c0 = blockIdx.x * FIN_CH;
+    sum_partial_rows<NK>(rows, nrows, Cp, c0, red, tot);
+    if (threadIdx.x >= NK * FIN_CH) return;
+    const int k = threadIdx.x / FIN_CH, c = c0 + threadIdx.x % FIN_CH;
+    const double v = tot[threadIdx.x];
+    if (totals) totals[(size_t)k * Cp + c] = v;
+    if (reduce && k < 2) reduce[(size_t)k * Cp + c] = v;
+    if (reduce && blockIdx.x == 0 && threadIdx.x == 0) reduce[2 * Cp] = count;
+}
+
+// reduce = all-reduced [sum x][sum x^2][count] -> bn_finalize_channel (train mode).  One thread per channel.
+__global__ void __launch_bounds__(256) bn_finalize_total_kernel(const double* __restrict__ reduce, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float* running_mean, float* running_var,
+                                                                float* scale, float* shift, float* save_mean, float* save_istd,
+                                                                int Cp, int C, double momentum, double eps, long long* num_batches_tracked) {
+    PASS_PRIO();
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cp) return;
+    if (num_batches_tracked && c == 0) *num_batches_tracked += 1;
+    bn_finalize_channel(true, reduce[c], reduce[Cp + c], reduce[2 * Cp], c, C, gamma, beta, running_mean, running_var, scale, shift,
+                        save_mean, save_istd, momentum, eps);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -297,8 +342,30 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
     }
 }
 
+// One channel of the BN backward finalise.  k0, k1, k2 (g_z = [y>0] (k0 g + k1 y + k2)) from the sums gs0 = sum g, gs1 = sum g y over
+// `count` pixels; the parameter gradients from s0..s4 (sum g, sum g y, sum g [y>0], sum [y>0], sum y): d gamma, d beta and, with dbias,
+// d conv-bias = sum g_z.  One rank: gs = s.  Synchronised BatchNorm: gs and count are the sums over all ranks (torch.nn.SyncBatchNorm's
+// g_z), s stays this rank's own (the parameter gradients are all-reduced with the others afterwards).
+__device__ inline void bn_bwd_finalize_channel(double gs0, double gs1, double count, double s0, double s1, double s2, double s3, double s4,
+                                               int c, int C, int Cp, const float* __restrict__ gamma, const float* __restrict__ save_mean,
+                                               const float* __restrict__ save_istd, float* k012, float* dgamma, float* dbeta, float* dbias) {
+    const double mu = save_mean[c], istd = save_istd[c];
+    const double g = c < C ? (double)gamma[c] : 0.;
+    const double inv_n = 1. / count;
+    const double k0 = g * istd;
+    const double c2 = istd * istd * (gs1 * inv_n - mu * gs0 * inv_n);
+    const double k1 = -k0 * c2;
+    const double k2 = k0 * (mu * c2 - gs0 * inv_n);
+    k012[c] = (float)k0; k012[Cp + c] = (float)k1; k012[2 * Cp + c] = (float)k2;
+    if (c < C) {
+        dgamma[c] = (float)(istd * (s1 - mu * s0));
+        dbeta[c] = (float)s0;
+        if (dbias) dbias[c] = (float)(k0 * s2 + k1 * s4 + k2 * s3);
+    }
+}
+
 // partial rows of the five sums -> k0,k1,k2 per channel, and the parameter gradients d_gamma, d_beta, d_convbias.
-// One block per 8 channels; fixed-order fp64 row sums (sum_partial_rows), coefficients formed in fp64.
+// One block per FIN_CH channels; fixed-order fp64 row sums (sum_partial_rows), coefficients formed in fp64.
 __global__ void __launch_bounds__(FIN_THREADS) bn_bwd_finalize_kernel(const float* __restrict__ sums, int nrows, const float* __restrict__ gamma,
                                        const float* __restrict__ save_mean, const float* __restrict__ save_istd,
                                        float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C,
@@ -312,19 +379,22 @@ __global__ void __launch_bounds__(FIN_THREADS) bn_bwd_finalize_kernel(const floa
     double s[NSUM];
 #pragma unroll
     for (int k = 0; k < NSUM; ++k) s[k] = tot[k * FIN_CH + threadIdx.x];
-    const double mu = save_mean[c], istd = save_istd[c];
-    const double g = c < C ? (double)gamma[c] : 0.;
-    const double inv_n = 1. / count;
-    const double k0 = g * istd;
-    const double c2 = istd * istd * (s[1] * inv_n - mu * s[0] * inv_n);
-    const double k1 = -k0 * c2;
-    const double k2 = k0 * (mu * c2 - s[0] * inv_n);
-    k012[c] = (float)k0; k012[Cp + c] = (float)k1; k012[2 * Cp + c] = (float)k2;
-    if (c < C) {
-        dgamma[c] = (float)(istd * (s[1] - mu * s[0]));
-        dbeta[c] = (float)s[0];
-        if (dbias) dbias[c] = (float)(k0 * s[2] + k1 * s[4] + k2 * s[3]);
-    }
+    bn_bwd_finalize_channel(s[0], s[1], count, s[0], s[1], s[2], s[3], s[4], c, C, Cp, gamma, save_mean, save_istd, k012, dgamma, dbeta, dbias);
+}
+
+// Synchronised form: totals [NSUM][Cp] = this rank's five sums (bn_rows_total_kernel), reduce = all-reduced [sum g][sum g y][count].
+// One thread per channel.  dbias == NULL: the two-sum rows (k = 2..4 NaN), the bias gradient comes from the apply pass.
+__global__ void __launch_bounds__(256) bn_bwd_finalize_total_kernel(const double* __restrict__ totals, const double* __restrict__ reduce,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ save_mean,
+                                                                    const float* __restrict__ save_istd, float* k012, float* dgamma,
+                                                                    float* dbeta, float* dbias, int Cp, int C) {
+    PASS_PRIO();
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cp) return;
+    const double* t = totals + c;
+    const double s2 = dbias ? t[2 * (size_t)Cp] : 0., s3 = dbias ? t[3 * (size_t)Cp] : 0., s4 = dbias ? t[4 * (size_t)Cp] : 0.;
+    bn_bwd_finalize_channel(reduce[c], reduce[Cp + c], reduce[2 * Cp], t[0], t[Cp], s2, s3, s4, c, C, Cp, gamma, save_mean, save_istd,
+                            k012, dgamma, dbeta, dbias);
 }
 
 // g_z = k0 g + k1 y + k2 where the ReLU was active: ONE expression (two fused multiply-adds) for every apply kernel, so the variants
@@ -822,6 +892,31 @@ int clamd_bn_finalize(const float* stats, int stat_rows, const float* gamma, con
     return clamd_check_launch("bn_finalize");
 }
 
+int clamd_bn_rows_total(const float* rows, int nrows, int nk, int Cp, double count, double* totals, double* reduce, void* stream) {
+    if (Cp <= 0 || Cp % 8) return clamd_fail("bn_rows_total: bad channel count");
+    if (!rows || nrows <= 0) return clamd_fail("bn_rows_total: nrows must be the row count the producing launch wrote");
+    if (!totals && !reduce) return clamd_fail("bn_rows_total: nothing to write");
+    if (!(count > 0.)) return clamd_fail("bn_rows_total: count must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    if (nk == 2)
+        hipLaunchKernelGGL(bn_rows_total_kernel<2>, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, s, rows, nrows, Cp, count, totals, reduce);
+    else if (nk == NSUM)
+        hipLaunchKernelGGL(bn_rows_total_kernel<NSUM>, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, s, rows, nrows, Cp, count, totals, reduce);
+    else return clamd_fail("bn_rows_total: nk must be 2 (statistics rows) or 5 (clamd_bn_bwd_nsums rows)");
+    return clamd_check_launch("bn_rows_total");
+}
+
+int clamd_bn_finalize_total(const double* reduce, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            float* scale, float* shift, float* save_mean, float* save_istd, int Cp, int C, double momentum, double eps,
+                            long long* num_batches_tracked, void* stream) {
+    if (Cp <= 0 || Cp % 8 || C <= 0 || C > Cp) return clamd_fail("bn_finalize_total: bad channel counts");
+    if (!reduce || !gamma || !beta || !scale || !shift || !save_mean || !save_istd) return clamd_fail("bn_finalize_total: null argument");
+    if (!running_mean != !running_var) return clamd_fail("bn_finalize_total: running_mean and running_var go together");
+    hipLaunchKernelGGL(bn_finalize_total_kernel, dim3((Cp + 255) / 256), dim3(256), 0, (hipStream_t)stream, reduce, gamma, beta, running_mean,
+                       running_var, scale, shift, save_mean, save_istd, Cp, C, momentum, eps, num_batches_tracked);
+    return clamd_check_launch("bn_finalize_total");
+}
+
 int clamd_bn_apply(const void* y, int y_ldc, const float* scale, const float* shift, void* out, int out_ldc,
                    void* pooled, int p_ldc, int B, int H, int W, int Cp, int dtype, void* stream) {
     if (!pow2_channels(Cp)) return clamd_fail("bn_apply: physical channels must be a power of two in [32,2048]");
@@ -906,6 +1001,16 @@ int clamd_bn_bwd_finalize(const float* sums, int sum_rows, const float* gamma, c
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, (hipStream_t)stream, sums, sum_rows,
                        gamma, save_mean, save_istd, k012, dgamma, dbeta, dbias, Cp, C, count);
     return clamd_check_launch("bn_bwd_finalize");
+}
+
+int clamd_bn_bwd_finalize_total(const double* totals, const double* reduce, const float* gamma, const float* save_mean,
+                                const float* save_istd, float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C, void* stream) {
+    if (Cp <= 0 || Cp % 8 || C <= 0 || C > Cp) return clamd_fail("bn_bwd_finalize_total: bad channel counts");
+    if (!totals || !reduce || !gamma || !save_mean || !save_istd || !k012 || !dgamma || !dbeta)
+        return clamd_fail("bn_bwd_finalize_total: null argument");
+    hipLaunchKernelGGL(bn_bwd_finalize_total_kernel, dim3((Cp + 255) / 256), dim3(256), 0, (hipStream_t)stream, totals, reduce, gamma,
+                       save_mean, save_istd, k012, dgamma, dbeta, dbias, Cp, C);
+    return clamd_check_launch("bn_bwd_finalize_total");
 }
 
 int clamd_bn_bwd_apply(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc,

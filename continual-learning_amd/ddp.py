@@ -1,7 +1,8 @@
 """Data-parallel gradient exchange over RCCL (torch.distributed backend "nccl" IS RCCL on ROCm), one process per GPU.
 
 Replaces nn.DataParallel (trainer.py:120-122): each rank runs the full train step on its own
-B images (BatchNorm statistics stay per-replica, as under DataParallel), and the 31 M gradients are summed with ONE
+B images (BatchNorm statistics are per-replica, as under DataParallel, unless the model was converted with
+``convert_sync_batchnorm``: then every train-mode BatchNorm uses the global batch, syncbn.py), and the 31 M gradients are summed with ONE
 collective per decoder/encoder stage, launched on a side stream the moment that stage's weight gradients are written
 (the flat gradient buffer is laid out in the order gradients are produced, so every bucket is a contiguous slice) and
 overlapped with the rest of the backward pass.  The 1/world factor is folded into the Adam kernel (grad_scale).
@@ -147,8 +148,9 @@ class GradSync:
             cu_reserve = int(os.environ['CLAMD_CU_RESERVE'])
         if cu_reserve is not None:          # otherwise whatever the user set on model.tuning stays
             model.tuning.cu_reserve = max(0, min(128, int(cu_reserve)))
-        # a rank uses five streams (default, the engine's second and third, this object's, RCCL's own): with fewer hardware queues some
-        # share one, and a kernel waits behind whatever shares its queue -- measured, not read from the environment
+        # a rank uses five streams (default, the engine's second and third, this object's, RCCL's own; six with synchronised BatchNorm,
+        # whose group has a communicator of its own): with fewer hardware queues some share one, and a kernel waits behind whatever shares
+        # its queue -- measured, not read from the environment
         self.hw_queues = None
         p0 = next(iter(model.parameters()), None)
         if p0 is not None and p0.is_cuda:
@@ -272,3 +274,10 @@ def broadcast_parameters(model, src=0, group=None):
     with one process per GPU a single broadcast at start is enough because every rank applies identical updates)."""
     for t in list(model.parameters()) + list(model.buffers()):
         dist.broadcast(t.data, src=src, group=group)
+
+
+def convert_sync_batchnorm(model, group=None):
+    """``nn.SyncBatchNorm.convert_sync_batchnorm(model, group)``: every BatchNorm of the model then normalises with the statistics of the
+    global batch in train mode (syncbn.py).  The parameters and buffers stay the same objects; the model is returned."""
+    import torch.nn as nn
+    return nn.SyncBatchNorm.convert_sync_batchnorm(model, group)

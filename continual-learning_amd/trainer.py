@@ -12,6 +12,8 @@ Out of scope here: JPEG dumps, prints, checkpoint file
 Continual learning (config 4): ``begin_task2(c_old, ...)`` snapshots the model and switches the criterion to
 DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined); ``freeze_bn=True`` also trains task 2 with
 every BatchNorm in eval mode (running statistics, not updated).
+Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
+of the global batch, syncbn.py).
 """
 import os
 import warnings
@@ -24,13 +26,14 @@ from torch.optim.lr_scheduler import LambdaLR
 from .loss import CrossEntropyLoss, DistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam
+from . import syncbn
 from .unet import UNet
 
 
 def default_config(**kw):
     """Defaults of main.py:64-105 for the flags the hot path reads."""
     cfg = dict(n_iters=10000, train_batch_size=2, lr=1e-4, lr_exp=0.9, beta1=0.5, beta2=0.99, h_image_size=512,
-               w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10)
+               w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -48,6 +51,8 @@ class Trainer:
         cfg = self.cfg
         self.model = UNet(num_classes=cfg.num_classes, in_dim=3, conv_dim=cfg.conv_dim,
                           compute_dtype=cfg.compute_dtype).to(self.device)
+        if getattr(cfg, 'sync_bn', False) and syncbn.initialized():
+            self.model = nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
         self.optim = FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
         self.scheduler = LambdaLR(self.optim, lr_lambda=lambda n: (1 - n / cfg.n_iters) ** cfg.lr_exp)
         self.c_loss = CrossEntropyLoss().to(self.device)
@@ -72,7 +77,7 @@ class Trainer:
             self.optim.set_l2_anchor([p.detach().clone() for p in self.old_model.parameters()], l2_lambda)
         if freeze_bn:
             for mod in m.modules():
-                if isinstance(mod, nn.BatchNorm2d):
+                if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
                     mod.eval()
 
     # ---- checkpoints: same file name and keys as trainer.py:68-102, but the model never leaves

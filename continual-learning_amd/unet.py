@@ -15,7 +15,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, syncbn
 from ._lib import call, ptr, tune_ptr
 from .ops import PackTable, WinoPackTable, cpad
 from .plan import ALGOS, Switches, plan_net
@@ -364,6 +364,9 @@ class _Engine:
         self.generation = 0
         self.dl_src = None
         self.fwd_modes = ()          # per conv unit: its BatchNorm's .training at the last forward (False = running statistics)
+        self.bn_group = None         # process group of the synchronised BatchNorm layers at the last forward (syncbn.py), or None
+        self._has_sync = None        # any nn.SyncBatchNorm among the units' modules (None: not looked at yet)
+        self._sync_arena = None
         self.esize = 2 if self.dcode == _lib.BF16 else 4      # activation element size in HBM (bf16x3 stores fp32)
         K, d = model.num_classes, model.conv_dim
         self.K, self.Kp = K, cpad(K)
@@ -408,6 +411,7 @@ class _Engine:
             u.rm, u.rv = bufs[f'{prefix}.{bi}.running_mean'], bufs[f'{prefix}.{bi}.running_var']
             u.nbt = bufs[f'{prefix}.{bi}.num_batches_tracked']
             u.bn, u.bn_train = mods[f'{prefix}.{bi}'], True         # its .training is the unit's BatchNorm mode (read every forward)
+            u.bn_parent, u.bn_parent_name, u.bn_key, u.bn_sync = mods[prefix], prefix, str(bi), False      # where the module lives (convert_sync_batchnorm swaps it)
             u.keys = (f'{prefix}.{ci}.weight', f'{prefix}.{ci}.bias', f'{prefix}.{bi}.weight', f'{prefix}.{bi}.bias')
             u.level, u.h, u.w_, u.cin_p, u.cout, u.cout_p = p.level, p.h, p.w, p.cin_p, p.cout, p.cout_p
             u.cin_segs, u.cin = list(p.cin_segs), sum(s[0] for s in p.cin_segs)      # [(logical, physical), ...] one or two segments
@@ -644,10 +648,10 @@ class _Engine:
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x, params, predict=False):
         m = self.model
-        # BatchNorm mode per unit, from its own nn.BatchNorm2d (torch's semantics: model.train() then bn.eval() freezes that layer's statistics)
-        for u in self.convs:
-            u.bn_train = bool(u.bn.training)
-        self.fwd_modes = tuple(u.bn_train for u in self.convs)
+        self._bn_modes()
+        if self.bn_group is not None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('UNet.forward: SyncBatchNorm layers in train mode all-reduce their statistics, which a captured graph cannot '
+                               'do; capture an unconverted model or put those layers in eval mode')
         self.generation += 1
         self.dl_src = None
         self._check_ptrs(params)
@@ -720,6 +724,34 @@ class _Engine:
             self._pack_pending = 0
         self._join_pack_late()
         return logits
+
+    def _bn_modes(self):
+        """BatchNorm mode per unit, from its own module (torch's semantics: model.train() then bn.eval() freezes that layer's statistics),
+        and which units all-reduce their statistics (a train-mode nn.SyncBatchNorm while a process group is initialised, syncbn.py).  The
+        module is looked up in its parent every forward: a conversion after the first forward takes effect at the next one."""
+        swapped = False
+        for u in self.convs:
+            bn = u.bn_parent._modules[u.bn_key]
+            if bn is not u.bn:
+                u.bn, swapped = bn, True
+            u.bn_train = bool(bn.training)
+        self.fwd_modes = tuple(u.bn_train for u in self.convs)
+        if swapped or self._has_sync is None:
+            self._has_sync = any(isinstance(u.bn, nn.SyncBatchNorm) for u in self.convs)
+        self.bn_group, flags = (None, None) if not self._has_sync else syncbn.resolve([(f'{u.bn_parent_name}.{u.bn_key}', u.bn) for u in self.convs])
+        for i, u in enumerate(self.convs):
+            u.bn_sync = bool(flags and flags[i])
+        if self.bn_group is not None and self._sync_arena is None:
+            # per unit: the all-reduced [sum][sum of squares or products][count] and this rank's five backward totals, fp64
+            sizes = [(2 * u.cout_p + 1, self.NS * u.cout_p) for u in self.convs]
+            self._sync_arena = torch.empty(sum(a + b for a, b in sizes), dtype=torch.float64, device=self.dev)
+            if self.x3_stream is not None:      # _x3_allowed asks for the measured queue count: probed here, not inside the backward pass
+                from . import ddp
+                ddp.hw_queues(self.dev)
+            off = 0
+            for u, (a, b) in zip(self.convs, sizes):
+                u.sync_red, u.sync_tot = self._sync_arena[off:off + a], self._sync_arena[off + a:off + a + b]
+                off += a + b
 
     @staticmethod
     def executed_fraction(u, direction):
@@ -834,6 +866,13 @@ class _Engine:
 
     def _fwd_finalize(self, u, training, s):
         v = u.vec
+        if training and u.bn_sync:
+            # synchronised BatchNorm: this rank's totals and pixel count, summed over the ranks, then the usual outputs from the global sums
+            call('clamd_bn_rows_total', ptr(u.stats), u.stat_rows, 2, u.cout_p, float(self.B * u.h * u.w_), None, ptr(u.sync_red), s)
+            syncbn.all_reduce(u.sync_red, self.bn_group)
+            call('clamd_bn_finalize_total', ptr(u.sync_red), ptr(u.gamma), ptr(u.beta), ptr(u.rm), ptr(u.rv), ptr(v[0]), ptr(v[1]), ptr(v[2]),
+                 ptr(v[3]), u.cout_p, u.cout, BN_MOMENTUM, BN_EPS, ptr(u.nbt), s)
+            return
         call('clamd_bn_finalize', ptr(u.stats) if training else None, u.stat_rows, ptr(u.gamma), ptr(u.beta), ptr(u.rm), ptr(u.rv),
              ptr(v[0]), ptr(v[1]), ptr(v[2]), ptr(v[3]), u.cout_p, u.cout, float(self.B * u.h * u.w_), BN_MOMENTUM, BN_EPS,
              ptr(u.nbt) if training else None, s)      # num_batches_tracked += 1 inside the launch (was a torch._foreach_add_ on the critical chain)
@@ -874,6 +913,8 @@ class _Engine:
         if tuple(self.tuning.as_dict().values()) != self._tune_key:
             # the partial-row buffers were planned for the forward's kernel structure
             raise RuntimeError('model.tuning changed between forward and backward: change it between steps (before the forward)')
+        if self.bn_group is not None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('UNet.backward: SyncBatchNorm layers in train mode all-reduce their sums, which a captured graph cannot do')
         p0 = next(iter(m.parameters()))
         if p0.grad is not None:
             lo = self.gflat.data_ptr()
@@ -949,11 +990,12 @@ class _Engine:
         """The third stream only where it cannot end up on a hardware queue with RCCL's kernels: HIP multiplexes streams onto a fixed number of
         hardware queues in creation order and a kernel waits behind whatever shares its queue.  A data-parallel rank has the default stream,
         the second and third streams, GradSync's stream and RCCL's: five -- so under ddp.GradSync the third stream needs at least eight queues
-        (two rounds of the assignment apart).  The count is MEASURED (ddp.hw_queues: spin kernels on eight streams), not read from
-        GPU_MAX_HW_QUEUES -- the runtime reads that variable once, when it starts."""
+        (two rounds of the assignment apart).  Synchronised BatchNorm adds the stream of its own group's communicator (six with GradSync,
+        four without): any RCCL stream in play asks for the same eight.  The count is MEASURED (ddp.hw_queues: spin kernels on eight
+        streams), not read from GPU_MAX_HW_QUEUES -- the runtime reads that variable once, when it starts."""
         if self.x3_stream is None or self.wg_stream is None or KERNEL_TIMING is not None:
             return False
-        if self.model.grad_sync is not None:
+        if self.model.grad_sync is not None or self.bn_group is not None:
             from . import ddp
             if ddp.hw_queues(self.dev) < 8:
                 return False
@@ -987,8 +1029,16 @@ class _Engine:
                     _hbm('bn_bwd', 0,                      # algorithmically free: one backward pass reads g and y once (the apply pass below is charged for it)
                          'clamd_bn_bwd_reduce', ptr(ga), ga_ldc, ptr(gp), gp.shape[-1] if gp is not None else 0, ptr(u.y), u.y_ldc,
                          ptr(v[0]), ptr(v[1]), ptr(u.sums), u.sum_rows, B, u.h, u.w_, u.cout_p, dc, tp, s)
-                call('clamd_bn_bwd_finalize', ptr(u.sums), u.sum_rows, ptr(u.gamma), ptr(v[2]), ptr(v[3]), ptr(v[4]), g[u.keys[2]],
-                     g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, count, s)
+                if u.bn_sync:
+                    # synchronised BatchNorm: k0, k1, k2 from sum g, sum g y and the count of all ranks (critical chain: the collective sits
+                    # between this unit's sums and its apply pass); d gamma, d beta, d conv-bias from this rank's totals, as torch
+                    call('clamd_bn_rows_total', ptr(u.sums), u.sum_rows, self.NS, u.cout_p, count, ptr(u.sync_tot), ptr(u.sync_red), s)
+                    syncbn.all_reduce(u.sync_red, self.bn_group)
+                    call('clamd_bn_bwd_finalize_total', ptr(u.sync_tot), ptr(u.sync_red), ptr(u.gamma), ptr(v[2]), ptr(v[3]), ptr(v[4]),
+                         g[u.keys[2]], g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, s)
+                else:
+                    call('clamd_bn_bwd_finalize', ptr(u.sums), u.sum_rows, ptr(u.gamma), ptr(v[2]), ptr(v[3]), ptr(v[4]), g[u.keys[2]],
+                         g[u.keys[3]], None if two else g[u.keys[1]], u.cout_p, u.cout, count, s)
             if two:
                 assert gp is None
                 _hbm('bn_bwd', self.esize * B * u.h * u.w_ * u.cout * 3,

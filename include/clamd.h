@@ -316,6 +316,24 @@ int clamd_bn_bwd_eval(const void* ga, int ga_ldc, const void* gp, int gp_ldc, co
                       void* gz, int gz_ldc, float* rows, int nrows, int B, int H, int W, int Cp, int C, int dtype, void* stream);
 int clamd_bn_bwd_eval_finalize(const float* rows, int nrows, int nsums, const float* scale, const float* save_mean, const float* save_istd,
                                float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C, void* stream);
+/* Synchronised BatchNorm (torch.nn.SyncBatchNorm): the statistics of a train-mode layer come from the whole global batch.  The partial rows
+ * of one rank are added into fp64 totals, the caller all-reduces (SUM) the [2][Cp] + 1 doubles of `reduce` across ranks, and the *_total
+ * finalizes read the result.  With one rank (or equal totals) the outputs are those of clamd_bn_finalize / clamd_bn_bwd_finalize on the
+ * same rows, bit for bit.
+ * clamd_bn_rows_total: rows[nrows][nk][Cp] (nk = 2: clamd_bn_finalize's statistics rows; nk = 5 = clamd_bn_bwd_nsums(): backward sums,
+ * the two-sum form included) added in the fixed order of the finalize kernels -> totals[nk][Cp] (optional, this rank's own) and
+ * reduce[0..2Cp) = totals k = 0, 1, reduce[2Cp] = count (optional; the buffer to all-reduce).  At least one of the two.
+ * clamd_bn_finalize_total: clamd_bn_finalize in train mode from the all-reduced (sum x, sum x^2, count): scale / shift / save_mean /
+ * save_istd, running statistics with the global count, num_batches_tracked += 1.
+ * clamd_bn_bwd_finalize_total: clamd_bn_bwd_finalize with k0, k1, k2 from the all-reduced (sum g, sum g y, count) and d gamma, d beta,
+ * d conv-bias from this rank's totals[5][Cp] (as torch: the parameter gradients are all-reduced with the others).  dbias = NULL: the
+ * two-sum form (k = 2..4 unused). */
+int clamd_bn_rows_total(const float* rows, int nrows, int nk, int Cp, double count, double* totals, double* reduce, void* stream);
+int clamd_bn_finalize_total(const double* reduce, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            float* scale, float* shift, float* save_mean, float* save_istd, int Cp, int C, double momentum, double eps,
+                            long long* num_batches_tracked, void* stream);
+int clamd_bn_bwd_finalize_total(const double* totals, const double* reduce, const float* gamma, const float* save_mean,
+                                const float* save_istd, float* k012, float* dgamma, float* dbeta, float* dbias, int Cp, int C, void* stream);
 /* nn.MaxPool2d(2,2) alone (models/unet.py:12: the first layer of a DownBlock run as a stand-alone block, blocks.py; inside the UNet step
  * the pool is part of clamd_bn_apply / clamd_bn_bwd_*): x [B,H,W,ldc] -> pooled [B,H/2,W/2,ldc]; backward: gx [B,H,W,ldc] = gp at the first
  * maximum of each window (the tie rule of clamd_bn_apply and of torch's CPU kernel), 0 elsewhere.
