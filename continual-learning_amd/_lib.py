@@ -52,6 +52,7 @@ SIGNATURES = {
     'clamd_sizeof_pack_job': (_I, []),
     'clamd_sizeof_adam_tensor': (_I, []),
     'clamd_adam_chunk_elems': (_I, []),
+    'clamd_sizeof_importance_tensor': (_I, []),
     'clamd_pack_tile': (_I, []),
     'clamd_bn_bwd_nsums': (_I, []),
     'clamd_sizeof_tuning': (_I, []),
@@ -125,6 +126,8 @@ SIGNATURES = {
     'clamd_ce_count': (_I, [_P, _I, _I, _I, _I, _LL, _P, _SZ, _P]),
     'clamd_ce_fwd_bwd_counted': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
     'clamd_adam_step': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    'clamd_adam_step_consolidated': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),
     'clamd_argmax_confusion': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'clamd_voc_prepare': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'clamd_label_to_rgb': (_I, [_P, _P, _LL, _LL, _P]),

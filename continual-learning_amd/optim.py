@@ -8,6 +8,10 @@ can be replayed while a scheduler (trainer.py:111-112,147) changes ``param_group
 
 Optional L2-to-old-weights regulariser (build-defined): ``set_l2_anchor(old_params, lam)`` adds
 2*lam*(theta - theta_old) to every gradient inside the same kernel.
+
+Optional elastic weight consolidation (build-defined as well): ``set_consolidation(old_params, importance, lam)`` adds
+lam*omega*(theta - theta_old); such a step runs ``clamd_adam_step_consolidated`` (36 B / parameter), every other step the unchanged
+``clamd_adam_step``.
 """
 import numpy as np
 import torch
@@ -29,6 +33,10 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_scale = grad_scale
         self._l2_lambda = 0.0
         self._anchor = None
+        self._l2_on = False           # the anchor serves the L2 term, the consolidation term, or both
+        self._importance = None
+        self._ewc_lambda = 0.0
+        self._ewcacc = None
         self._table = None
         self._hyper_host = None
         self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
@@ -79,6 +87,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._nchunks = len(chunks)
         self._numel = int(sum(p.numel() for p in params))
         self._l2acc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+        self._ewcacc = self._importance_dev = None
+        if self._importance is not None:
+            self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
+            self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
         self._table = [(p.data_ptr(), p.grad.data_ptr()) for p in params]
 
     def load_state_dict(self, state_dict):
@@ -88,23 +100,78 @@ class FusedAdam(torch.optim.Optimizer):
             del self._m
 
     def set_l2_anchor(self, old_params, lam):
-        """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot)."""
-        self._anchor = [o.detach().contiguous().float() for o in old_params] if old_params is not None else None
-        self._l2_lambda = float(lam) if old_params is not None else 0.0
+        """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot).  With a consolidation set the
+        anchor is shared (one pointer per tensor in the device table): it has to be the same snapshot."""
+        anchor = [o.detach().contiguous().float() for o in old_params] if old_params is not None else None
+        if anchor is not None and self._importance is not None:
+            self._same_anchor(anchor)
+        elif self._importance is None:
+            self._anchor = anchor
+        self._l2_on = anchor is not None
+        self._l2_lambda = float(lam) if anchor is not None else 0.0
         self._table = None
         self._hyper_host = None
+
+    def _same_anchor(self, anchor):
+        """Setup-time check (compares on the device, so it synchronises; never on the step path)."""
+        if len(anchor) != len(self._anchor) or not all(a.shape == b.shape and a.device == b.device and
+                                                       (a.data_ptr() == b.data_ptr() or torch.equal(a, b))
+                                                       for a, b in zip(anchor, self._anchor)):
+            raise ValueError('FusedAdam: the L2 anchor and the consolidation anchor must be the same snapshot (one anchor per tensor)')
 
     def l2_penalty(self):
         """lam * sum ||theta - theta_old||^2 as accumulated by the LAST step (device scalar)."""
         return self._l2acc[:1] * self._l2_lambda
 
+    def set_consolidation(self, old_params, importance, lam):
+        """Elastic weight consolidation: every step adds lam * importance * (theta - old) to the gradient inside the Adam kernel.
+        old_params / importance: lists of tensors aligned with this optimiser's parameters (same shapes, on the parameters' device; the
+        importance fp32 and contiguous -- it is read in place, so a consolidate.Consolidation can update it between steps).
+        importance >= 0 is the caller's contract: it is not checked (that would synchronise).  old_params None clears the term."""
+        if old_params is None:
+            self._importance, self._ewc_lambda = None, 0.0
+            if not self._l2_on:
+                self._anchor = None
+            self._table = None
+            self._hyper_host = None
+            return
+        params = self.param_groups[0]['params']
+        old_params, importance = list(old_params), list(importance)
+        if len(old_params) != len(params) or len(importance) != len(params):
+            raise ValueError(f'FusedAdam.set_consolidation: {len(params)} parameters, {len(old_params)} anchors, {len(importance)} importance tensors')
+        for i, (p, o, w) in enumerate(zip(params, old_params, importance)):
+            if o.shape != p.shape or w.shape != p.shape:
+                raise ValueError(f'FusedAdam.set_consolidation: parameter {i} has shape {tuple(p.shape)}, anchor {tuple(o.shape)}, '
+                                 f'importance {tuple(w.shape)}')
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                raise ValueError(f'FusedAdam.set_consolidation: importance {i} must be contiguous fp32')
+            if o.device != p.device or w.device != p.device:
+                raise ValueError(f'FusedAdam.set_consolidation: parameter {i} is on {p.device}, anchor on {o.device}, importance on {w.device}')
+        if not float(lam) >= 0.0:
+            raise ValueError('FusedAdam.set_consolidation: lam must be >= 0')
+        anchor = [o.detach().contiguous().float() for o in old_params]
+        if self._l2_on:
+            self._same_anchor(anchor)         # the L2 anchor stays: one pointer per tensor serves both terms
+        else:
+            self._anchor = anchor
+        self._importance = [w.detach() for w in importance]
+        self._ewc_lambda = float(lam)
+        self._table = None
+        self._hyper_host = None
+
+    def consolidation_penalty(self):
+        """(lam / 2) * sum importance * (theta - theta_old)^2 as accumulated by the LAST step (device scalar)."""
+        if self._ewcacc is None:
+            raise RuntimeError('FusedAdam.consolidation_penalty: no step with a consolidation has run')
+        return self._ewcacc[:1] * (0.5 * self._ewc_lambda)
+
     def sync_hyper(self):
-        """Upload lr / betas / eps / gradient scale / L2 weight to device memory if they changed on the host (LambdaLR
+        """Upload lr / betas / eps / gradient scale / L2 and consolidation weights to device memory if they changed on the host (LambdaLR
         writes param_groups[0]['lr']).  step() calls this; a replayed HIP graph of the step (tools/graphed_step.py) calls it
         before every replay, because the captured Adam kernel reads the values from that device buffer."""
         group = self.param_groups[0]
         hyper = (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]), float(group['eps']),
-                 float(self.grad_scale), float(self._l2_lambda), 0.0, 0.0)
+                 float(self.grad_scale), float(self._l2_lambda), float(self._ewc_lambda), 0.0)
         if hyper != self._hyper_host:
             self._hyper.copy_(torch.tensor(hyper, dtype=torch.float32))
             self._hyper_host = hyper
@@ -136,9 +203,15 @@ class FusedAdam(torch.optim.Optimizer):
             self._build_table(params)
         self.sync_hyper()
         from . import unet as U
-        U._hbm('adam', 28 * self._numel,      # p, g, m, v read; p, m, v written
-               'clamd_adam_step', ptr(self._tensors_dev), ptr(self._chunks_dev), self._nchunks, ptr(self._hyper),
-               ptr(self._step_dev), ptr(self._derived), ptr(self._l2acc) if self._anchor is not None else None,
-               _lib.stream_ptr())
+        if self._importance is not None:
+            U._hbm('adam', 36 * self._numel,      # p, g, m, v, old, importance read; p, m, v written
+                   'clamd_adam_step_consolidated', ptr(self._tensors_dev), ptr(self._importance_dev), ptr(self._chunks_dev), self._nchunks,
+                   ptr(self._hyper), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc),
+                   ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
+        else:
+            U._hbm('adam', 28 * self._numel,      # p, g, m, v read; p, m, v written
+                   'clamd_adam_step', ptr(self._tensors_dev), ptr(self._chunks_dev), self._nchunks, ptr(self._hyper),
+                   ptr(self._step_dev), ptr(self._derived), ptr(self._l2acc) if self._anchor is not None else None,
+                   _lib.stream_ptr())
         self._step_host += 1                # host-side mirror of the device counter (shared by all param states)
         return loss

@@ -11,7 +11,8 @@ Out of scope here: JPEG dumps, prints, checkpoint file
 (trainer.py:177-189) are computed on the GPU by metrics.argmax_confusion instead of .cpu() round trips.
 Continual learning (config 4): ``begin_task2(c_old, ...)`` snapshots the model and switches the criterion to
 DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined); ``freeze_bn=True`` also trains task 2 with
-every BatchNorm in eval mode (running statistics, not updated).
+every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0`` estimates the finished task's per-parameter importance
+(``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py).
 Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
 of the global batch, syncbn.py).
 """
@@ -26,6 +27,7 @@ from torch.optim.lr_scheduler import LambdaLR
 from .loss import CrossEntropyLoss, DistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam
+from .consolidate import Consolidation
 from . import syncbn
 from .unet import UNet
 
@@ -45,6 +47,8 @@ class Trainer:
         self.device = torch.device(device)
         self.start_epoch = 0
         self.old_model = None
+        self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
+        self.ewc_lambda = 0.0
         self.build_model()
 
     def build_model(self):
@@ -60,10 +64,51 @@ class Trainer:
     def reset_grad(self):
         self.optim.zero_grad()
 
-    def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False):
+    def estimate_importance(self, data_loader, max_batches=None):
+        """Diagonal empirical Fisher information of the current model over a loader -> consolidate.Consolidation (finished; its anchor is
+        a clone of the current weights).  Every module in eval mode (BatchNorm on its running statistics, nothing updated), one
+        CrossEntropyLoss backward per batch, the squared gradients averaged over the batches; no optimizer step.  A loader of batch size 1
+        gives the per-image estimate, larger batches the square of the batch-mean gradient (consolidate.py).  Under an initialised process
+        group every rank ends with the mean over all ranks' batches.  Each module's own mode is restored and the gradients are cleared."""
+        model = self.model
+        modes = [(mod, mod.training) for mod in model.modules()]
+        sync, model.grad_sync = model.grad_sync, None      # the gradient exchange would average the gradients BEFORE they are squared
+        cons = Consolidation(model.named_parameters())
+        params = list(model.parameters())
+        try:
+            model.eval()
+            for i, (images, masks) in enumerate(data_loader):
+                if max_batches is not None and i >= max_batches:
+                    break
+                outputs = model(images.to(self.device, non_blocking=True))
+                self.reset_grad()
+                self.c_loss(outputs, masks.to(self.device, non_blocking=True)).backward()
+                cons.accumulate(params)
+            cons.finish()
+        finally:
+            self.reset_grad()
+            for mod, mode in modes:
+                mod.training = mode
+            model.grad_sync = sync
+        return cons
+
+    def _apply_consolidation(self):
+        self.optim.set_consolidation(self.consolidation.anchor, self.consolidation.importance, self.ewc_lambda)
+
+    def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
+                    importance_loader=None, ewc_gamma=1.0):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
-        still reach gamma and beta)."""
+        still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
+        importance_loader (default: the training loader) before anything of the new task is switched on, merged with the previous tasks'
+        (importance <- ewc_gamma * previous + new, online EWC) when this is not the first call, and the Adam kernel adds
+        ewc_lambda * importance * (theta - theta_old) to every gradient."""
+        if ewc_lambda > 0:
+            cons = self.estimate_importance(self.train_data_loader if importance_loader is None else importance_loader)
+            cons.gamma = float(ewc_gamma)
+            if self.consolidation is not None:
+                cons.merge_from(self.consolidation, ewc_gamma)
+            self.consolidation, self.ewc_lambda = cons, float(ewc_lambda)
         # a fresh module with a CLONE of the state (not copy.deepcopy: that would duplicate the engine's multi-GB activation
         # buffers and, under data parallelism, the GradSync object with its process group and stream)
         m = self.model
@@ -73,8 +118,12 @@ class Trainer:
         for p in self.old_model.parameters():
             p.requires_grad_(False)
         self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
+        if ewc_lambda > 0:
+            self.optim.set_l2_anchor(None, 0.0)        # an earlier task's L2 anchor is another snapshot than the new consolidation anchor
+            self._apply_consolidation()
         if l2_lambda > 0:
-            self.optim.set_l2_anchor([p.detach().clone() for p in self.old_model.parameters()], l2_lambda)
+            self.optim.set_l2_anchor(self.consolidation.anchor if ewc_lambda > 0 else [p.detach().clone() for p in self.old_model.parameters()],
+                                     l2_lambda)
         if freeze_bn:
             for mod in m.modules():
                 if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
@@ -102,14 +151,24 @@ class Trainer:
             opt_host = {'param_groups': opt['param_groups'],
                         'state': {i: {n: (t.to('cpu', non_blocking=True) if torch.is_tensor(t) and t.is_cuda else t)
                                       for n, t in s.items()} for i, s in opt['state'].items()}}
+            cons_host = None
+            if self.consolidation is not None:       # one optional key beside the reference's four
+                cs = self.consolidation.state_dict()
+                cons_host = {'anchor': {n: t.to('cpu', non_blocking=True) for n, t in cs['anchor'].items()},
+                             'importance': {n: t.to('cpu', non_blocking=True) for n, t in cs['importance'].items()},
+                             'lambda': self.ewc_lambda, 'gamma': cs['gamma'], 'n_batches': cs['n_batches']}
             done = torch.cuda.Event()
             done.record(st)
-        return {'epoch': epoch + 1, 'model_state': host, 'optimizer_state': opt_host,
+        snap = {'epoch': epoch + 1, 'model_state': host, 'optimizer_state': opt_host,
                 'scheduler_state': self.scheduler.state_dict(), '_event': done}
+        if cons_host is not None:
+            snap['consolidation_state'] = cons_host
+        return snap
 
     def save_network(self, network_label, epoch_label, epoch, save_dir):
         """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/
-        scheduler_state (loadable by the reference's load_network and by torch.optim.Adam)."""
+        scheduler_state (loadable by the reference's load_network and by torch.optim.Adam); with elastic weight consolidation
+        active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -127,7 +186,17 @@ class Trainer:
         self.start_epoch = ck['epoch']
         self.optim.load_state_dict(ck['optimizer_state'])
         self.scheduler.load_state_dict(ck['scheduler_state'])
+        self.load_consolidation_state(ck.get('consolidation_state'))
         return True
+
+    def load_consolidation_state(self, state):
+        """Restores what snapshot() stored under 'consolidation_state' (None, e.g. a checkpoint without the key: nothing changes)."""
+        if state is None:
+            return
+        cons = Consolidation(self.model.named_parameters())
+        cons.load_state_dict(state)
+        self.consolidation, self.ewc_lambda = cons, float(state['lambda'])
+        self._apply_consolidation()
 
     def train_step(self, inputs, labels):
         """trainer.py:172-176."""

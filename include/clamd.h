@@ -39,6 +39,7 @@ int clamd_version(void);
 int clamd_sizeof_pack_job(void);
 int clamd_sizeof_adam_tensor(void);
 int clamd_adam_chunk_elems(void);
+int clamd_sizeof_importance_tensor(void);   /* clamd_importance_accum: one table row {float* dst; const float* src; long long n} */
 int clamd_pack_tile(void);            /* clamd_pack: blocks per job = ceil(Np/tile) * ceil(Kp/tile) */
 int clamd_bn_bwd_nsums(void);
 
@@ -383,6 +384,23 @@ int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float
  * order (no float atomics: the value is bit-reproducible). */
 int clamd_adam_step(const void* tensors_dev, const void* chunks_dev, int nchunks, const float* hyper_dev, int* step_dev,
                     float* derived_dev, float* l2_accum_dev, void* stream);
+/* The same step with the elastic-weight-consolidation term (build-defined, like the L2 term: the reference has neither):
+ * g += lam_ewc * omega * (theta - theta_old) on top of 2 * l2_lambda * (theta - theta_old); one anchor (the `old` pointer of the
+ * unchanged 48-byte Adam table, required here) serves both.  importance_dev: device array of one `const float*` per table row,
+ * omega >= 0 of the row's shape.  lam_ewc = hyper_dev[6] (device memory: a replayed graph sees a changed value).
+ * ewc_accum_dev: 1 + nchunks floats, [0] = sum omega (theta - theta_old)^2 of this step, reduced like l2_accum_dev (fixed order, no
+ * float atomics, bit-reproducible); l2_accum_dev (optional): sum (theta - theta_old)^2 as in clamd_adam_step.  36 B / parameter.
+ * A step without consolidation keeps calling clamd_adam_step: its kernel is untouched. */
+int clamd_adam_step_consolidated(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks,
+                                 const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev,
+                                 void* stream);
+/* dst = decay * dst + scale * (power == 2 ? src * src : src) over every tensor of a device table of clamd_sizeof_importance_tensor()-byte
+ * rows {float* dst; const float* src; long long n}, in ONE launch through a (tensor, chunk) job list as the Adam step uses (chunks of
+ * clamd_adam_chunk_elems() elements).  The three passes of the Fisher-diagonal estimate: accumulate g*g (decay 1, scale 1, power 2,
+ * src = the gradient), normalise (decay 1/N, scale 0, src = dst) and the online merge (decay gamma, scale 1, power 1, src = the new
+ * importance; or, kept in the new one, decay 1, scale gamma, src = the previous importance).  decay and scale must be finite and >= 0.  Enqueue only: no allocation, no synchronisation, no atomics; element-wise,
+ * so bit-reproducible.  12 B / element; dst and src need 4-byte alignment only (16-byte accesses from dst's first 16-byte boundary). */
+int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double scale, int power, void* stream);
 /* argmax over classes + confusion matrix (trainer.py:183-188, metrics.py:32-38). */
 int clamd_argmax_confusion(const float* logits, const long long* labels, long long* pred, unsigned long long* conf,
                            int B, int K, int Kc, int H, int W, void* stream);
