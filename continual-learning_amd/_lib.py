@@ -125,6 +125,7 @@ SIGNATURES = {
     'clamd_ce_fwd_bwd': (_I, [_P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
     'clamd_ce_count': (_I, [_P, _I, _I, _I, _I, _LL, _P, _SZ, _P]),
     'clamd_ce_fwd_bwd_counted': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
+    'clamd_ce_unbiased_fwd_bwd': (_I, [_P, _P, _P, _I, _I, _D, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
     'clamd_adam_step': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     'clamd_adam_step_consolidated': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),

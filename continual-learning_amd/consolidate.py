@@ -122,6 +122,34 @@ class Consolidation:
         self.gamma = gamma
         return self
 
+    @torch.no_grad()
+    def grow(self, name, new_param):
+        """Class-incremental head growth: parameter `name` now has more rows along dim 0 (UNet.expand_classes).  The flat importance buffer
+        is laid out again once: old rows keep their importance, the new rows get zero, and their anchor is new_param's current (initial)
+        value -- no pull on classes the finished task never had.  Anything but growth along dim 0 is a ValueError."""
+        if name not in self.names:
+            raise KeyError(f'Consolidation.grow: no parameter {name!r}')
+        i = self.names.index(name)
+        old, new = self.shapes[i], tuple(new_param.shape)
+        if len(new) != len(old) or len(old) < 1 or new[0] <= old[0] or new[1:] != old[1:]:
+            raise ValueError(f'Consolidation.grow: {name}: {old} -> {new} is not growth along dim 0')
+        shapes = list(self.shapes)
+        shapes[i] = new
+        sizes = [int(np.prod(sh)) for sh in shapes]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.device)
+        views, off = [], 0
+        for j, (k, shape) in enumerate(zip(sizes, shapes)):
+            w = flat[off:off + k].view(shape)
+            w[:self.shapes[j][0]].copy_(self.importance[j])
+            views.append(w)
+            off += k
+        anchor = new_param.detach().clone().float().contiguous().to(self.device)
+        anchor[:old[0]].copy_(self.anchor[i])
+        self.flat, self.importance, self.shapes = flat, views, shapes
+        self.anchor[i] = anchor
+        self._tables.clear()
+        return self
+
     # ---- checkpoints ------------------------------------------------------------------------------------------------
     def state_dict(self):
         """Tensors by parameter NAME (views of this object's buffers: clone or copy them to keep them)."""

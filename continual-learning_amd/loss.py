@@ -7,6 +7,9 @@ pass: the forward computes the loss and d loss / d logits; backward only scales 
 ``DistillationCrossEntropy`` adds  lam * mean_px KL(softmax(z_old[:, :c_old]/T) || softmax(z[:, :c_old]/T))  (LwF-style,
 SURVEY.md §8a row A12).  The reference has NO such code: this term is build-defined and its parity is
 pinned only by tests against this repo's own CPU restatement.
+
+``UnbiasedDistillationCrossEntropy`` is the class-incremental step's criterion (build-defined and parity-unpinned as well): the unbiased
+cross-entropy and unbiased distillation of Cermelli et al. (CVPR 2020) as include/clamd.h states them, on ``clamd_ce_unbiased_fwd_bwd``.
 """
 import os
 
@@ -110,3 +113,72 @@ class DistillationCrossEntropy(nn.Module):
 
     def forward(self, logits, labels, old_logits):
         return _CEFn.apply(logits, labels, old_logits.detach(), self.c_old, self.temperature, self.lam, self.ignore_index, self)
+
+
+class _UCEFn(torch.autograd.Function):
+    """clamd_ce_count + clamd_ce_unbiased_fwd_bwd; the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, old_logits, c_old, lam, ignore_index, holder):
+        if not logits.is_cuda or not labels.is_cuda or (old_logits is not None and not old_logits.is_cuda):
+            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
+        lib = _lib.load()
+        logits_in = logits
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            raise TypeError('labels must be int64 (datasets/voc.py:72)')
+        B, K, H, W = logits.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
+        kold = 0
+        if old_logits is not None:
+            old_logits = old_logits.contiguous().float()
+            kold = old_logits.shape[1]
+            if old_logits.dim() != 4 or old_logits.shape[0] != B or tuple(old_logits.shape[2:]) != (H, W):
+                raise ValueError('old_logits must be [B, K_old, H, W]')
+        dl = torch.empty_like(logits)
+        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+        wsb = lib.clamd_ce_workspace_bytes()
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
+        from . import unet as U
+        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
+        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
+        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
+        kd = old_logits is not None and lam != 0
+        # algorithmic bytes: logits read, d logits written, the c_old old-model logits, the label, the NHWC copy
+        U._hbm('loss', B * H * W * ((2 * K + (c_old if kd else 0)) * 4 + 8 + (ldc * eng.esize if eng is not None else 0)),
+               'clamd_ce_unbiased_fwd_bwd', ptr(logits), ptr(labels), ptr(old_logits), kold, int(c_old), float(lam), ptr(dl), ptr(nh), ldc, dcode,
+               ptr(out3), ptr(ws), wsb, B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
+        ctx.sink = None
+        if eng is not None:
+            ctx.sink = eng
+            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)      # a strong reference, as in _CEFn.forward
+        ctx.save_for_backward(dl)
+        ctx.parts = out3
+        off = lib.clamd_ce_bad_label_count_offset() // 4
+        holder.bad_labels = ws[off:off + 1].view(torch.int32)
+        holder.parts = out3
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return _CEFn.backward(ctx, g)[:7]
+
+
+class UnbiasedDistillationCrossEntropy(nn.Module):
+    """Unbiased cross-entropy + lam * unbiased distillation over the old classes [0, c_old) (class 0 = background); build-defined, parity
+    unpinned.  A label below c_old means "background or any old class"; the old model's background is compared with the new model's
+    background-or-new-class mass.  ``old_logits`` None: the cross-entropy term alone.  After a forward: ``parts`` = device {total, ce, kd},
+    ``bad_labels`` as on CrossEntropyLoss."""
+
+    def __init__(self, c_old, lam=10.0, ignore_index=-100):
+        super().__init__()
+        if c_old < 1:
+            raise ValueError('c_old must be >= 1 (class 0, the background, is always an old class)')
+        self.c_old, self.lam, self.ignore_index = int(c_old), float(lam), ignore_index
+        self.bad_labels = None
+        self.parts = None
+
+    def forward(self, logits, labels, old_logits=None):
+        return _UCEFn.apply(logits, labels, None if old_logits is None else old_logits.detach(), self.c_old, self.lam, self.ignore_index, self)

@@ -53,6 +53,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._derived = torch.zeros(2, dtype=torch.float32, device=dev)
         self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+        self._hyper_host = None       # a new device buffer: sync_hyper uploads again
         self._l2acc = None            # [0] = sum ||theta - theta_old||^2 of the last step, [1..] = per-workgroup partials
         off, steps0 = 0, set()
         self._step_host = torch.tensor(0.0)          # ONE host-side step counter shared by every parameter's state
@@ -99,6 +100,54 @@ class FusedAdam(torch.optim.Optimizer):
         if hasattr(self, '_m'):
             del self._m
 
+    @staticmethod
+    def _grown(old, new_shape, fill):
+        """`old` with rows appended along dim 0 up to new_shape; the new rows take `fill`'s (None: zero)."""
+        out = torch.zeros(new_shape, dtype=old.dtype, device=old.device)
+        out[:old.shape[0]].copy_(old)
+        if fill is not None:
+            out[old.shape[0]:].copy_(fill[old.shape[0]:])
+        return out
+
+    @torch.no_grad()
+    def replace_params(self, mapping):
+        """Class-incremental head growth (UNet.expand_classes): swaps parameter objects inside the group and re-homes their state.
+        mapping: {old_param: new_param}; new_param has more rows along dim 0 and the same trailing shape (anything else: ValueError).
+        exp_avg / exp_avg_sq of the leading rows are kept, the new rows start at zero, the shared step counter stays.  The L2 /
+        consolidation anchor of the new rows is their current (initial) value and their importance zero: nothing pulls on classes the
+        finished task never had.  The importance list is replaced (grown copies); a Consolidation re-installs its own views after
+        Consolidation.grow.  Device tables are rebuilt at the next step."""
+        params = self.param_groups[0]['params']
+        index = {id(p): i for i, p in enumerate(params)}
+        todo = []
+        for old, new in mapping.items():
+            if id(old) not in index:
+                raise ValueError('FusedAdam.replace_params: a key of the mapping is not a parameter of this optimiser')
+            if old.dim() != new.dim() or old.dim() < 1 or new.shape[0] <= old.shape[0] or new.shape[1:] != old.shape[1:]:
+                raise ValueError(f'FusedAdam.replace_params: {tuple(old.shape)} -> {tuple(new.shape)} is not growth along dim 0')
+            if new.device != old.device or new.dtype != old.dtype:
+                raise ValueError('FusedAdam.replace_params: the new parameter must keep the device and dtype')
+            todo.append((index[id(old)], old, new))
+        states = [self.state.get(p) for p in params]
+        for i, old, new in todo:
+            st = states[i]
+            if st:       # moments of the leading rows; _init_state re-homes them into new flat buffers at the next step
+                states[i] = {'step': st['step'], 'exp_avg': self._grown(st['exp_avg'], new.shape, None),
+                             'exp_avg_sq': self._grown(st['exp_avg_sq'], new.shape, None)}
+            if self._anchor is not None:
+                self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
+            if self._importance is not None:
+                self._importance[i] = self._grown(self._importance[i], new.shape, None)
+            self.state.pop(old, None)
+            params[i] = new
+        step = float(self._step_host) if hasattr(self, '_step_host') else None
+        for p, st in zip(params, states):
+            if st:
+                self.state[p] = dict(st, step=torch.tensor(step) if step is not None else st['step'])
+        if hasattr(self, '_m'):
+            del self._m              # as after load_state_dict: the flat moment buffers are laid out again
+        self._table = None
+
     def set_l2_anchor(self, old_params, lam):
         """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot).  With a consolidation set the
         anchor is shared (one pointer per tensor in the device table): it has to be the same snapshot."""
@@ -118,6 +167,11 @@ class FusedAdam(torch.optim.Optimizer):
                                                        (a.data_ptr() == b.data_ptr() or torch.equal(a, b))
                                                        for a, b in zip(anchor, self._anchor)):
             raise ValueError('FusedAdam: the L2 anchor and the consolidation anchor must be the same snapshot (one anchor per tensor)')
+
+    @property
+    def l2_lambda(self):
+        """Weight of the L2-to-old-weights term (0 when it is off)."""
+        return self._l2_lambda if self._l2_on else 0.0
 
     def l2_penalty(self):
         """lam * sum ||theta - theta_old||^2 as accumulated by the LAST step (device scalar)."""

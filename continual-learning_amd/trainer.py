@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch.optim.lr_scheduler import LambdaLR
 
-from .loss import CrossEntropyLoss, DistillationCrossEntropy
+from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam
 from .consolidate import Consolidation
@@ -96,13 +96,17 @@ class Trainer:
         self.optim.set_consolidation(self.consolidation.anchor, self.consolidation.importance, self.ewc_lambda)
 
     def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
-                    importance_loader=None, ewc_gamma=1.0):
+                    importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background'):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
         still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
         importance_loader (default: the training loader) before anything of the new task is switched on, merged with the previous tasks'
         (importance <- ewc_gamma * previous + new, online EWC) when this is not the first call, and the Adam kernel adds
-        ewc_lambda * importance * (theta - theta_old) to every gradient."""
+        ewc_lambda * importance * (theta - theta_old) to every gradient.
+        Class-incremental step (build-defined): new_classes > 0 grows the trained model's head by that many outputs AFTER the importance
+        estimate and the snapshot (the old model keeps its width; UNet.expand_classes(new_classes, head_init)), carrying Adam's moments and
+        the anchors over; unbiased=True distils with UnbiasedDistillationCrossEntropy(c_old, distill_lambda) (no temperature) instead of
+        DistillationCrossEntropy.  A later call (task 3) snapshots the grown model: c_old is then the grown width."""
         if ewc_lambda > 0:
             cons = self.estimate_importance(self.train_data_loader if importance_loader is None else importance_loader)
             cons.gamma = float(ewc_gamma)
@@ -117,17 +121,50 @@ class Trainer:
         self.old_model.eval()
         for p in self.old_model.parameters():
             p.requires_grad_(False)
-        self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
+        if unbiased:
+            self.distill = UnbiasedDistillationCrossEntropy(c_old, distill_lambda)
+        else:
+            self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
         if ewc_lambda > 0:
             self.optim.set_l2_anchor(None, 0.0)        # an earlier task's L2 anchor is another snapshot than the new consolidation anchor
             self._apply_consolidation()
         if l2_lambda > 0:
             self.optim.set_l2_anchor(self.consolidation.anchor if ewc_lambda > 0 else [p.detach().clone() for p in self.old_model.parameters()],
                                      l2_lambda)
+        if new_classes > 0:
+            self.grow_head(new_classes, head_init)
         if freeze_bn:
             for mod in m.modules():
                 if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
                     mod.eval()
+
+    def grow_head(self, n, init='background'):
+        """UNet.expand_classes on the trained model with the optimiser state, the anchors and the consolidation carried over; cfg.num_classes
+        (the confusion-matrix width of train_epoch) follows.  Under an initialised process group the grown head is broadcast from rank 0
+        (init='default' draws the new rows from each rank's own RNG), so the replicas stay identical whatever their seeds."""
+        m = self.model
+        names = {id(p): k for k, p in m.named_parameters()}
+        ow, ob, nw, nb = m.expand_classes(n, init)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            group = m.grad_sync.group if m.grad_sync is not None else None
+            for t in (nw, nb):
+                torch.distributed.broadcast(t.data, src=0, group=group)
+        # The order matters.  (1) The Consolidation grows first: it owns the importance (one flat buffer, laid out again) and the anchors,
+        # and takes the new rows' anchor from the (broadcast) new parameters.  (2) replace_params swaps the parameter objects and re-homes
+        # Adam's moments; it also grows the optimiser's own anchor / importance entries, which is all there is when only the L2 term is on.
+        # (3) With a consolidation the optimiser must read the Consolidation's NEW importance views and anchors, so both terms are set
+        # again from it (set_l2_anchor(None) first: set_consolidation compares a kept L2 anchor with the one it is given).
+        if self.consolidation is not None:
+            self.consolidation.grow(names[id(ow)], nw)
+            self.consolidation.grow(names[id(ob)], nb)
+        self.optim.replace_params({ow: nw, ob: nb})
+        if self.consolidation is not None and self.ewc_lambda > 0:
+            l2 = self.optim.l2_lambda
+            self.optim.set_l2_anchor(None, 0.0)
+            self._apply_consolidation()
+            if l2 > 0:
+                self.optim.set_l2_anchor(self.consolidation.anchor, l2)
+        self.cfg.num_classes = m.num_classes
 
     # ---- checkpoints (SURVEY.md §8f row 3): same file name and keys as trainer.py:68-102, but the model never leaves
     # the GPU: the reference does network.cpu() ... network.cuda() (a full D2H + H2D round trip of 124 MB every

@@ -9,6 +9,7 @@ The child modules (nn.Conv2d, nn.BatchNorm2d, ...) are only PARAMETER CONTAINERS
 and backward are fixed schedules of C-ABI kernel launches on NHWC activations (fp32 or bf16) kept in buffers owned by
 PyTorch's allocator.  There is no CPU path: calling it with CPU tensors raises.
 """
+import math
 import os
 import weakref
 
@@ -288,6 +289,43 @@ class UNet(nn.Module):
         """``torch.max(self(x), 1)[1]`` (trainer.py:279) without materialising the logits: the arg-max over classes runs
         in the epilogue of the head kernel.  int64 [B,H,W]; every BatchNorm follows its own ``.training``."""
         return self._engine(x).forward(x.contiguous().float(), list(self.parameters()), predict=True)
+
+    MAX_CLASSES = 32      # the head's padded width cpad(K) and the loss kernels' register arrays
+
+    @torch.no_grad()
+    def expand_classes(self, n, init='background'):
+        """Class-incremental growth of the head (build-defined, parity unpinned): ``last.6`` goes from K to K + n output rows, old rows keep
+        their values.  init='background': every new row's weight is a copy of the background row's (row 0) and, with b0 the old background
+        bias, the background bias and every new bias become b0 - log(n + 1) -- the softmax of the grown head then gives every old class
+        k >= 1 its old probability and splits the old background probability evenly over background and the new classes.  init='default':
+        nn.Conv2d's own initialisation for the new rows (global torch RNG).  Parameter order and state_dict keys do not change; the engine
+        is dropped (the next forward plans and allocates for the new width).  Returns (old_weight, old_bias, new_weight, new_bias), the
+        mapping FusedAdam.replace_params / Consolidation.grow take."""
+        n, K = int(n), self.num_classes
+        if n <= 0:
+            raise ValueError(f'expand_classes: n must be positive, got {n}')
+        if K + n > self.MAX_CLASSES:
+            raise ValueError(f'expand_classes: {K} + {n} classes exceed the {self.MAX_CLASSES} the head and the loss kernels hold')
+        if init not in ('background', 'default'):
+            raise ValueError("expand_classes: init must be 'background' or 'default'")
+        st = self._table[-1]
+        kind, ti, cin, _ = st['tail']
+        seq = self._seq(st)
+        old = seq[ti]
+        new = _Conv2d(cin, K + n, 1, 1).to(device=old.weight.device, dtype=old.weight.dtype)      # torch's init: the 'default' rows
+        new.weight[:K].copy_(old.weight)
+        new.bias[:K].copy_(old.bias)
+        if init == 'background':
+            new.weight[K:].copy_(old.weight[:1].expand(n, -1, -1, -1))
+            b0 = old.bias[0] - math.log(n + 1)
+            new.bias[0] = b0
+            new.bias[K:] = b0
+        new.train(old.training)
+        seq[ti] = new
+        st['tail'] = (kind, ti, cin, K + n)      # the same dict is the stand-alone block's spec (blocks.py)
+        self.num_classes = K + n
+        self._engines = {}
+        return old.weight, old.bias, new.weight, new.bias
 
     def extra_repr(self):
         return f'num_classes={self.num_classes}, in_dim={self.in_dim}, conv_dim={self.conv_dim}, compute={self.compute_dtype}'

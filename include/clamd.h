@@ -378,6 +378,22 @@ int clamd_ce_count(const long long* labels, int B, int K, int H, int W, long lon
 int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype,
                              float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
                              double grad_scale, void* stream);
+/* The class-incremental step (build-defined, parity unpinned: the reference has no continual-learning code; the two terms follow Cermelli
+ * et al., "Modeling the Background for Incremental Learning in Semantic Segmentation", CVPR 2020).  Classes [0, c_old) are old, [c_old, K)
+ * new, class 0 is background; LSE(S) = log sum_{k in S} exp(z_k), bgnew = {0} u [c_old, K).
+ *   unbiased CE   -(LSE(old) - LSE(all)) for a label < c_old ("background or any old class"), -(z_y - LSE(all)) for a label >= c_old;
+ *                 mean over the pixels whose label is not ignore_index and lies in [0, K) (others are counted as by clamd_ce_fwd_bwd)
+ *   unbiased KD   q = softmax(old_logits[:, 0 .. c_old)), log p~_0 = LSE(bgnew) - LSE(all), log p~_k = z_k - LSE(all) for 1 <= k < c_old:
+ *                 -(1 / c_old) sum_k q_k log p~_k, mean over ALL B * H * W pixels, times lam; no temperature
+ * loss3 = {total, ce, kd}.  old_logits: [B, K_old_total, H, W] with K_old_total >= c_old; NULL or lam == 0: the CE term alone (kd = 0,
+ * old_logits not read).  With c_old == 1 and no KD term the results equal clamd_ce_fwd_bwd_counted's bit for bit.  The workspace holds
+ * clamd_ce_count's partial rows (same K, same stream, called before), as for clamd_ce_fwd_bwd_counted; dl_nhwc / dl_ldc / dl_dtype as
+ * there.  One pass over four pixels per thread with 16-byte accesses when H * W % 4 == 0 and logits / old_logits / dlogits are 16-byte
+ * and labels 32-byte aligned; any other size or alignment takes a one-pixel-per-thread variant of the same arithmetic inside this entry
+ * point (same results, slower).  Enqueue only: no allocation, no synchronisation, no atomics (bit-reproducible), graph-capturable. */
+int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
+                              float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
+                              int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream);
 /* torch.optim.Adam.step over all parameters in one launch (trainer.py:108-110,176); hyper/step/derived live on the
  * device so a captured graph can be replayed with a new learning rate.  l2_accum_dev (optional, with the L2-to-old-weights
  * term): 1 + nchunks floats, [0] = sum ||theta - theta_old||^2 of this step, [1..] = per-workgroup partials added in a fixed
