@@ -9,12 +9,9 @@ No stock-torch operator is involved and there is no CPU path.
 """
 import torch
 
-from . import _lib, syncbn
+from . import _lib, bnops, syncbn
 from ._lib import call, ptr
 from .ops import PackTable, TORCH_DT, cpad, from_nhwc, to_nhwc
-
-BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-
 
 def _stream():
     return _lib.stream_ptr()
@@ -63,15 +60,9 @@ class _BlockFn(torch.autograd.Function):
                 call('clamd_conv3x3', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(y), cout_p, ptr(stats), None, None, rows, B, H, W,
                      cin_p, cout_p, 1, 1 if 9 * cout_p > B * H * W else 0, dcode, None, s)
                 vec = torch.zeros(7, cout_p, dtype=torch.float32, device=dev)       # scale, shift, mean, istd, k0, k1, k2
-                if sync:       # the statistics of the global batch (as in the UNet engine)
-                    red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev)
-                    call('clamd_bn_rows_total', ptr(stats), rows, 2, cout_p, float(B * H * W), None, ptr(red), s)
-                    syncbn.all_reduce(red, group)
-                    call('clamd_bn_finalize_total', ptr(red), ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), ptr(vec[0]), ptr(vec[1]),
-                         ptr(vec[2]), ptr(vec[3]), cout_p, cout, BN_MOMENTUM, BN_EPS, ptr(nbt), s)
-                else:
-                    call('clamd_bn_finalize', ptr(stats), rows, ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), ptr(vec[0]), ptr(vec[1]),
-                         ptr(vec[2]), ptr(vec[3]), cout_p, cout, float(B * H * W), BN_MOMENTUM, BN_EPS, ptr(nbt) if training else None, s)
+                # sync: the statistics of the global batch (as in the UNet engine)
+                red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev) if sync else None
+                bnops.fwd_finalize(stats, rows, gamma.detach(), beta.detach(), rm, rv, nbt, vec, cout_p, cout, float(B * H * W), training or sync, s, red, group)
                 out = torch.empty_like(y)
                 call('clamd_bn_apply', ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(out), cout_p, None, 0, B, H, W, cout_p, dcode, s)
                 saved.append(('crb', cur, y, vec, wd, gamma.detach(), training, sync, (cin, cin_p, cout, cout_p, H, W)))
@@ -165,16 +156,12 @@ class _BlockFn(torch.autograd.Function):
                     sums = torch.empty(rows, lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float32, device=dev)
                     call('clamd_bn_bwd_reduce', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
                          B, H, W, cout_p, dcode, None, s)
+                    scratch = None
                     if sync:   # g_z from the sums of the global batch; d gamma, d beta, d conv-bias from this rank's own (as torch)
                         red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev)
-                        tot = torch.empty(lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float64, device=dev)
-                        call('clamd_bn_rows_total', ptr(sums), rows, lib.clamd_bn_bwd_nsums(), cout_p, float(B * H * W), ptr(tot), ptr(red), s)
-                        syncbn.all_reduce(red, ctx.group)
-                        call('clamd_bn_bwd_finalize_total', ptr(tot), ptr(red), ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma),
-                             ptr(dbeta), ptr(dbias), cout_p, cout, s)
-                    else:
-                        call('clamd_bn_bwd_finalize', ptr(sums), rows, ptr(gamma), ptr(vec[2]), ptr(vec[3]), ptr(vec[4]), ptr(dgamma), ptr(dbeta),
-                             ptr(dbias), cout_p, cout, float(B * H * W), s)
+                        scratch = (torch.empty(lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float64, device=dev), red)
+                    bnops.bwd_finalize(sums, rows, lib.clamd_bn_bwd_nsums(), gamma, vec, ptr(dgamma), ptr(dbeta), ptr(dbias), cout_p, cout,
+                                       float(B * H * W), s, scratch, ctx.group)
                     call('clamd_bn_bwd_apply', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
                          B, H, W, cout_p, dcode, s)
                 else:      # running statistics: one pass writes g_z and the rows of the parameter gradients
@@ -184,8 +171,7 @@ class _BlockFn(torch.autograd.Function):
                     er = torch.empty(rows, 3, cout_p, dtype=torch.float32, device=dev)
                     call('clamd_bn_bwd_eval', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(gz), cout_p, ptr(er), rows,
                          B, H, W, cout_p, cout, dcode, s)
-                    call('clamd_bn_bwd_eval_finalize', ptr(er), rows, 3, ptr(vec[0]), ptr(vec[2]), ptr(vec[3]), None, ptr(dgamma), ptr(dbeta),
-                         ptr(dbias), cout_p, cout, s)
+                    bnops.bwd_eval_finalize(er, rows, 3, vec, False, ptr(dgamma), ptr(dbeta), ptr(dbias), cout_p, cout, s)
                 gx = torch.empty(B, H, W, cin_p, dtype=T, device=dev)
                 call('clamd_conv3x3', ptr(gz), cout_p, ptr(wd), None, ptr(gx), cin_p, None, None, None, 0, B, H, W, cout_p, cin_p, 0,
                      1 if 9 * cin_p > B * H * W else 0, dcode, None, s)

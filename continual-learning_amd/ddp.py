@@ -189,7 +189,7 @@ class GradSync:
         last = st is eng.stages[0]
         if (self._lo[1] - self._lo[0]) * 4 >= self.min_bucket or last:
             # the weight gradients of the bucket are produced on the engine's second stream (unet.WGRAD_STREAM)
-            self._wg_stream = getattr(eng, 'wg_stream', None) if getattr(eng, '_wg_used', False) else None
+            self._wg_stream = eng.streams.gradient_stream()
             self._launch(eng.gflat[self._lo[0]:self._lo[1]])
             self._lo = None
 

@@ -90,6 +90,6 @@ for label, wino in (('ours', True), ('ours-direct', False)):
         istd_ = u.vec[3][:u.cout].cpu().numpy()
         gw = dict(ours.named_parameters())[cname + '.weight'].grad.cpu().numpy()
         kern = u.plan.fwd
-        print(f'{cname:18s} {B * u.h * u.w_:6d} {rel(yy_, r64):9.2e} {rel(bo_, b64):9.2e} {rel(istd_, istd64):9.2e} {rel(gz_, z64):9.2e} {rel(gw, g64[cname + ".weight"]):9.2e} | '
+        print(f'{cname:18s} {B * u.h * u.width:6d} {rel(yy_, r64):9.2e} {rel(bo_, b64):9.2e} {rel(istd_, istd64):9.2e} {rel(gz_, z64):9.2e} {rel(gw, g64[cname + ".weight"]):9.2e} | '
               f'{rel(a32[bname]["relu"].cpu().numpy(), r64):9.2e} {rel(a32[bname]["bn"].cpu().numpy(), b64):9.2e} {rel(a32[cname]["gz"].cpu().numpy(), z64):9.2e} '
               f'{rel(g32[cname + ".weight"], g64[cname + ".weight"]):9.2e}   {kern}')

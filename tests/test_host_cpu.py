@@ -137,7 +137,7 @@ def test_synth_is_deterministic_and_blocky(C):
 
 
 def test_engine_geometry_and_pack_table(C):
-    from continual_learning_amd.unet import _Engine
+    from continual_learning_amd.unet import _Engine, _FoldSource
     m = C.UNet(21, 3, 8)
     e = _Engine(m, 2, 64, 64, torch.device('cpu'))
     assert len(e.convs) == 18 and len(e.stages) == 9
@@ -156,7 +156,7 @@ def test_engine_geometry_and_pack_table(C):
     # transformed by the Winograd pack table instead
     wino = lambda u: u.plan.fwd not in ('im2col', 'igemm')    # the unit's forward runs a Winograd form (plan.ALGOS)
     wino_units = [u for u in e.convs if wino(u)]
-    assert len(wino_units) == 15 and all(min(u.h, u.w_) >= 8 for u in wino_units)
+    assert len(wino_units) == 15 and all(min(u.h, u.width) >= 8 for u in wino_units)
     w24 = [u for u in wino_units if u.plan.fwd != 'f22']
     assert len(w24) == 15                                   # every width here (64 ... 8) is a multiple of 4: F(2x4,3x3)
     nw = sum(len(t.jobs) for t in e.wino_early + e.wino_late)          # two launches per form: enc1-enc3 first, the rest behind
@@ -167,7 +167,7 @@ def test_engine_geometry_and_pack_table(C):
     # into both: the block's second conv writes its conv+ReLU output into the concat buffer and only a pooling pass is left
     pooled = [u for u in e.convs if u.pool_fold]
     assert [u.name for u in pooled] == ['enc3.block.4'] and pooled[0].y is e.cat[2] and pooled[0].y_ldc == 64
-    assert sorted(u.name for u in fold if not hasattr(u.fold_a, 'name')) == ['dec3.block.0', 'enc4.block.1']
+    assert sorted(u.name for u in fold if isinstance(u.fold_a, _FoldSource)) == ['dec3.block.0', 'enc4.block.1']
     assert len(fold) == 11 and all(u.fold_a.apply_in_filters and len(u.fold_table.jobs) == 1 and len(u.plain_table.jobs) == 1 for u in fold)
     ks = lambda u, t: t.jobs[0][-1 if wino(u) else -2]       # kscale: the last field of a Winograd pack job, the one before dst_t of a plain one
     assert all(ks(u, u.fold_table) == u.fold_a.vec[0].data_ptr() and ks(u, u.plain_table) == 0 for u in fold)

@@ -62,7 +62,7 @@ for unit, (sec, flops, n, ex) in acc.items():
         continue
     tf = flops / t / 1e12
     pre = getattr(u.plan, unit.split()[-1], None) in ('f24_pre', 'f44_pre')
-    print(f'{unit:22s} {t * 1e6:8.1f} {tf:9.1f} {tf * ex / PEAK:8.3f}   {u.cin}->{u.cout} @{u.h}x{u.w_}{"  pre-transformed" if pre else ""}')
+    print(f'{unit:22s} {t * 1e6:8.1f} {tf:9.1f} {tf * ex / PEAK:8.3f}   {u.cin}->{u.cout} @{u.h}x{u.width}{"  pre-transformed" if pre else ""}')
     d = unit.split()[-1]
     tt = tot.setdefault(d, [0.0, 0.0])
     tt[0] += t; tt[1] += flops

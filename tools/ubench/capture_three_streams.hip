@@ -1,5 +1,5 @@
-// Reproducer (ROCm 7.2, gfx950): stream capture of the engine's three-stream backward pattern (unet._Engine._conv_bwd with
-// WGRAD_XFORM_STREAM): origin stream A forks B (weight gradients) and C (gradient-side transforms); C additionally waits on an event that
+// Reproducer (ROCm 7.2, gfx950): stream capture of the engine's three-stream backward pattern (engine._Engine._conv_bwd with
+// unet.WGRAD_XFORM_STREAM): origin stream A forks B (weight gradients) and C (gradient-side transforms); C additionally waits on an event that
 // B recorded earlier in the SAME capture (the GEMM that last read the operand buffer), B waits on C's event, A joins B at the end.
 //   hipcc --offload-arch=gfx950 -O2 -o /tmp/cap3 tools/ubench/capture_three_streams.hip && /tmp/cap3 [pattern]
 // pattern 0: fork/join A->B, A->C, C->B, B->A                         (plain diamond)
