@@ -8,9 +8,10 @@ from .unet import UNet, cpad, stage_table  # noqa: F401
 from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .consolidate import Consolidation  # noqa: F401
+from .pseudo import PseudoLabeler, thresholds_from_histogram  # noqa: F401
 from .metrics import argmax_confusion, eval_metrics, metrics_from_confusion  # noqa: F401
 from .trainer import Trainer, default_config  # noqa: F401
-from . import consolidate, data, ddp, syncbn  # noqa: F401
+from . import consolidate, data, ddp, pseudo, syncbn  # noqa: F401
 
-__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'FusedAdam', 'Consolidation', 'Trainer', 'default_config',
+__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'FusedAdam', 'Consolidation', 'PseudoLabeler', 'thresholds_from_histogram', 'Trainer', 'default_config',
            'argmax_confusion', 'eval_metrics', 'metrics_from_confusion', 'data', 'ddp', 'synth']

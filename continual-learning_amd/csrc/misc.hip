@@ -5,6 +5,7 @@
 #include <string.h>
 #include <stdio.h>
 #include "common.hip.h"
+#include "ce_common.hip.h"
 #include "clamd_internal.h"
 #include "../../include/clamd_debug.h"
 
@@ -276,7 +277,6 @@ __global__ void count_valid_kernel(const long long* __restrict__ labels, long lo
 
 // The same count as one partial pair per workgroup (plain stores: no memset in front, no serialised atomics behind); the consumers add the
 // CE_COUNT_BLOCKS pairs themselves (integers: any order gives the same sum).
-constexpr int CE_COUNT_BLOCKS = 256;
 __global__ void __launch_bounds__(256) count_valid_rows_kernel(const long long* __restrict__ labels, long long n, long long ignore_index,
                                                                int K, unsigned int* rows /* [CE_COUNT_BLOCKS][2] */) {
     unsigned int c = 0, bad = 0;
@@ -295,15 +295,6 @@ __global__ void __launch_bounds__(256) count_valid_rows_kernel(const long long* 
         rows[2 * blockIdx.x + 0] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
         rows[2 * blockIdx.x + 1] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
     }
-}
-// total of column `col` of those rows, by every thread of a 256-thread workgroup (through `tmp`, 4 words of LDS)
-__device__ inline unsigned int ce_count_total(const unsigned int* __restrict__ rows, int col, unsigned int* tmp) {
-    static_assert(CE_COUNT_BLOCKS == 256, "one row per thread");
-    unsigned int v = rows[2 * threadIdx.x + col];
-    v += __shfl_xor(v, 32); v += __shfl_xor(v, 16); v += __shfl_xor(v, 8); v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
-    if ((threadIdx.x & 63) == 0) tmp[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return tmp[0] + tmp[1] + tmp[2] + tmp[3];
 }
 
 template <int KMAX>
@@ -393,72 +384,6 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
 // NT != void: d logits is ALSO written as an NHWC tensor [pixel][ldc] of compute dtype NT (channels K .. 31 zero) -- the layout the 1x1
 // head's data gradient reads, so the backward pass needs no NCHW -> NHWC conversion (88 + 67 MB at config 2 in bf16): a thread's four
 // pixels are consecutive there too (4 x 64 bytes in bf16).
-struct ce_no_nhwc {};
-#ifdef CE_NO_EXCHANGE      // A/B builds of the NHWC copy stored straight from the registers
-#define CE_EXCHANGE false
-#else
-#define CE_EXCHANGE true
-#endif
-// The second copy of d logits of a lane's four consecutive pixels (v[k] = the gradient of class k), NHWC [pixel][dl_ldc] in dtype NT, channels
-// K .. 31 zero: ce4_kernel's store block as a function, for ce4u_kernel (ce4_kernel keeps its inline copy: calling this there changed
-// the register allocation of its NHWC instantiations).  XCH (bf16): through LDS, with two workgroup barriers -- every lane of the workgroup calls.
-template <int KMAX, typename NT, bool XCH>
-__device__ inline void ce_store_nhwc4(const float4 (&v)[KMAX], int K, NT* dl_nhwc, int dl_ldc, long long pix, long long base, long long nq,
-                                      uint4 (*xbuf)[XCH ? 1024 : 1]) {
-    if constexpr (XCH) {
-        // A lane owns 4 pixels x 64 bytes; stored straight from its registers every instruction would write 16 bytes every 256 (64 partial
-        // lines).  Instead the wave's 1024 16-byte pieces go through LDS (piece P = 16 lane + 4 q + cg at slot P ^ (lane & 7): the eight
-        // lanes a ds_write_b128 is served in hit eight different bank groups; the reader undoes it with (P >> 4) & 7) and leave in pixel
-        // order: one store instruction = 16 pixels x 64 bytes = 1 KB of contiguous output.
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int cg = 0; cg < 4; ++cg) {
-                unsigned w[4];
-#pragma unroll
-                for (int j2 = 0; j2 < 4; ++j2) {
-                    float e[2];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int k = cg * 8 + 2 * j2 + u;
-                        float t = 0.f;
-                        if (k < KMAX) { if (k < K) t = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
-                        e[u] = t;
-                    }
-                    w[j2] = (unsigned)f2bf(e[0]) | ((unsigned)f2bf(e[1]) << 16);
-                }
-                const int P = 16 * lane + 4 * q + cg;
-                xbuf[wv][P ^ (lane & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        __syncthreads();
-        const long long wave_pix = 4 * (base + 64 * wv);          // first pixel of this wave's 256
-        const long long npix = 4 * nq;
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int P = 64 * it + lane;
-            const long long px = wave_pix + (P >> 2);
-            if (px < npix) *reinterpret_cast<uint4*>((uint16_t*)dl_nhwc + px * dl_ldc + (P & 3) * 8) = xbuf[wv][P ^ ((P >> 4) & 7)];
-        }
-        __syncthreads();
-    } else if constexpr (!__is_same(NT, ce_no_nhwc)) {
-        NT* o = dl_nhwc + pix * dl_ldc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int cg = 0; cg < 4; ++cg) {          // 32 physical channels: four groups of eight
-                float t[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = cg * 8 + j;
-                    float e = 0.f;
-                    if (k < KMAX) { if (k < K) e = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
-                    t[j] = e;
-                }
-                Vec8<NT>::store(o + (long long)q * dl_ldc + cg * 8, t);
-            }
-    }
-}
 
 template <int KMAX, typename NT = ce_no_nhwc>
 __global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
@@ -596,12 +521,6 @@ __global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logi
 // (fO / fN carry the shift), so  LSE(old) - LSE(all) and softmax_old stay exact however far apart the groups are.
 // With c_old == 1 and KOLD == 0 every operation on the path to d logits and to the loss is the one ce4_kernel makes (bit-equal results).
 // NPX = 1: the same arithmetic, one pixel per thread with 4-byte accesses, for H * W % 4 != 0 or unaligned tensors.
-template <int NPX> __device__ inline float4 ce_ldpx(const float* p) {
-    if constexpr (NPX == 4) return *reinterpret_cast<const float4*>(p);
-    else return make_float4(*p, 0.f, 0.f, 0.f);
-}
-__device__ inline float& ce_at(float4& a, int c) { return c == 0 ? a.x : c == 1 ? a.y : c == 2 ? a.z : a.w; }
-__device__ inline float ce_at(const float4& a, int c) { return c == 0 ? a.x : c == 1 ? a.y : c == 2 ? a.z : a.w; }
 #define CE_PX _Pragma("unroll") for (int c = 0; c < NPX; ++c)
 
 template <int KMAX, int KOLD, int NPX, typename NT>
@@ -1195,6 +1114,13 @@ static void ce_unbiased_launch(int g, hipStream_t s, const float* logits, const 
         else { if (ko == 0) CEU(32, 0); else if (ko == 16) CEU(32, 16); else CEU(32, 32); }
     }
 #undef CEU
+}
+
+// ce_finalize_kernel for the loss kernels of other translation units (pseudo.hip): the counted form, no distillation term
+void clamd_ce_finalize_counted(const float* partial, int nblocks, void* workspace, long long npix, float* loss3, hipStream_t s) {
+    unsigned int* nvalid = (unsigned int*)((float*)workspace + 2 * 2048);
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, nblocks, nvalid, (float)(1.0 / (double)npix), 0.f, loss3,
+                       (const unsigned int*)(nvalid + 4));
 }
 
 extern "C" {

@@ -10,6 +10,9 @@ pinned only by tests against this repo's own CPU restatement.
 
 ``UnbiasedDistillationCrossEntropy`` is the class-incremental step's criterion (build-defined and parity-unpinned as well): the unbiased
 cross-entropy and unbiased distillation of Cermelli et al. (CVPR 2020) as include/clamd.h states them, on ``clamd_ce_unbiased_fwd_bwd``.
+
+``CrossEntropyLoss()(logits, labels, image_weight)`` is the pseudo-label step's loss (build-defined, pseudo.py): every pixel's term times its
+image's weight, on ``clamd_ce_fwd_bwd_weighted``; without the weight nothing changes.
 """
 import os
 
@@ -100,7 +103,11 @@ class CrossEntropyLoss(nn.Module):
         self.ignore_index = ignore_index
         self.bad_labels = None        # after a forward: device int32[1], labels that are neither ignore_index nor a class
 
-    def forward(self, logits, labels):
+    def forward(self, logits, labels, image_weight=None):
+        """image_weight (fp32 [B] on the device, e.g. PseudoLabeler's nu): every pixel's term and gradient times its image's weight, the mean
+        still over the unweighted count of valid pixels (clamd_ce_fwd_bwd_weighted; build-defined).  None: the plain loss."""
+        if image_weight is not None:
+            return _WCEFn.apply(logits, labels, image_weight.detach(), self.ignore_index, self)
         return _CEFn.apply(logits, labels, None, 0, 1.0, 0.0, self.ignore_index, self)
 
 
@@ -164,6 +171,52 @@ class _UCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return _CEFn.backward(ctx, g)[:7]
+
+
+class _WCEFn(torch.autograd.Function):
+    """clamd_ce_count + clamd_ce_fwd_bwd_weighted; the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, image_weight, ignore_index, holder):
+        if not logits.is_cuda or not labels.is_cuda or not image_weight.is_cuda:
+            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
+        lib = _lib.load()
+        logits_in = logits
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            raise TypeError('labels must be int64 (datasets/voc.py:72)')
+        B, K, H, W = logits.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
+        if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
+            raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
+        image_weight = image_weight.contiguous()
+        dl = torch.empty_like(logits)
+        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+        wsb = lib.clamd_ce_workspace_bytes()
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
+        from . import unet as U
+        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
+        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
+        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
+        # algorithmic bytes: as clamd_ce_fwd_bwd_counted (the B weights do not count)
+        U._hbm('loss', B * H * W * (2 * K * 4 + 8 + (ldc * eng.esize if eng is not None else 0)),
+               'clamd_ce_fwd_bwd_weighted', ptr(logits), ptr(labels), ptr(image_weight), ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb,
+               B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
+        ctx.sink = None
+        if eng is not None:
+            ctx.sink = eng
+            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)      # a strong reference, as in _CEFn.forward
+        ctx.save_for_backward(dl)
+        ctx.parts = out3
+        off = lib.clamd_ce_bad_label_count_offset() // 4
+        holder.bad_labels = ws[off:off + 1].view(torch.int32)
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return _CEFn.backward(ctx, g)[:5]
 
 
 class UnbiasedDistillationCrossEntropy(nn.Module):

@@ -14,7 +14,8 @@ DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-d
 every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0`` estimates the finished task's per-parameter importance
 (``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py).
 Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
-of the global batch, syncbn.py).
+of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
+confident predictions (build-defined, pseudo.py).
 """
 import os
 import warnings
@@ -28,6 +29,7 @@ from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillati
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam
 from .consolidate import Consolidation
+from .pseudo import PseudoLabeler
 from . import syncbn
 from .unet import UNet
 
@@ -47,6 +49,7 @@ class Trainer:
         self.device = torch.device(device)
         self.start_epoch = 0
         self.old_model = None
+        self.pseudo = None                # pseudo.PseudoLabeler once begin_task2(pseudo_label=True) ran
         self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
         self.ewc_lambda = 0.0
         self.build_model()
@@ -96,7 +99,8 @@ class Trainer:
         self.optim.set_consolidation(self.consolidation.anchor, self.consolidation.importance, self.ewc_lambda)
 
     def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
-                    importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background'):
+                    importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background',
+                    pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
         still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
@@ -106,7 +110,20 @@ class Trainer:
         Class-incremental step (build-defined): new_classes > 0 grows the trained model's head by that many outputs AFTER the importance
         estimate and the snapshot (the old model keeps its width; UNet.expand_classes(new_classes, head_init)), carrying Adam's moments and
         the anchors over; unbiased=True distils with UnbiasedDistillationCrossEntropy(c_old, distill_lambda) (no temperature) instead of
-        DistillationCrossEntropy.  A later call (task 3) snapshots the grown model: c_old is then the grown width."""
+        DistillationCrossEntropy.  A later call (task 3) snapshots the grown model: c_old is then the grown width.
+        Pseudo-labels (build-defined, pseudo.py): pseudo_label=True calibrates a PseudoLabeler(c_old, pseudo_bins, pseudo_adaptive,
+        pseudo_min_factor) with the snapshot on pseudo_loader (default: the training loader -- it should hold the NEW task's data, whose
+        old-class pixels are labelled 0); every step then runs the old model's forward, also with distill_lambda == 0, relabels the
+        background pixels it is confident about, ignores the others, and (pseudo_adaptive) weights each image's loss by the accepted share.
+        Not with unbiased=True (that criterion treats every label < c_old alike: pseudo-labels would change nothing), and pseudo_adaptive
+        not with distill_lambda > 0 (DistillationCrossEntropy's kernel has no per-image weight).  The canonical setting is
+        begin_task2(c_old, distill_lambda=0, pseudo_label=True, pseudo_adaptive=True)."""
+        if pseudo_label and unbiased:
+            raise ValueError('pseudo_label=True with unbiased=True: the unbiased cross-entropy treats every label below c_old alike, '
+                             'so pseudo-labels would change nothing')
+        if pseudo_label and pseudo_adaptive and distill_lambda > 0:
+            raise ValueError('pseudo_adaptive=True with distill_lambda > 0: DistillationCrossEntropy has no per-image weight '
+                             '(use distill_lambda=0, or pseudo_adaptive=False)')
         if ewc_lambda > 0:
             cons = self.estimate_importance(self.train_data_loader if importance_loader is None else importance_loader)
             cons.gamma = float(ewc_gamma)
@@ -125,6 +142,12 @@ class Trainer:
             self.distill = UnbiasedDistillationCrossEntropy(c_old, distill_lambda)
         else:
             self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
+        self.pseudo = None
+        if pseudo_label:
+            self.pseudo = PseudoLabeler(c_old, bins=pseudo_bins, adaptive=pseudo_adaptive, min_factor=pseudo_min_factor,
+                                        ignore_index=self.c_loss.ignore_index)
+            group = m.grad_sync.group if getattr(m, 'grad_sync', None) is not None else None
+            self.pseudo.calibrate(self.old_model, self.train_data_loader if pseudo_loader is None else pseudo_loader, self.device, group=group)
         if ewc_lambda > 0:
             self.optim.set_l2_anchor(None, 0.0)        # an earlier task's L2 anchor is another snapshot than the new consolidation anchor
             self._apply_consolidation()
@@ -239,12 +262,17 @@ class Trainer:
         """trainer.py:172-176."""
         outputs = self.model(inputs)
         self.reset_grad()
-        if self.old_model is not None and getattr(self, 'distill', None) is not None:
+        distill = getattr(self, 'distill', None) if self.old_model is not None else None
+        if distill is not None or self.pseudo is not None:
             with torch.no_grad():
                 old = self.old_model(inputs)
-            loss = self.distill(outputs, labels, old)
+        nu = None
+        if self.pseudo is not None:       # the caller's labels stay what they were (train_epoch's confusion matrix reads them)
+            labels, nu = self.pseudo(old, labels)
+        if distill is not None:
+            loss = distill(outputs, labels, old)
         else:
-            loss = self.c_loss(outputs, labels)
+            loss = self.c_loss(outputs, labels, nu) if nu is not None else self.c_loss(outputs, labels)
         loss.backward()
         self.optim.step()
         return outputs, loss

@@ -394,6 +394,44 @@ int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float
 int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
                               float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
                               int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream);
+/* ---- pseudo-labelling of the old classes (pseudo.hip) --------------------------------------------------------
+ * Build-defined, parity unpinned (the reference has no continual-learning code): the classification half of PLOP (Douillard et al.,
+ * CVPR 2021, section 3.2).  In a task-2 batch every pixel of an old class is labelled 0; the frozen old model labels the background
+ * pixels it is confident about, the others are ignored, and each image's loss is scaled by the accepted share of its background.
+ * Notation: zo = old_logits[:, 0:c_old] (fp32 NCHW; K_old_total >= c_old), NB = number of bins, ign = ignore_index.  Per pixel:
+ *   c* = the LOWEST index of the maximum of zo over [0, c_old) (torch's arg-max tie rule);  q = softmax(zo);
+ *   u = -(sum_k q_k ln q_k) / ln(c_old), in fp32 with the usual max-subtraction;  c_old == 1 gives u = 0, c* = 0;
+ *   bin(u) = min(NB-1, floor(u * NB));  CANDIDATE pixels are exactly those with label == 0.
+ * Calibration histogram: hist[c*][bin(u)] += 1 over the candidate pixels; int64 [c_old, NB], ADDED into what is there (several batches
+ *   accumulate; the caller zeroes it once).
+ * Thresholds (host side, integer arithmetic on the histogram): n_c = sum_j hist[c][j]; n_c == 0 gives tau_c = 0; otherwise j* is the
+ *   smallest j with sum_{i<=j} hist[c][i] >= ceil(n_c / 2) and tau_c = (j* + 1) / NB: the per-class median entropy, rounded up to a bin edge.
+ * Relabelling: a candidate is accepted iff u < tau_{c*} (strict); accepted: labels_out = c* (c* == 0 keeps it background); rejected:
+ *   labels_out = ign; every other label (new classes, ign, out-of-range values, which the loss counts as bad labels) passes through
+ *   unchanged.  labels_in is not modified.
+ * Adaptive factor: per image b, n_bg[b] candidates and n_acc[b] accepted ones; nu_b = n_bg ? max(min_factor, float(n_acc) / float(n_bg)) : 1.
+ * Image-weighted cross-entropy: N = number of pixels whose label is not ign and lies in [0, K) (unweighted, what clamd_ce_count counts);
+ *   loss = (1 / max(N,1)) * sum_b nu_b * sum_{valid p in b} -log softmax(z_p)[y_p];
+ *   d logits = nu_b * (softmax - onehot) / max(N,1) * grad_scale on valid pixels, 0 elsewhere;  loss3 = {total, ce, 0}.
+ *   With every nu_b == 1.0f the results equal clamd_ce_fwd_bwd_counted's bit for bit (the same partial-row reduction order; the weight is
+ *   multiplied in as one fp32 factor).
+ * All three: enqueue only, no allocation, no host synchronisation, device taken from the stream; bit-reproducible (integer atomics only,
+ * no float atomics).  c_old in [1, 32].  Four pixels per thread with 16-byte logit and 32-byte label accesses when H * W % 4 == 0 and the
+ * logits are 16-byte / the labels 32-byte aligned; any other size or alignment takes a one-pixel variant of the same arithmetic inside the
+ * same entry point.
+ * clamd_pseudo_entropy_hist: c_old * nbins <= 8192.
+ * clamd_pseudo_label: counts = unsigned int [B][2] = {n_bg, n_acc}, cleared by the entry point itself; image_weight = float [B] (nu_b), or
+ *   NULL when the factor is not wanted; thresholds = device float [c_old]; B <= 4096.
+ * clamd_ce_fwd_bwd_weighted: clamd_ce_fwd_bwd_counted's arguments plus image_weight (device, B floats, required); the workspace holds
+ *   clamd_ce_count's partial rows (same K, same stream, called before), dl_nhwc / dl_ldc / dl_dtype and the bad-label counter as there. */
+int clamd_pseudo_entropy_hist(const float* old_logits, int K_old_total, int c_old, const long long* labels, long long* hist, int nbins,
+                              int B, int H, int W, void* stream);
+int clamd_pseudo_label(const float* old_logits, int K_old_total, int c_old, const long long* labels_in, const float* thresholds,
+                       long long* labels_out, unsigned int* counts, float* image_weight, double min_factor, int B, int H, int W,
+                       long long ignore_index, void* stream);
+int clamd_ce_fwd_bwd_weighted(const float* logits, const long long* labels, const float* image_weight, float* dlogits, void* dl_nhwc,
+                              int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W,
+                              long long ignore_index, double grad_scale, void* stream);
 /* torch.optim.Adam.step over all parameters in one launch (trainer.py:108-110,176); hyper/step/derived live on the
  * device so a captured graph can be replayed with a new learning rate.  l2_accum_dev (optional, with the L2-to-old-weights
  * term): 1 + nchunks floats, [0] = sum ||theta - theta_old||^2 of this step, [1..] = per-workgroup partials added in a fixed
