@@ -52,10 +52,6 @@ inline int clamd_usable_cus(const clamd_tuning& t) {
 long long clamd_winograd_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn);
 long long clamd_bn_bwd_reduce_rows(int B, int H, int W, int Cp, bool pooled, const clamd_tuning& tn);
 
-// the loss's finalize launch (misc.hip) behind a loss kernel of another translation unit: `partial` = nblocks {ce, 0} pairs at the start of
-// the clamd_ce_workspace_bytes() workspace, whose count rows clamd_ce_count wrote -> loss3 and the {valid, bad} totals
-void clamd_ce_finalize_counted(const float* partial, int nblocks, void* workspace, long long npix, float* loss3, hipStream_t stream);
-
 // the three filter-pack launches with an optional border-class bias table appended (grid = total_blocks + Cout_p; bnfold.hip)
 namespace clamd { struct FoldBias; }
 int clamd_launch_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, const clamd::FoldBias* fold, hipStream_t stream);

@@ -752,7 +752,7 @@ __global__ void __launch_bounds__(256) nchw_im2col3x4_kernel(const float* __rest
     const long long hw = (long long)H * W, nq = (long long)B * hw / 4;
     const int wq = W / 4;
     // bf16, pitch 32: a lane owns 4 pixels x 64 bytes; its 16 pieces go through LDS (piece P = 16 lane + 4 j + cg at slot P ^ (lane & 7), undone
-    // by the reader with (P >> 4) & 7 -- the ce4_kernel exchange, misc.hip) so that one store instruction writes 1 KB of contiguous output
+    // by the reader with (P >> 4) & 7 -- the ce4_kernel exchange, loss.hip) so that one store instruction writes 1 KB of contiguous output
     constexpr bool XCH = __is_same(T, bf16_t);
     __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
     for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {

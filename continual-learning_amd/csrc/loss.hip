@@ -1,0 +1,724 @@
+// The per-pixel loss family: fused cross-entropy forward + backward and its build-defined continual-learning
+// variants (A12: the distillation term, the unbiased class-incremental step, the per-image weight of the pseudo-label step).
+//   clamd_ce_fwd_bwd            plain loss, any size; or + temperature distillation (ce_kernel, one pixel per thread)
+//   clamd_ce_count              the {valid, bad} pixel counts as partial rows, for the three entry points below
+//   clamd_ce_fwd_bwd_counted    the training-step form: four pixels per thread, d logits optionally a second time in NHWC
+//   clamd_ce_fwd_bwd_weighted   the same with the image's factor nu_b on every pixel's term
+//   clamd_ce_unbiased_fwd_bwd   unbiased cross-entropy + unbiased distillation
+// Every entry point: [count ->] one loss kernel (a {ce, kd} partial pair per workgroup) -> ce_finalize_kernel.
+#include <math.h>
+#include <stdio.h>
+#include <type_traits>
+#include "common.hip.h"
+#include "ce_common.hip.h"
+#include "clamd_internal.h"
+
+namespace clamd {
+
+// logits NCHW fp32 [B,K,H,W]; labels int64 [B,H,W].  nn.CrossEntropyLoss() (trainer.py:113): mean over pixels
+// whose label != ignore_index.  Optional distillation (build-defined, parity unpinned):
+//   + lam * mean_px KL( softmax(z_old[:, :c_old]/T) || softmax(z[:, :c_old]/T) )
+// count[0] = pixels that take part in the mean (label != ignore_index and inside [0, K)); count[1] = pixels whose label is
+// neither ignore_index nor a class -- torch's CrossEntropyLoss asserts on those; here they are left out of the loss and
+// REPORTED (the host side exposes the counter, loss.py), so a label bug in a class split cannot hide.
+
+// The caller's workspace, in 32-bit words: the loss kernel's partial pairs, the two totals (two spare words), the count rows.
+constexpr int CE_MAX_BLOCKS = 2048;                            // grid cap of the loss kernels: one partial {ce, kd} pair each
+constexpr int CE_COUNT_BLOCKS = 256;                           // workgroups of count_valid_rows_kernel: one partial {valid, bad} pair each
+constexpr int CE_WS_TOTALS = 2 * CE_MAX_BLOCKS;                // {valid, bad} totals, written by ce_finalize_kernel
+constexpr int CE_WS_ROWS = CE_WS_TOTALS + 4;
+constexpr int CE_WS_WORDS = CE_WS_ROWS + 2 * CE_COUNT_BLOCKS;
+
+// The count as one partial pair per workgroup (plain stores: no memset in front, no serialised atomics behind); the consumers add the
+// CE_COUNT_BLOCKS pairs themselves (integers: any order gives the same sum).
+__global__ void __launch_bounds__(256) count_valid_rows_kernel(const long long* __restrict__ labels, long long n, long long ignore_index,
+                                                               int K, unsigned int* rows /* [CE_COUNT_BLOCKS][2] */) {
+    unsigned int c = 0, bad = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long l = labels[i];
+        const bool in = l >= 0 && l < K;
+        c += (l != ignore_index && in) ? 1u : 0u;
+        bad += (l != ignore_index && !in) ? 1u : 0u;
+    }
+    __shared__ unsigned int wsum[2][4];
+    c = (unsigned int)wave_sum((float)c);   // <= 64 * iterations: exact in fp32 for the sizes used here
+    bad = (unsigned int)wave_sum((float)bad);
+    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = c; wsum[1][threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        rows[2 * blockIdx.x + 0] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
+        rows[2 * blockIdx.x + 1] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+    }
+}
+
+// total of column `col` of those rows, by every thread of a 256-thread workgroup (through `tmp`, 4 words of LDS)
+__device__ inline unsigned int ce_count_total(const unsigned int* __restrict__ rows, int col, unsigned int* tmp) {
+    static_assert(CE_COUNT_BLOCKS == 256, "one row per thread");
+    unsigned int v = rows[2 * threadIdx.x + col];
+    v += __shfl_xor(v, 32); v += __shfl_xor(v, 16); v += __shfl_xor(v, 8); v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
+    if ((threadIdx.x & 63) == 0) tmp[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return tmp[0] + tmp[1] + tmp[2] + tmp[3];
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                 const float* __restrict__ old_logits, int K_old_total, int c_old,
+                                                 float inv_temp, float lam, float* __restrict__ dlogits,
+                                                 float* __restrict__ partial, const unsigned int* __restrict__ count_rows,
+                                                 int B, int K, long long HW, long long ignore_index, float grad_scale) {
+    __shared__ float red[2][4];
+    __shared__ unsigned int cnt_tmp[4];
+    const long long npix = (long long)B * HW;
+    const float inv_valid = 1.f / (float)max(ce_count_total(count_rows, 0, cnt_tmp), 1u);
+    const float inv_npix = 1.f / (float)npix;
+    float ce_sum = 0.f, kd_sum = 0.f;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / HW, p = i - b * HW;
+        const float* z = logits + b * K * HW + p;
+        float v[KMAX];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            v[k] = k < K ? z[k * HW] : -INFINITY;
+            mx = fmaxf(mx, v[k]);
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) se += k < K ? expf(v[k] - mx) : 0.f;
+        const float lse = mx + logf(se);
+        const long long lab = labels[i];
+        const bool valid = lab != ignore_index && lab >= 0 && lab < K;
+        float picked = 0.f;
+        float g[KMAX];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            const float sm = k < K ? expf(v[k] - lse) : 0.f;
+            const bool hit = valid && k == (int)lab;
+            picked = hit ? v[k] : picked;
+            g[k] = valid ? (sm - (hit ? 1.f : 0.f)) * inv_valid : 0.f;
+        }
+        if (valid) ce_sum += lse - picked;
+        if (old_logits) {
+            const float* zo = old_logits + b * K_old_total * HW + p;
+            float o[KMAX];
+            float mo = -INFINITY, mn = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                o[k] = k < c_old ? zo[k * HW] * inv_temp : -INFINITY;
+                mo = fmaxf(mo, o[k]);
+                mn = fmaxf(mn, k < c_old ? v[k] * inv_temp : -INFINITY);
+            }
+            float so = 0.f, sn = 0.f;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                so += k < c_old ? expf(o[k] - mo) : 0.f;
+                sn += k < c_old ? expf(v[k] * inv_temp - mn) : 0.f;
+            }
+            const float lo = mo + logf(so), ln = mn + logf(sn);
+            float kl = 0.f;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < c_old) {
+                    const float lp = o[k] - lo, lq = v[k] * inv_temp - ln;
+                    const float pk = expf(lp);
+                    kl += pk * (lp - lq);
+                    g[k] += lam * inv_npix * inv_temp * (expf(lq) - pk);
+                }
+            kd_sum += kl;
+        }
+        float* d = dlogits + b * K * HW + p;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) d[k * HW] = g[k] * grad_scale;
+    }
+    ce_sum = wave_sum(ce_sum);
+    kd_sum = wave_sum(kd_sum);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = ce_sum; red[1][wave] = kd_sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+struct ce_no_nhwc {};
+#ifdef CE_NO_EXCHANGE      // A/B builds of the NHWC copy stored straight from the registers
+#define CE_EXCHANGE false
+#else
+#define CE_EXCHANGE true
+#endif
+// The second copy of d logits of a lane's four consecutive pixels (v[k] = the gradient of class k), NHWC [pixel][dl_ldc] in dtype NT, channels
+// K .. 31 zero.  XCH (bf16): through LDS, with two workgroup barriers -- every lane of the workgroup calls.
+template <int KMAX, typename NT, bool XCH>
+__device__ inline void ce_store_nhwc4(const float4 (&v)[KMAX], int K, NT* dl_nhwc, int dl_ldc, long long pix, long long base, long long nq,
+                                      uint4 (*xbuf)[XCH ? 1024 : 1]) {
+    if constexpr (XCH) {
+        // A lane owns 4 pixels x 64 bytes; stored straight from its registers every instruction would write 16 bytes every 256 (64 partial
+        // lines).  Instead the wave's 1024 16-byte pieces go through LDS (piece P = 16 lane + 4 q + cg at slot P ^ (lane & 7): the eight
+        // lanes a ds_write_b128 is served in hit eight different bank groups; the reader undoes it with (P >> 4) & 7) and leave in pixel
+        // order: one store instruction = 16 pixels x 64 bytes = 1 KB of contiguous output.
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int cg = 0; cg < 4; ++cg) {
+                unsigned w[4];
+#pragma unroll
+                for (int j2 = 0; j2 < 4; ++j2) {
+                    float e[2];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int k = cg * 8 + 2 * j2 + u;
+                        float t = 0.f;
+                        if (k < KMAX) { if (k < K) t = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
+                        e[u] = t;
+                    }
+                    w[j2] = (unsigned)f2bf(e[0]) | ((unsigned)f2bf(e[1]) << 16);
+                }
+                const int P = 16 * lane + 4 * q + cg;
+                xbuf[wv][P ^ (lane & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        __syncthreads();
+        const long long wave_pix = 4 * (base + 64 * wv);          // first pixel of this wave's 256
+        const long long npix = 4 * nq;
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            const int P = 64 * it + lane;
+            const long long px = wave_pix + (P >> 2);
+            if (px < npix) *reinterpret_cast<uint4*>((uint16_t*)dl_nhwc + px * dl_ldc + (P & 3) * 8) = xbuf[wv][P ^ ((P >> 4) & 7)];
+        }
+        __syncthreads();
+    } else if constexpr (!__is_same(NT, ce_no_nhwc)) {
+        NT* o = dl_nhwc + pix * dl_ldc;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int cg = 0; cg < 4; ++cg) {          // 32 physical channels: four groups of eight
+                float t[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = cg * 8 + j;
+                    float e = 0.f;
+                    if (k < KMAX) { if (k < K) e = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
+                    t[j] = e;
+                }
+                Vec8<NT>::store(o + (long long)q * dl_ldc + cg * 8, t);
+            }
+    }
+}
+// ... and of a lane's one pixel (NPX = 1: v[k].x), straight from the registers
+template <int KMAX, typename NT>
+__device__ inline void ce_store_nhwc1(const float4 (&v)[KMAX], int K, NT* dl_nhwc, int dl_ldc, long long pix) {
+    if constexpr (!__is_same(NT, ce_no_nhwc)) {
+#pragma unroll
+        for (int cg = 0; cg < 4; ++cg) {
+            float t[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t[j] = (cg * 8 + j < KMAX && cg * 8 + j < K) ? v[cg * 8 + j < KMAX ? cg * 8 + j : 0].x : 0.f;
+            Vec8<NT>::store(dl_nhwc + pix * dl_ldc + cg * 8, t);
+        }
+    }
+}
+
+// The plain loss of the training step and, WEIGHTED, the pseudo-label step's: NPX = 4 consecutive pixels per thread (H * W % 4 == 0, so they
+// share an image) -- 16-byte loads and stores, K * 16 bytes in flight per lane instead of K * 4 -- and ONE exponential per logit (e = exp(z - max)
+// is kept in the logit's register; softmax = e / sum).  NPX = 1: the same arithmetic, one pixel per thread, for any size or alignment.
+// NT != ce_no_nhwc: d logits is ALSO written as an NHWC tensor [pixel][ldc] of compute dtype NT (channels K .. 31 zero) -- the layout the 1x1
+// head's data gradient reads, so the backward pass needs no NCHW -> NHWC conversion (88 + 67 MB at config 2 in bf16): a thread's four
+// pixels are consecutive there too (4 x 64 bytes in bf16).
+// WEIGHTED: the image's nu_b multiplied in as ONE fp32 factor, into the pixel's loss term and into gs = grad_scale / max(N, 1); every other
+// operation is the unweighted one in the same order, so nu_b == 1.0f changes no bit.  Unweighted, the kernel takes no weight at all.
+struct ce_no_weight {};
+template <int KMAX, int NPX, typename NT, bool WEIGHTED>
+__global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                  std::conditional_t<WEIGHTED, const float* __restrict__, ce_no_weight> image_weight,
+                                                  float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
+                                                  long long ignore_index, float grad_scale, NT* dl_nhwc, int dl_ldc,
+                                                  const unsigned int* __restrict__ count_rows) {
+    __shared__ float red[4];
+    __shared__ unsigned int cnt_tmp[4];
+    const long long nq = (long long)B * HW / NPX;
+    const unsigned int nv = ce_count_total(count_rows, 0, cnt_tmp);
+    const float gs = grad_scale / (float)max(nv, 1u);
+    float ce_sum = 0.f;
+    constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;      // NHWC copy through LDS: whole KBs per store instruction
+    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange below has barriers)
+        if (!XCH && !live) continue;
+        const long long pix = NPX * (live ? i : nq - 1), b = pix / HW, p = pix - b * HW;
+        float nu = 1.f, gw = gs;
+        if constexpr (WEIGHTED) { nu = image_weight[b]; gw = gs * nu; }
+        const float* z = logits + b * K * HW + p;
+        float4 v[KMAX];
+        float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                v[k] = ce_ldpx<NPX>(z + k * HW);
+                CE_PX ce_at(mx, c) = fmaxf(ce_at(mx, c), ce_at(v[k], c));
+            }
+        long long lab[4];
+        ce_ld_labels<NPX>(labels, pix, lab);
+        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), picked = se;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                CE_PX ce_at(picked, c) = lab[c] == k ? ce_at(v[k], c) : ce_at(picked, c);
+                CE_PX ce_at(v[k], c) = expf(ce_at(v[k], c) - ce_at(mx, c));
+                CE_PX ce_at(se, c) += ce_at(v[k], c);
+            }
+        bool ok[NPX];
+        CE_PX ok[c] = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K;
+        if (live) CE_PX {
+            if (ok[c]) {
+                const float t = ce_at(mx, c) + logf(ce_at(se, c)) - ce_at(picked, c);
+                if constexpr (WEIGHTED) ce_sum += nu * t; else ce_sum += t;
+            }
+        }
+        float r[NPX], h[NPX];
+        CE_PX r[c] = ok[c] ? gw / ce_at(se, c) : 0.f;
+        CE_PX h[c] = ok[c] ? gw : 0.f;
+        float* d = dlogits + b * K * HW + p;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+                CE_PX ce_at(g, c) = ce_at(v[k], c) * r[c] - (lab[c] == k ? h[c] : 0.f);
+                if (live) {
+                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
+                    else d[k * HW] = g.x;
+                }
+                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
+            }
+        if constexpr (NPX == 1) ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
+        else if constexpr (XCH) {
+            // A lane owns 4 pixels x 64 bytes; stored straight from its registers every instruction would write 16 bytes every 256 (64 partial
+            // lines).  Instead the wave's 1024 16-byte pieces go through LDS (piece P = 16 lane + 4 q + cg at slot P ^ (lane & 7): the eight
+            // lanes a ds_write_b128 is served in hit eight different bank groups; the reader undoes it with (P >> 4) & 7) and leave in pixel
+            // order: one store instruction = 16 pixels x 64 bytes = 1 KB of contiguous output.
+            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int cg = 0; cg < 4; ++cg) {
+                    unsigned w[4];
+#pragma unroll
+                    for (int j2 = 0; j2 < 4; ++j2) {
+                        float e[2];
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int k = cg * 8 + 2 * j2 + u;
+                            float t = 0.f;
+                            if (k < KMAX) { if (k < K) t = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
+                            e[u] = t;
+                        }
+                        w[j2] = (unsigned)f2bf(e[0]) | ((unsigned)f2bf(e[1]) << 16);
+                    }
+                    const int P = 16 * lane + 4 * q + cg;
+                    xbuf[wv][P ^ (lane & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            __syncthreads();
+            const long long wave_pix = 4 * (base + 64 * wv);          // first pixel of this wave's 256
+            const long long npix = 4 * nq;
+#pragma unroll
+            for (int it = 0; it < 16; ++it) {
+                const int P = 64 * it + lane;
+                const long long px = wave_pix + (P >> 2);
+                if (px < npix) *reinterpret_cast<uint4*>((uint16_t*)dl_nhwc + px * dl_ldc + (P & 3) * 8) = xbuf[wv][P ^ ((P >> 4) & 7)];
+            }
+            __syncthreads();
+        } else if constexpr (!__is_same(NT, ce_no_nhwc)) {
+            NT* o = dl_nhwc + pix * dl_ldc;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int cg = 0; cg < 4; ++cg) {          // 32 physical channels: four groups of eight
+                    float t[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int k = cg * 8 + j;
+                        float e = 0.f;
+                        if (k < KMAX) { if (k < K) e = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
+                        t[j] = e;
+                    }
+                    Vec8<NT>::store(o + (long long)q * dl_ldc + cg * 8, t);
+                }
+        }
+    }
+    ce_sum = wave_sum(ce_sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ce_sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x + 0] = red[0] + red[1] + red[2] + red[3];
+        partial[2 * blockIdx.x + 1] = 0.f;
+    }
+}
+
+// The class-incremental step (build-defined, parity unpinned: the reference has no continual-learning code; the definitions are the "MiB"
+// losses of Cermelli et al., CVPR 2020, restated in include/clamd.h).  Classes [0, c_old) are old, [c_old, K) new, 0 is background:
+//   unbiased CE   label y <  c_old: -(LSE(old) - LSE(all))          gradient  softmax_all - [k < c_old] softmax_old
+//                 label y >= c_old: -(z_y - LSE(all))                          softmax_all - [k == y]            mean over the valid pixels
+//   unbiased KD   q = softmax(zo[0 .. c_old)),  -(1 / c_old) (q_0 (LSE(bgnew) - LSE(all)) + sum_{1 <= k < c_old} q_k (z_k - LSE(all)))
+//                 gradient softmax_all - [k in bgnew] q_0 exp(z_k - LSE(bgnew)) - [1 <= k < c_old] q_k          mean over ALL pixels, times lam
+// ce4_kernel's shape: NPX = 4 consecutive pixels per thread, 16-byte accesses, e_k = exp(z_k - max) computed ONCE per logit and kept in
+// the logit's register; sum_old e, sum_new e and e_0 give the three log-sum-exps.  KOLD > 0: the distillation term, exp(zo_k - max) of the
+// c_old <= KOLD old-model logits kept in KOLD more registers per pixel (one exponential each; instantiated per (KMAX, KOLD) so that
+// K = 21, c_old = 11 holds 24 + 16 float4).  A group whose largest logit lies 41 or more below the pixel's maximum (sum < 1e-18) has lost its
+// exponentials to underflow: the rare `rebase` branch reloads that group's logits and takes them relative to the group's own maximum
+// (fO / fN carry the shift), so  LSE(old) - LSE(all) and softmax_old stay exact however far apart the groups are.
+// With c_old == 1 and KOLD == 0 every operation on the path to d logits and to the loss is the one ce4_kernel makes (bit-equal results).
+// NPX = 1: the same arithmetic, one pixel per thread with 4-byte accesses, for H * W % 4 != 0 or unaligned tensors.
+template <int KMAX, int KOLD, int NPX, typename NT>
+__global__ void __launch_bounds__(256) ce4u_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                   const float* __restrict__ old_logits, int K_old_total, int c_old, float kd_scale,
+                                                   float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
+                                                   long long ignore_index, float grad_scale, NT* dl_nhwc, int dl_ldc,
+                                                   const unsigned int* __restrict__ count_rows) {
+    constexpr bool KD = KOLD > 0;
+    constexpr float NEG = -INFINITY, TINY = 1e-18f;
+    __shared__ float red[2][4];
+    __shared__ unsigned int cnt_tmp[4];
+    const long long nq = (long long)B * HW / NPX;
+    const unsigned int nv = ce_count_total(count_rows, 0, cnt_tmp);
+    const float gs = grad_scale / (float)max(nv, 1u);
+    const float gk = KD ? grad_scale * kd_scale : 0.f;             // kd_scale = lam / (c_old * B * H * W)
+    float ce_sum = 0.f, kd_sum = 0.f;
+    constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;
+    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange has barriers)
+        if (!XCH && !live) continue;
+        const long long pix = NPX * (live ? i : nq - 1), b = pix / HW, p = pix - b * HW;
+        const float* z = logits + b * K * HW + p;
+        float4 v[KMAX];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) v[k] = ce_ldpx<NPX>(z + k * HW);
+        long long lab[4];
+        ce_ld_labels<NPX>(labels, pix, lab);
+        // ---- the old model: o[k] = exp(zo_k - max), rq = 1 / sum
+        float4 o[KD ? KOLD : 1], rq = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (KD) {
+            const float* zo = old_logits + b * K_old_total * HW + p;
+            float4 mo = make_float4(NEG, NEG, NEG, NEG), so = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < KOLD; ++k)
+                if (k < c_old) {
+                    o[k] = ce_ldpx<NPX>(zo + k * HW);
+                    CE_PX ce_at(mo, c) = fmaxf(ce_at(mo, c), ce_at(o[k], c));
+                }
+#pragma unroll
+            for (int k = 0; k < KOLD; ++k)
+                if (k < c_old) CE_PX { ce_at(o[k], c) = expf(ce_at(o[k], c) - ce_at(mo, c)); ce_at(so, c) += ce_at(o[k], c); }
+            CE_PX ce_at(rq, c) = 1.f / ce_at(so, c);
+        }
+        // ---- the maxima of the two groups, then one exponential per logit
+        float4 mO = make_float4(NEG, NEG, NEG, NEG), mN = mO, mx;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) CE_PX {
+                ce_at(mO, c) = k < c_old ? fmaxf(ce_at(mO, c), ce_at(v[k], c)) : ce_at(mO, c);
+                ce_at(mN, c) = k < c_old ? ce_at(mN, c) : fmaxf(ce_at(mN, c), ce_at(v[k], c));
+            }
+        CE_PX ce_at(mx, c) = fmaxf(ce_at(mO, c), ce_at(mN, c));
+        const float4 z0 = v[0];
+        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), sO = se, sN = se, vmO = se, picked = se, dot = se;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) CE_PX {
+                float& e = ce_at(v[k], c);
+                ce_at(picked, c) = lab[c] == k ? e : ce_at(picked, c);
+                if constexpr (KD) { if (k >= 1 && k < KOLD) ce_at(dot, c) += k < c_old ? ce_at(o[k < KOLD ? k : 0], c) * (e - ce_at(mx, c)) : 0.f; }
+                e = expf(e - ce_at(mx, c));
+                ce_at(se, c) += e;                                   // in ce4_kernel's order
+                ce_at(sO, c) = k < c_old ? ce_at(se, c) : ce_at(sO, c);       // the prefix sum at k = c_old - 1
+                ce_at(vmO, c) = k < c_old ? fmaxf(ce_at(vmO, c), e) : ce_at(vmO, c);
+                ce_at(sN, c) += k < c_old ? 0.f : e;
+            }
+        bool ok[NPX], yold[NPX];
+        CE_PX { ok[c] = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K; yold[c] = ok[c] && lab[c] < c_old; }
+        // ---- underflowed groups (rare): their exponentials again, relative to the group's own maximum
+        float fO[NPX], fN[NPX], bN[NPX];
+        CE_PX { fO[c] = fN[c] = 1.f; bN[c] = ce_at(mx, c); }
+        bool nO[NPX], nN[NPX], anyO = false, anyN = false;
+        CE_PX { nO[c] = yold[c] && ce_at(sO, c) < TINY; nN[c] = KD && c_old < K && ce_at(sN, c) < TINY; anyO |= nO[c]; anyN |= nN[c]; }
+        if (anyO) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < c_old && k < K) {
+                    const float4 t = ce_ldpx<NPX>(z + k * HW);
+                    CE_PX { if (nO[c]) ce_at(v[k], c) = expf(ce_at(t, c) - ce_at(mO, c)); ce_at(s, c) += ce_at(v[k], c); }
+                }
+            CE_PX if (nO[c]) { ce_at(sO, c) = ce_at(s, c); ce_at(vmO, c) = 1.f; fO[c] = expf(ce_at(mO, c) - ce_at(mx, c)); }
+        }
+        if (anyN) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k >= c_old && k < K) {
+                    const float4 t = ce_ldpx<NPX>(z + k * HW);
+                    CE_PX { if (nN[c]) ce_at(v[k], c) = expf(ce_at(t, c) - ce_at(mN, c)); ce_at(s, c) += ce_at(v[k], c); }
+                }
+            CE_PX if (nN[c]) { ce_at(sN, c) = ce_at(s, c); bN[c] = ce_at(mN, c); fN[c] = expf(ce_at(mN, c) - ce_at(mx, c)); }
+        }
+        // ---- the loss terms and the per-pixel coefficients of the gradient
+        float rAO[NPX], rAN[NPX], h[NPX], hO[NPX], den[NPX], kq[NPX] = {}, kb0[NPX] = {}, kbN[NPX] = {};
+        CE_PX {
+            const float lse = ce_at(mx, c) + logf(ce_at(se, c));
+            if (live && ok[c])
+                ce_sum += yold[c] ? lse - (ce_at(mO, c) + logf(ce_at(sO, c) / ce_at(vmO, c))) : lse - ce_at(picked, c);
+            float rA = ok[c] ? gs / ce_at(se, c) : 0.f;
+            h[c] = ok[c] ? gs : 0.f;
+            hO[c] = yold[c] ? gs : 0.f;
+            den[c] = yold[c] ? ce_at(sO, c) : 1.f;
+            if constexpr (KD) {
+                rA = ((ok[c] ? gs : 0.f) + gk) / ce_at(se, c);
+                // LSE(bgnew) from z_0 and LSE(new) in the log domain: no second pass of exponentials, no underflow
+                const float lN = bN[c] + logf(ce_at(sN, c));                 // -inf when there is no new class
+                const float hi = fmaxf(ce_at(z0, c), lN), lo = fminf(ce_at(z0, c), lN);
+                const float lbg = hi + log1pf(expf(lo - hi));
+                const float q0 = ce_at(o[0], c) * ce_at(rq, c);
+                if (live) kd_sum -= q0 * (lbg - ce_at(mx, c)) + ce_at(rq, c) * ce_at(dot, c) - logf(ce_at(se, c));
+                kq[c] = gk * ce_at(rq, c);
+                kb0[c] = gk * q0 * expf(ce_at(z0, c) - lbg);
+                kbN[c] = gk * q0 * expf(bN[c] - lbg);
+            }
+            rAO[c] = rA * fO[c];
+            rAN[c] = rA * fN[c];
+        }
+        float* d = dlogits + b * K * HW + p;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                float4 g;
+                if (k < c_old) {
+                    CE_PX {
+                        const float e = ce_at(v[k], c);
+                        float t = fmaf(e, rAO[c], -((e / den[c]) * hO[c]));
+                        if constexpr (KD) t -= k == 0 ? kb0[c] : ce_at(o[k < KOLD ? k : 0], c) * kq[c];
+                        ce_at(g, c) = t;
+                    }
+                } else {
+                    CE_PX {
+                        const float e = ce_at(v[k], c);
+                        float t = fmaf(e, rAN[c], -(lab[c] == k ? h[c] : 0.f));
+                        if constexpr (KD) t -= e * kbN[c];
+                        ce_at(g, c) = t;
+                    }
+                }
+                if (live) {
+                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
+                    else d[k * HW] = g.x;
+                }
+                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
+            }
+        if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, base, nq, xbuf);
+        else ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
+    }
+    ce_sum = wave_sum(ce_sum);
+    kd_sum = wave_sum(kd_sum);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce_sum; red[1][threadIdx.x >> 6] = kd_sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+// out3 = {total, ce, kd} from the nblocks partial pairs (summed in double, in a fixed order); totals = {valid, bad} from the count rows
+__global__ void ce_finalize_kernel(const float* __restrict__ partial, int nblocks, unsigned int* totals,
+                                   float inv_npix, float lam, float* out3, const unsigned int* __restrict__ count_rows) {
+    __shared__ double red[2][256];
+    __shared__ unsigned int cnt_tmp[2][4];
+    const unsigned int nvalid = ce_count_total(count_rows, 0, cnt_tmp[0]), nbad = ce_count_total(count_rows, 1, cnt_tmp[1]);
+    if (threadIdx.x == 0) { totals[0] = nvalid; totals[1] = nbad; }
+    double a = 0, b = 0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float ce = (float)(red[0][0] / (double)max(nvalid, 1u));
+        const float kd = (float)(red[1][0] * inv_npix * lam);
+        out3[0] = ce + kd; out3[1] = ce; out3[2] = kd;
+    }
+}
+
+}  // namespace clamd
+
+using namespace clamd;
+
+// ------------------------------------------------------------------------------------------------ host side
+// What the entry points share: the argument checks, whether the four-pixel form applies, the grid, the pieces of the workspace.
+struct CePlan {
+    long long HW, npix;
+    bool four;               // H * W % 4 == 0 and every per-pixel tensor aligned for 16-byte (labels: 32-byte) accesses
+    int grid;                // workgroups of the loss kernel = partial pairs the finalize adds
+    float* partial;
+    unsigned int *totals, *rows;
+    hipStream_t s;
+};
+
+static int ce_fail(const char* who, const char* text) {
+    static thread_local char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", who, text);
+    return clamd_fail(msg);
+}
+
+// `who` prefixes the messages; `old_logits` may be null; dl_nhwc null: no NHWC copy; four_ok: the caller has a four-pixel kernel for this call
+static int ce_plan(CePlan* p, const char* who, bool four_ok, const float* logits, const long long* labels, const float* old_logits, const float* dlogits,
+                   const void* dl_nhwc, int dl_ldc, int dl_dtype, const float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H,
+                   int W, void* stream) {
+    if (!logits || !labels || !dlogits || !loss3 || !workspace || B <= 0 || H <= 0 || W <= 0) return ce_fail(who, "null pointer or empty shape");
+    if (K < 1 || K > 32) return ce_fail(who, "number of classes must be in [1, 32]");
+    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
+    if (((size_t)logits % 4) || ((size_t)dlogits % 4) || ((size_t)old_logits % 4) || ((size_t)labels % 8)) return ce_fail(who, "misaligned tensor");
+    if (dl_nhwc) {
+        if (dl_ldc < 32 || dl_ldc % 8 || ((size_t)dl_nhwc % 16)) return ce_fail(who, "the NHWC copy needs a pitch >= 32 channels, a multiple of 8, and a 16-byte aligned base");
+        if (dl_dtype != CLAMD_BF16 && dl_dtype != CLAMD_F32 && dl_dtype != CLAMD_SPLIT) return ce_fail(who, "bad dtype");
+        if (int e = clamd_check_split(dl_dtype, dl_nhwc, dl_ldc)) return e;
+    }
+    p->HW = (long long)H * W;
+    p->npix = B * p->HW;
+    p->four = four_ok && p->HW % 4 == 0 && ((size_t)logits % 16) == 0 && ((size_t)dlogits % 16) == 0 && ((size_t)old_logits % 16) == 0 && ((size_t)labels % 32) == 0;
+    const long long g = ((p->four ? p->npix / 4 : p->npix) + 255) / 256;
+    p->grid = g > CE_MAX_BLOCKS ? CE_MAX_BLOCKS : (int)g;
+    p->partial = (float*)workspace;
+    p->totals = (unsigned int*)workspace + CE_WS_TOTALS;
+    p->rows = (unsigned int*)workspace + CE_WS_ROWS;
+    p->s = (hipStream_t)stream;
+    return 0;
+}
+
+// f(tag) with the element type of the NHWC copy (ce_plan has checked dl_dtype) and with KMAX, the smallest multiple of 8 that holds K
+template <typename T> struct ce_type { using type = T; };
+template <int N> using ce_int = std::integral_constant<int, N>;
+template <typename F> static void ce_for_nt(const void* dl_nhwc, int dl_dtype, F f) {
+    if (!dl_nhwc) f(ce_type<ce_no_nhwc>{});
+    else if (dl_dtype == CLAMD_BF16) f(ce_type<bf16_t>{});
+    else if (dl_dtype == CLAMD_F32) f(ce_type<float>{});
+    else f(ce_type<split_t>{});
+}
+template <typename F> static void ce_for_kmax(int K, F f) {
+    if (K <= 8) f(ce_int<8>{}); else if (K <= 16) f(ce_int<16>{}); else if (K <= 24) f(ce_int<24>{}); else f(ce_int<32>{});
+}
+
+// ce4_kernel, plain (WT = ce_no_weight; four pixels only: the callers have no other use) or weighted (WT = const float*)
+template <typename WT>
+static void ce_launch(const CePlan& p, const float* logits, const long long* labels, WT weight, float* dlogits, void* dl_nhwc, int dl_ldc,
+                      int dl_dtype, int B, int K, long long ignore_index, float grad_scale) {
+    constexpr bool WEIGHTED = !__is_same(WT, ce_no_weight);
+    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
+        using NT = typename decltype(nt)::type;
+        auto launch = [&](auto kmax, auto npx) {
+            hipLaunchKernelGGL((ce4_kernel<decltype(kmax)::value, decltype(npx)::value, NT, WEIGHTED>), dim3(p.grid), dim3(256), 0, p.s, logits,
+                               labels, weight, dlogits, p.partial, B, K, p.HW, ignore_index, grad_scale, (NT*)dl_nhwc, dl_ldc, p.rows);
+        };
+        if constexpr (WEIGHTED) {
+            if (!p.four) return launch(ce_int<32>{}, ce_int<1>{});
+        }
+        ce_for_kmax(K, [&](auto kmax) { launch(kmax, ce_int<4>{}); });
+    });
+}
+
+// lam: the factor of the kd partial sums' mean over all pixels
+static void ce_finalize(const CePlan& p, float lam, float* loss3) {
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, p.s, p.partial, p.grid, p.totals, (float)(1.0 / (double)p.npix), lam, loss3, p.rows);
+}
+
+static void ce_count(const long long* labels, long long npix, long long ignore_index, int K, unsigned int* rows, hipStream_t s) {
+    hipLaunchKernelGGL(count_valid_rows_kernel, dim3(CE_COUNT_BLOCKS), dim3(256), 0, s, labels, npix, ignore_index, K, rows);
+}
+
+extern "C" {
+
+size_t clamd_ce_workspace_bytes(void) { return (size_t)CE_WS_WORDS * 4; }
+size_t clamd_ce_bad_label_count_offset(void) { return (size_t)(CE_WS_TOTALS + 1) * 4; }
+
+int clamd_ce_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old,
+                     double temperature, double lam, float* dlogits, float* loss3, void* workspace, size_t ws_bytes,
+                     int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream) {
+    CePlan p;
+    if (int e = ce_plan(&p, "ce", !old_logits, logits, labels, old_logits, dlogits, nullptr, 0, 0, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    if (old_logits && (c_old < 1 || c_old > K || c_old > K_old_total)) return clamd_fail("ce: bad c_old");
+    ce_count(labels, p.npix, ignore_index, K, p.rows, p.s);
+    if (p.four)
+        ce_launch(p, logits, labels, ce_no_weight{}, dlogits, nullptr, 0, 0, B, K, ignore_index, (float)grad_scale);
+    else      // the distillation term, odd sizes, misaligned storage: one pixel per thread
+        hipLaunchKernelGGL(ce_kernel<32>, dim3(p.grid), dim3(256), 0, p.s, logits, labels, old_logits, K_old_total, c_old,
+                           (float)(1.0 / temperature), (float)lam, dlogits, p.partial, p.rows, B, K, p.HW, ignore_index, (float)grad_scale);
+    ce_finalize(p, (float)lam, loss3);
+    return clamd_check_launch("ce_fwd_bwd");
+}
+
+int clamd_ce_count(const long long* labels, int B, int K, int H, int W, long long ignore_index, void* workspace, size_t ws_bytes, void* stream) {
+    if (K < 1 || K > 32 || !labels || B <= 0 || H <= 0 || W <= 0) return clamd_fail("ce_count: bad arguments");
+    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
+    ce_count(labels, (long long)B * H * W, ignore_index, K, (unsigned int*)workspace + CE_WS_ROWS, (hipStream_t)stream);
+    return clamd_check_launch("ce_count");
+}
+
+int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype,
+                             float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
+                             double grad_scale, void* stream) {
+    CePlan p;
+    if (int e = ce_plan(&p, "ce_fwd_bwd_counted", true, logits, labels, nullptr, dlogits, dl_nhwc, dl_ldc, dl_dtype, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    if (!p.four) return clamd_fail("ce_fwd_bwd_counted: needs H * W % 4 == 0 and 16-byte aligned logits / 32-byte aligned labels (use clamd_ce_fwd_bwd)");
+    ce_launch(p, logits, labels, ce_no_weight{}, dlogits, dl_nhwc, dl_ldc, dl_dtype, B, K, ignore_index, (float)grad_scale);
+    ce_finalize(p, 0.f, loss3);
+    return clamd_check_launch("ce_fwd_bwd_counted");
+}
+
+int clamd_ce_fwd_bwd_weighted(const float* logits, const long long* labels, const float* image_weight, float* dlogits, void* dl_nhwc,
+                              int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W,
+                              long long ignore_index, double grad_scale, void* stream) {
+    if (!image_weight || ((size_t)image_weight % 4)) return clamd_fail("ce_weighted: image_weight (B floats) is required (clamd_ce_fwd_bwd_counted is the unweighted loss)");
+    CePlan p;
+    if (int e = ce_plan(&p, "ce_weighted", true, logits, labels, nullptr, dlogits, dl_nhwc, dl_ldc, dl_dtype, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    ce_launch(p, logits, labels, image_weight, dlogits, dl_nhwc, dl_ldc, dl_dtype, B, K, ignore_index, (float)grad_scale);
+    ce_finalize(p, 0.f, loss3);
+    return clamd_check_launch("ce_fwd_bwd_weighted");
+}
+
+int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
+                              float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
+                              int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream) {
+    if (c_old < 1 || c_old > K) return clamd_fail("ce_unbiased: c_old must be in [1, K]");
+    if (!(lam >= 0.0)) return clamd_fail("ce_unbiased: lam must be >= 0");
+    if (lam == 0.0) old_logits = nullptr;
+    if (old_logits && c_old > K_old_total) return clamd_fail("ce_unbiased: c_old exceeds the old model's class count K_old_total");
+    CePlan p;
+    if (int e = ce_plan(&p, "ce_unbiased", true, logits, labels, old_logits, dlogits, dl_nhwc, dl_ldc, dl_dtype, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    const float kd_scale = old_logits ? (float)(lam / ((double)c_old * (double)p.npix)) : 0.f;
+    // ce4u_kernel<KMAX, KOLD, NPX, NT>: KOLD in {0, 16, 32} sizes the register array of the old model's exponentials (only its first c_old
+    // entries are touched); the odd-size path is not tuned: one instantiation per term
+    const int ko = !old_logits ? 0 : c_old <= 16 ? 16 : 32;
+    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
+        using NT = typename decltype(nt)::type;
+        auto launch = [&](auto kmax, auto kold, auto npx) {
+            hipLaunchKernelGGL((ce4u_kernel<decltype(kmax)::value, decltype(kold)::value, decltype(npx)::value, NT>), dim3(p.grid), dim3(256), 0, p.s,
+                               logits, labels, old_logits, K_old_total, c_old, kd_scale, dlogits, p.partial, B, K, p.HW, ignore_index,
+                               (float)grad_scale, (NT*)dl_nhwc, dl_ldc, p.rows);
+        };
+        if (!p.four) return old_logits ? launch(ce_int<32>{}, ce_int<32>{}, ce_int<1>{}) : launch(ce_int<32>{}, ce_int<0>{}, ce_int<1>{});
+        ce_for_kmax(K, [&](auto kmax) {
+            if (ko == 0) launch(kmax, ce_int<0>{}, ce_int<4>{});
+            else if (ko == 16) launch(kmax, ce_int<16>{}, ce_int<4>{});
+            else if constexpr (decltype(kmax)::value > 16) launch(kmax, ce_int<32>{}, ce_int<4>{});      // c_old > 16 needs K > 16
+        });
+    });
+    // the kernel leaves sum_px of c_old * kd_px: the finalize multiplies by 1 / npix and by its `lam` argument
+    ce_finalize(p, old_logits ? (float)(lam / (double)c_old) : 0.f, loss3);
+    return clamd_check_launch("ce_unbiased_fwd_bwd");
+}
+
+}  // extern "C"

@@ -1,11 +1,9 @@
 // Remaining pieces of the train-step path: error plumbing, weight re-packing (fp32 NCHW-style master parameters ->
-// the K-innermost compute-dtype layouts the implicit-GEMM kernels read), fused per-pixel cross-entropy forward+backward
-// (+ the build-defined distillation term), fused multi-tensor Adam (+ L2-to-old-weights, A13),
-// and the GPU-resident arg-max/confusion-matrix instrument.
+// the K-innermost compute-dtype layouts the implicit-GEMM kernels read), fused multi-tensor Adam (+ L2-to-old-weights, A13),
+// and the GPU-resident arg-max/confusion-matrix instrument.  The per-pixel loss is loss.hip.
 #include <string.h>
 #include <stdio.h>
 #include "common.hip.h"
-#include "ce_common.hip.h"
 #include "clamd_internal.h"
 #include "../../include/clamd_debug.h"
 
@@ -243,476 +241,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackJob* __restrict__ j
                 }
             }
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ loss
-// logits NCHW fp32 [B,K,H,W]; labels int64 [B,H,W].  nn.CrossEntropyLoss() (trainer.py:113): mean over pixels
-// whose label != ignore_index.  Optional distillation (build-defined, parity unpinned):
-//   + lam * mean_px KL( softmax(z_old[:, :c_old]/T) || softmax(z[:, :c_old]/T) )
-// count[0] = pixels that take part in the mean (label != ignore_index and inside [0, K)); count[1] = pixels whose label is
-// neither ignore_index nor a class -- torch's CrossEntropyLoss asserts on those; here they are left out of the loss and
-// REPORTED (the host side exposes the counter, loss.py), so a label bug in a class split cannot hide.
-__global__ void count_valid_kernel(const long long* __restrict__ labels, long long n, long long ignore_index,
-                                   int K, unsigned int* count) {
-    unsigned int c = 0, bad = 0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long l = labels[i];
-        const bool in = l >= 0 && l < K;
-        c += (l != ignore_index && in) ? 1u : 0u;
-        bad += (l != ignore_index && !in) ? 1u : 0u;
-    }
-    // ONE (integer, order-independent) atomic per block: atomics on a single address serialise at ~12 ns each
-    __shared__ unsigned int wsum[2][4];
-    c = (unsigned int)wave_sum((float)c);   // <= 64 * iterations: exact in fp32 for the sizes used here
-    bad = (unsigned int)wave_sum((float)bad);
-    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = c; wsum[1][threadIdx.x >> 6] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(count, wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3]);
-        const unsigned int b = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
-        if (b) atomicAdd(count + 1, b);
-    }
-}
-
-// The same count as one partial pair per workgroup (plain stores: no memset in front, no serialised atomics behind); the consumers add the
-// CE_COUNT_BLOCKS pairs themselves (integers: any order gives the same sum).
-__global__ void __launch_bounds__(256) count_valid_rows_kernel(const long long* __restrict__ labels, long long n, long long ignore_index,
-                                                               int K, unsigned int* rows /* [CE_COUNT_BLOCKS][2] */) {
-    unsigned int c = 0, bad = 0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long l = labels[i];
-        const bool in = l >= 0 && l < K;
-        c += (l != ignore_index && in) ? 1u : 0u;
-        bad += (l != ignore_index && !in) ? 1u : 0u;
-    }
-    __shared__ unsigned int wsum[2][4];
-    c = (unsigned int)wave_sum((float)c);   // <= 64 * iterations: exact in fp32 for the sizes used here
-    bad = (unsigned int)wave_sum((float)bad);
-    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = c; wsum[1][threadIdx.x >> 6] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        rows[2 * blockIdx.x + 0] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
-        rows[2 * blockIdx.x + 1] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
-    }
-}
-
-template <int KMAX>
-__global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                                 const float* __restrict__ old_logits, int K_old_total, int c_old,
-                                                 float inv_temp, float lam, float* __restrict__ dlogits,
-                                                 float* __restrict__ partial, const unsigned int* __restrict__ nvalid,
-                                                 int B, int K, long long HW, long long ignore_index, float grad_scale) {
-    __shared__ float red[2][4];
-    const long long npix = (long long)B * HW;
-    const float inv_valid = 1.f / (float)max(*nvalid, 1u);
-    const float inv_npix = 1.f / (float)npix;
-    float ce_sum = 0.f, kd_sum = 0.f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / HW, p = i - b * HW;
-        const float* z = logits + b * K * HW + p;
-        float v[KMAX];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            v[k] = k < K ? z[k * HW] : -INFINITY;
-            mx = fmaxf(mx, v[k]);
-        }
-        float se = 0.f;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) se += k < K ? expf(v[k] - mx) : 0.f;
-        const float lse = mx + logf(se);
-        const long long lab = labels[i];
-        const bool valid = lab != ignore_index && lab >= 0 && lab < K;
-        float picked = 0.f;
-        float g[KMAX];
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            const float sm = k < K ? expf(v[k] - lse) : 0.f;
-            const bool hit = valid && k == (int)lab;
-            picked = hit ? v[k] : picked;
-            g[k] = valid ? (sm - (hit ? 1.f : 0.f)) * inv_valid : 0.f;
-        }
-        if (valid) ce_sum += lse - picked;
-        if (old_logits) {
-            const float* zo = old_logits + b * K_old_total * HW + p;
-            float o[KMAX];
-            float mo = -INFINITY, mn = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                o[k] = k < c_old ? zo[k * HW] * inv_temp : -INFINITY;
-                mo = fmaxf(mo, o[k]);
-                mn = fmaxf(mn, k < c_old ? v[k] * inv_temp : -INFINITY);
-            }
-            float so = 0.f, sn = 0.f;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                so += k < c_old ? expf(o[k] - mo) : 0.f;
-                sn += k < c_old ? expf(v[k] * inv_temp - mn) : 0.f;
-            }
-            const float lo = mo + logf(so), ln = mn + logf(sn);
-            float kl = 0.f;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k)
-                if (k < c_old) {
-                    const float lp = o[k] - lo, lq = v[k] * inv_temp - ln;
-                    const float pk = expf(lp);
-                    kl += pk * (lp - lq);
-                    g[k] += lam * inv_npix * inv_temp * (expf(lq) - pk);
-                }
-            kd_sum += kl;
-        }
-        float* d = dlogits + b * K * HW + p;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) d[k * HW] = g[k] * grad_scale;
-    }
-    ce_sum = wave_sum(ce_sum);
-    kd_sum = wave_sum(kd_sum);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = ce_sum; red[1][wave] = kd_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
-}
-
-// The training-step case (no distillation term, H * W a multiple of 4): four consecutive pixels per thread -- 16-byte loads and stores, K * 16
-// bytes in flight per lane instead of K * 4 -- and ONE exponential per logit (e = exp(z - max) is kept; softmax = e / sum).  176 MB at
-// config 2: 71 -> 4x us per launch (the scalar kernel above stays for the distillation term and for odd sizes).
-// NT != void: d logits is ALSO written as an NHWC tensor [pixel][ldc] of compute dtype NT (channels K .. 31 zero) -- the layout the 1x1
-// head's data gradient reads, so the backward pass needs no NCHW -> NHWC conversion (88 + 67 MB at config 2 in bf16): a thread's four
-// pixels are consecutive there too (4 x 64 bytes in bf16).
-
-template <int KMAX, typename NT = ce_no_nhwc>
-__global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                                  float* __restrict__ dlogits, float* __restrict__ partial,
-                                                  const unsigned int* __restrict__ nvalid, int B, int K, long long HW,
-                                                  long long ignore_index, float grad_scale, NT* dl_nhwc = nullptr, int dl_ldc = 0,
-                                                  const unsigned int* __restrict__ count_rows = nullptr) {
-    __shared__ float red[4];
-    __shared__ unsigned int cnt_tmp[4];
-    const long long nq = (long long)B * HW / 4;
-    const unsigned int nv = count_rows ? ce_count_total(count_rows, 0, cnt_tmp) : *nvalid;
-    const float gs = grad_scale / (float)max(nv, 1u);
-    float ce_sum = 0.f;
-    constexpr bool XCH = __is_same(NT, bf16_t) && CE_EXCHANGE;      // NHWC copy through LDS: whole KBs per store instruction
-    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
-    for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {
-        const long long i = base + threadIdx.x;
-        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange below has barriers)
-        if (!XCH && !live) continue;
-        const long long pix = 4 * (live ? i : nq - 1), b = pix / HW, p = pix - b * HW;
-        const float* z = logits + b * K * HW + p;
-        float4 v[KMAX];
-        float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) {
-                v[k] = *reinterpret_cast<const float4*>(z + k * HW);
-                mx.x = fmaxf(mx.x, v[k].x); mx.y = fmaxf(mx.y, v[k].y); mx.z = fmaxf(mx.z, v[k].z); mx.w = fmaxf(mx.w, v[k].w);
-            }
-        long long lab[4];
-        *reinterpret_cast<longlong4*>(lab) = *reinterpret_cast<const longlong4*>(labels + pix);
-        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), picked = se;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) {
-                picked.x = lab[0] == k ? v[k].x : picked.x; picked.y = lab[1] == k ? v[k].y : picked.y;
-                picked.z = lab[2] == k ? v[k].z : picked.z; picked.w = lab[3] == k ? v[k].w : picked.w;
-                v[k].x = expf(v[k].x - mx.x); v[k].y = expf(v[k].y - mx.y); v[k].z = expf(v[k].z - mx.z); v[k].w = expf(v[k].w - mx.w);
-                se.x += v[k].x; se.y += v[k].y; se.z += v[k].z; se.w += v[k].w;
-            }
-        const bool ok[4] = {lab[0] != ignore_index && lab[0] >= 0 && lab[0] < K, lab[1] != ignore_index && lab[1] >= 0 && lab[1] < K,
-                            lab[2] != ignore_index && lab[2] >= 0 && lab[2] < K, lab[3] != ignore_index && lab[3] >= 0 && lab[3] < K};
-        if (live) {
-            if (ok[0]) ce_sum += mx.x + logf(se.x) - picked.x;
-            if (ok[1]) ce_sum += mx.y + logf(se.y) - picked.y;
-            if (ok[2]) ce_sum += mx.z + logf(se.z) - picked.z;
-            if (ok[3]) ce_sum += mx.w + logf(se.w) - picked.w;
-        }
-        const float4 r = make_float4(ok[0] ? gs / se.x : 0.f, ok[1] ? gs / se.y : 0.f, ok[2] ? gs / se.z : 0.f, ok[3] ? gs / se.w : 0.f);
-        const float4 h = make_float4(ok[0] ? gs : 0.f, ok[1] ? gs : 0.f, ok[2] ? gs : 0.f, ok[3] ? gs : 0.f);
-        float* d = dlogits + b * K * HW + p;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) {
-                float4 g;
-                g.x = v[k].x * r.x - (lab[0] == k ? h.x : 0.f); g.y = v[k].y * r.y - (lab[1] == k ? h.y : 0.f);
-                g.z = v[k].z * r.z - (lab[2] == k ? h.z : 0.f); g.w = v[k].w * r.w - (lab[3] == k ? h.w : 0.f);
-                if (live) *reinterpret_cast<float4*>(d + k * HW) = g;
-                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
-            }
-        if constexpr (XCH) {
-            // A lane owns 4 pixels x 64 bytes; stored straight from its registers every instruction would write 16 bytes every 256 (64 partial
-            // lines).  Instead the wave's 1024 16-byte pieces go through LDS (piece P = 16 lane + 4 q + cg at slot P ^ (lane & 7): the eight
-            // lanes a ds_write_b128 is served in hit eight different bank groups; the reader undoes it with (P >> 4) & 7) and leave in pixel
-            // order: one store instruction = 16 pixels x 64 bytes = 1 KB of contiguous output.
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int cg = 0; cg < 4; ++cg) {
-                    unsigned w[4];
-#pragma unroll
-                    for (int j2 = 0; j2 < 4; ++j2) {
-                        float e[2];
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            const int k = cg * 8 + 2 * j2 + u;
-                            float t = 0.f;
-                            if (k < KMAX) { if (k < K) t = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
-                            e[u] = t;
-                        }
-                        w[j2] = (unsigned)f2bf(e[0]) | ((unsigned)f2bf(e[1]) << 16);
-                    }
-                    const int P = 16 * lane + 4 * q + cg;
-                    xbuf[wv][P ^ (lane & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
-                }
-            __syncthreads();
-            const long long wave_pix = 4 * (base + 64 * wv);          // first pixel of this wave's 256
-            const long long npix = 4 * nq;
-#pragma unroll
-            for (int it = 0; it < 16; ++it) {
-                const int P = 64 * it + lane;
-                const long long px = wave_pix + (P >> 2);
-                if (px < npix) *reinterpret_cast<uint4*>((uint16_t*)dl_nhwc + px * dl_ldc + (P & 3) * 8) = xbuf[wv][P ^ ((P >> 4) & 7)];
-            }
-            __syncthreads();
-        } else if constexpr (!__is_same(NT, ce_no_nhwc)) {
-            NT* o = dl_nhwc + pix * dl_ldc;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int cg = 0; cg < 4; ++cg) {          // 32 physical channels: four groups of eight
-                    float t[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = cg * 8 + j;
-                        float e = 0.f;
-                        if (k < KMAX) { if (k < K) e = q == 0 ? v[k < KMAX ? k : 0].x : q == 1 ? v[k < KMAX ? k : 0].y : q == 2 ? v[k < KMAX ? k : 0].z : v[k < KMAX ? k : 0].w; }
-                        t[j] = e;
-                    }
-                    Vec8<NT>::store(o + (long long)q * dl_ldc + cg * 8, t);
-                }
-        }
-    }
-    ce_sum = wave_sum(ce_sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ce_sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0] + red[1] + red[2] + red[3];
-        partial[2 * blockIdx.x + 1] = 0.f;
-    }
-}
-
-// The class-incremental step (build-defined, parity unpinned: the reference has no continual-learning code; the definitions are the "MiB"
-// losses of Cermelli et al., CVPR 2020, restated in include/clamd.h).  Classes [0, c_old) are old, [c_old, K) new, 0 is background:
-//   unbiased CE   label y <  c_old: -(LSE(old) - LSE(all))          gradient  softmax_all - [k < c_old] softmax_old
-//                 label y >= c_old: -(z_y - LSE(all))                          softmax_all - [k == y]            mean over the valid pixels
-//   unbiased KD   q = softmax(zo[0 .. c_old)),  -(1 / c_old) (q_0 (LSE(bgnew) - LSE(all)) + sum_{1 <= k < c_old} q_k (z_k - LSE(all)))
-//                 gradient softmax_all - [k in bgnew] q_0 exp(z_k - LSE(bgnew)) - [1 <= k < c_old] q_k          mean over ALL pixels, times lam
-// ce4_kernel's shape: NPX = 4 consecutive pixels per thread, 16-byte accesses, e_k = exp(z_k - max) computed ONCE per logit and kept in
-// the logit's register; sum_old e, sum_new e and e_0 give the three log-sum-exps.  KOLD > 0: the distillation term, exp(zo_k - max) of the
-// c_old <= KOLD old-model logits kept in KOLD more registers per pixel (one exponential each; instantiated per (KMAX, KOLD) so that
-// K = 21, c_old = 11 holds 24 + 16 float4).  A group whose largest logit lies 41 or more below the pixel's maximum (sum < 1e-18) has lost its
-// exponentials to underflow: the rare `rebase` branch reloads that group's logits and takes them relative to the group's own maximum
-// (fO / fN carry the shift), so  LSE(old) - LSE(all) and softmax_old stay exact however far apart the groups are.
-// With c_old == 1 and KOLD == 0 every operation on the path to d logits and to the loss is the one ce4_kernel makes (bit-equal results).
-// NPX = 1: the same arithmetic, one pixel per thread with 4-byte accesses, for H * W % 4 != 0 or unaligned tensors.
-#define CE_PX _Pragma("unroll") for (int c = 0; c < NPX; ++c)
-
-template <int KMAX, int KOLD, int NPX, typename NT>
-__global__ void __launch_bounds__(256) ce4u_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                                   const float* __restrict__ old_logits, int K_old_total, int c_old, float kd_scale,
-                                                   float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
-                                                   long long ignore_index, float grad_scale, NT* dl_nhwc, int dl_ldc,
-                                                   const unsigned int* __restrict__ count_rows) {
-    constexpr bool KD = KOLD > 0;
-    constexpr float NEG = -INFINITY, TINY = 1e-18f;
-    __shared__ float red[2][4];
-    __shared__ unsigned int cnt_tmp[4];
-    const long long nq = (long long)B * HW / NPX;
-    const unsigned int nv = ce_count_total(count_rows, 0, cnt_tmp);
-    const float gs = grad_scale / (float)max(nv, 1u);
-    const float gk = KD ? grad_scale * kd_scale : 0.f;             // kd_scale = lam / (c_old * B * H * W)
-    float ce_sum = 0.f, kd_sum = 0.f;
-    constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;
-    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
-    for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {
-        const long long i = base + threadIdx.x;
-        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange has barriers)
-        if (!XCH && !live) continue;
-        const long long pix = NPX * (live ? i : nq - 1), b = pix / HW, p = pix - b * HW;
-        const float* z = logits + b * K * HW + p;
-        float4 v[KMAX];
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) v[k] = ce_ldpx<NPX>(z + k * HW);
-        long long lab[4];
-        if constexpr (NPX == 4) *reinterpret_cast<longlong4*>(lab) = *reinterpret_cast<const longlong4*>(labels + pix);
-        else lab[0] = labels[pix];
-        // ---- the old model: o[k] = exp(zo_k - max), rq = 1 / sum
-        float4 o[KD ? KOLD : 1], rq = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (KD) {
-            const float* zo = old_logits + b * K_old_total * HW + p;
-            float4 mo = make_float4(NEG, NEG, NEG, NEG), so = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < KOLD; ++k)
-                if (k < c_old) {
-                    o[k] = ce_ldpx<NPX>(zo + k * HW);
-                    CE_PX ce_at(mo, c) = fmaxf(ce_at(mo, c), ce_at(o[k], c));
-                }
-#pragma unroll
-            for (int k = 0; k < KOLD; ++k)
-                if (k < c_old) CE_PX { ce_at(o[k], c) = expf(ce_at(o[k], c) - ce_at(mo, c)); ce_at(so, c) += ce_at(o[k], c); }
-            CE_PX ce_at(rq, c) = 1.f / ce_at(so, c);
-        }
-        // ---- the maxima of the two groups, then one exponential per logit
-        float4 mO = make_float4(NEG, NEG, NEG, NEG), mN = mO, mx;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) CE_PX {
-                ce_at(mO, c) = k < c_old ? fmaxf(ce_at(mO, c), ce_at(v[k], c)) : ce_at(mO, c);
-                ce_at(mN, c) = k < c_old ? ce_at(mN, c) : fmaxf(ce_at(mN, c), ce_at(v[k], c));
-            }
-        CE_PX ce_at(mx, c) = fmaxf(ce_at(mO, c), ce_at(mN, c));
-        const float4 z0 = v[0];
-        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), sO = se, sN = se, vmO = se, picked = se, dot = se;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) CE_PX {
-                float& e = ce_at(v[k], c);
-                ce_at(picked, c) = lab[c] == k ? e : ce_at(picked, c);
-                if constexpr (KD) { if (k >= 1 && k < KOLD) ce_at(dot, c) += k < c_old ? ce_at(o[k < KOLD ? k : 0], c) * (e - ce_at(mx, c)) : 0.f; }
-                e = expf(e - ce_at(mx, c));
-                ce_at(se, c) += e;                                   // in ce4_kernel's order
-                ce_at(sO, c) = k < c_old ? ce_at(se, c) : ce_at(sO, c);       // the prefix sum at k = c_old - 1
-                ce_at(vmO, c) = k < c_old ? fmaxf(ce_at(vmO, c), e) : ce_at(vmO, c);
-                ce_at(sN, c) += k < c_old ? 0.f : e;
-            }
-        bool ok[NPX], yold[NPX];
-        CE_PX { ok[c] = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K; yold[c] = ok[c] && lab[c] < c_old; }
-        // ---- underflowed groups (rare): their exponentials again, relative to the group's own maximum
-        float fO[NPX], fN[NPX], bN[NPX];
-        CE_PX { fO[c] = fN[c] = 1.f; bN[c] = ce_at(mx, c); }
-        bool nO[NPX], nN[NPX], anyO = false, anyN = false;
-        CE_PX { nO[c] = yold[c] && ce_at(sO, c) < TINY; nN[c] = KD && c_old < K && ce_at(sN, c) < TINY; anyO |= nO[c]; anyN |= nN[c]; }
-        if (anyO) {
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k)
-                if (k < c_old && k < K) {
-                    const float4 t = ce_ldpx<NPX>(z + k * HW);
-                    CE_PX { if (nO[c]) ce_at(v[k], c) = expf(ce_at(t, c) - ce_at(mO, c)); ce_at(s, c) += ce_at(v[k], c); }
-                }
-            CE_PX if (nO[c]) { ce_at(sO, c) = ce_at(s, c); ce_at(vmO, c) = 1.f; fO[c] = expf(ce_at(mO, c) - ce_at(mx, c)); }
-        }
-        if (anyN) {
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k)
-                if (k >= c_old && k < K) {
-                    const float4 t = ce_ldpx<NPX>(z + k * HW);
-                    CE_PX { if (nN[c]) ce_at(v[k], c) = expf(ce_at(t, c) - ce_at(mN, c)); ce_at(s, c) += ce_at(v[k], c); }
-                }
-            CE_PX if (nN[c]) { ce_at(sN, c) = ce_at(s, c); bN[c] = ce_at(mN, c); fN[c] = expf(ce_at(mN, c) - ce_at(mx, c)); }
-        }
-        // ---- the loss terms and the per-pixel coefficients of the gradient
-        float rAO[NPX], rAN[NPX], h[NPX], hO[NPX], den[NPX], kq[NPX] = {}, kb0[NPX] = {}, kbN[NPX] = {};
-        CE_PX {
-            const float lse = ce_at(mx, c) + logf(ce_at(se, c));
-            if (live && ok[c])
-                ce_sum += yold[c] ? lse - (ce_at(mO, c) + logf(ce_at(sO, c) / ce_at(vmO, c))) : lse - ce_at(picked, c);
-            float rA = ok[c] ? gs / ce_at(se, c) : 0.f;
-            h[c] = ok[c] ? gs : 0.f;
-            hO[c] = yold[c] ? gs : 0.f;
-            den[c] = yold[c] ? ce_at(sO, c) : 1.f;
-            if constexpr (KD) {
-                rA = ((ok[c] ? gs : 0.f) + gk) / ce_at(se, c);
-                // LSE(bgnew) from z_0 and LSE(new) in the log domain: no second pass of exponentials, no underflow
-                const float lN = bN[c] + logf(ce_at(sN, c));                 // -inf when there is no new class
-                const float hi = fmaxf(ce_at(z0, c), lN), lo = fminf(ce_at(z0, c), lN);
-                const float lbg = hi + log1pf(expf(lo - hi));
-                const float q0 = ce_at(o[0], c) * ce_at(rq, c);
-                if (live) kd_sum -= q0 * (lbg - ce_at(mx, c)) + ce_at(rq, c) * ce_at(dot, c) - logf(ce_at(se, c));
-                kq[c] = gk * ce_at(rq, c);
-                kb0[c] = gk * q0 * expf(ce_at(z0, c) - lbg);
-                kbN[c] = gk * q0 * expf(bN[c] - lbg);
-            }
-            rAO[c] = rA * fO[c];
-            rAN[c] = rA * fN[c];
-        }
-        float* d = dlogits + b * K * HW + p;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < K) {
-                float4 g;
-                if (k < c_old) {
-                    CE_PX {
-                        const float e = ce_at(v[k], c);
-                        float t = fmaf(e, rAO[c], -((e / den[c]) * hO[c]));
-                        if constexpr (KD) t -= k == 0 ? kb0[c] : ce_at(o[k < KOLD ? k : 0], c) * kq[c];
-                        ce_at(g, c) = t;
-                    }
-                } else {
-                    CE_PX {
-                        const float e = ce_at(v[k], c);
-                        float t = fmaf(e, rAN[c], -(lab[c] == k ? h[c] : 0.f));
-                        if constexpr (KD) t -= e * kbN[c];
-                        ce_at(g, c) = t;
-                    }
-                }
-                if (live) {
-                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
-                    else d[k * HW] = g.x;
-                }
-                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
-            }
-        if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, base, nq, xbuf);
-        else if constexpr (!__is_same(NT, ce_no_nhwc)) {
-#pragma unroll
-            for (int cg = 0; cg < 4; ++cg) {
-                float t[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) t[j] = (cg * 8 + j < KMAX && cg * 8 + j < K) ? v[cg * 8 + j < KMAX ? cg * 8 + j : 0].x : 0.f;
-                Vec8<NT>::store(dl_nhwc + pix * dl_ldc + cg * 8, t);
-            }
-        }
-    }
-    ce_sum = wave_sum(ce_sum);
-    kd_sum = wave_sum(kd_sum);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce_sum; red[1][threadIdx.x >> 6] = kd_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
-}
-#undef CE_PX
-
-__global__ void ce_finalize_kernel(const float* __restrict__ partial, int nblocks, unsigned int* nvalid,
-                                   float inv_npix, float lam, float* out3, const unsigned int* __restrict__ count_rows = nullptr) {
-    __shared__ double red[2][256];
-    __shared__ unsigned int cnt_tmp[2][4];
-    if (count_rows) {      // the totals of the per-workgroup counts, left where the single-counter form keeps them
-        const unsigned int c = ce_count_total(count_rows, 0, cnt_tmp[0]), b = ce_count_total(count_rows, 1, cnt_tmp[1]);
-        if (threadIdx.x == 0) { nvalid[0] = c; nvalid[1] = b; }
-        __syncthreads();
-    }
-    double a = 0, b = 0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float ce = (float)(red[0][0] / (double)max(*nvalid, 1u));
-        const float kd = (float)(red[1][0] * inv_npix * lam);
-        out3[0] = ce + kd; out3[1] = ce; out3[2] = kd;
     }
 }
 
@@ -1097,32 +625,6 @@ int clamd_launch_pack(const void* jobs_dev, int njobs, int total_blocks, int dty
     return clamd_check_launch("pack");
 }
 
-// Dispatch of ce4u_kernel on (KMAX, KOLD, NPX, NT): KMAX the smallest multiple of 8 that holds K (as ce4_kernel), KOLD 16 or 32.
-template <int NPX, typename NT>
-static void ce_unbiased_launch(int g, hipStream_t s, const float* logits, const long long* labels, const float* old_logits, int K_old_total,
-                               int c_old, float kd_scale, float* dlogits, float* partial, int B, int K, long long HW, long long ignore_index,
-                               float grad_scale, void* dl_nhwc, int dl_ldc, const unsigned int* rows) {
-#define CEU(KM_, KO_) hipLaunchKernelGGL((ce4u_kernel<KM_, KO_, NPX, NT>), dim3(g), dim3(256), 0, s, logits, labels, old_logits, K_old_total, c_old, kd_scale, dlogits, partial, B, K, HW, ignore_index, grad_scale, (NT*)dl_nhwc, dl_ldc, rows)
-    if constexpr (NPX == 1) {      // the odd-size path is not tuned: one instantiation per term
-        if (old_logits) CEU(32, 32); else CEU(32, 0);
-    } else {
-        // KOLD in {0, 16, 32}: the register array of the old model's exponentials (only its first c_old entries are touched)
-        const int ko = !old_logits ? 0 : c_old <= 16 ? 16 : 32;
-        if (K <= 8) { if (ko == 0) CEU(8, 0); else CEU(8, 16); }
-        else if (K <= 16) { if (ko == 0) CEU(16, 0); else CEU(16, 16); }
-        else if (K <= 24) { if (ko == 0) CEU(24, 0); else if (ko == 16) CEU(24, 16); else CEU(24, 32); }
-        else { if (ko == 0) CEU(32, 0); else if (ko == 16) CEU(32, 16); else CEU(32, 32); }
-    }
-#undef CEU
-}
-
-// ce_finalize_kernel for the loss kernels of other translation units (pseudo.hip): the counted form, no distillation term
-void clamd_ce_finalize_counted(const float* partial, int nblocks, void* workspace, long long npix, float* loss3, hipStream_t s) {
-    unsigned int* nvalid = (unsigned int*)((float*)workspace + 2 * 2048);
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, nblocks, nvalid, (float)(1.0 / (double)npix), 0.f, loss3,
-                       (const unsigned int*)(nvalid + 4));
-}
-
 extern "C" {
 
 const char* clamd_last_error(void) { return g_err; }
@@ -1136,115 +638,6 @@ int clamd_bn_bwd_nsums(void) { return 5; }
 
 int clamd_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, void* stream) {
     return clamd_launch_pack(jobs_dev, njobs, total_blocks, dtype, nullptr, (hipStream_t)stream);
-}
-
-size_t clamd_ce_workspace_bytes(void) { return (size_t)(2 * 2048 + 4 + 2 * CE_COUNT_BLOCKS) * sizeof(float); }
-size_t clamd_ce_bad_label_count_offset(void) { return (size_t)(2 * 2048 + 1) * sizeof(float); }
-
-int clamd_ce_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old,
-                     double temperature, double lam, float* dlogits, float* loss3, void* workspace, size_t ws_bytes,
-                     int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream) {
-    if (K < 1 || K > 32) return clamd_fail("ce: number of classes must be in [1, 32]");
-    if (old_logits && (c_old < 1 || c_old > K || c_old > K_old_total)) return clamd_fail("ce: bad c_old");
-    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    float* partial = (float*)workspace;
-    unsigned int* nvalid = (unsigned int*)(partial + 2 * 2048);
-    const long long HW = (long long)H * W, npix = (long long)B * HW;
-    hipError_t me = hipMemsetAsync(nvalid, 0, 2 * sizeof(unsigned int), s);
-    if (me != hipSuccess) return clamd_fail("ce: memset failed");
-    int g = (int)((npix + 255) / 256);
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(count_valid_kernel, dim3(g > 512 ? 512 : g), dim3(256), 0, s, labels, npix, ignore_index, K, nvalid);
-    if (!old_logits && HW % 4 == 0 && ((size_t)logits % 16) == 0 && ((size_t)dlogits % 16) == 0 && ((size_t)labels % 32) == 0) {
-        g = (int)((npix / 4 + 255) / 256);
-        if (g > 2048) g = 2048;
-#define CE4(KM_) hipLaunchKernelGGL(ce4_kernel<KM_>, dim3(g), dim3(256), 0, s, logits, labels, dlogits, partial, nvalid, B, K, HW, ignore_index, (float)grad_scale)
-        if (K <= 8) CE4(8); else if (K <= 16) CE4(16); else if (K <= 24) CE4(24); else CE4(32);      // the logits of four pixels live in registers
-#undef CE4
-    } else
-        hipLaunchKernelGGL(ce_kernel<32>, dim3(g), dim3(256), 0, s, logits, labels, old_logits, K_old_total, c_old,
-                           (float)(1.0 / temperature), (float)lam, dlogits, partial, nvalid, B, K, HW, ignore_index, (float)grad_scale);
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, g, nvalid, (float)(1.0 / (double)npix),
-                       (float)lam, loss3);
-    return clamd_check_launch("ce_fwd_bwd");
-}
-
-int clamd_ce_count(const long long* labels, int B, int K, int H, int W, long long ignore_index, void* workspace, size_t ws_bytes, void* stream) {
-    if (K < 1 || K > 32 || !labels || B <= 0 || H <= 0 || W <= 0) return clamd_fail("ce_count: bad arguments");
-    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned int* rows = (unsigned int*)((float*)workspace + 2 * 2048 + 4);
-    const long long npix = (long long)B * H * W;
-    hipLaunchKernelGGL(count_valid_rows_kernel, dim3(CE_COUNT_BLOCKS), dim3(256), 0, s, labels, npix, ignore_index, K, rows);
-    return clamd_check_launch("ce_count");
-}
-
-int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype,
-                             float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
-                             double grad_scale, void* stream) {
-    if (K < 1 || K > 32) return clamd_fail("ce: number of classes must be in [1, 32]");
-    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
-    const long long HW = (long long)H * W, npix = (long long)B * HW;
-    if (HW % 4 || ((size_t)logits % 16) || ((size_t)dlogits % 16) || ((size_t)labels % 32))
-        return clamd_fail("ce_fwd_bwd_counted: needs H * W % 4 == 0 and 16-byte aligned logits / 32-byte aligned labels (use clamd_ce_fwd_bwd)");
-    if (dl_nhwc) {
-        if (dl_ldc < 32 || dl_ldc % 8 || ((size_t)dl_nhwc % 16)) return clamd_fail("ce_fwd_bwd_counted: the NHWC copy needs a pitch >= 32 channels, a multiple of 8, and a 16-byte aligned base");
-        if (int e = clamd_check_split(dl_dtype, dl_nhwc, dl_ldc)) return e;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    float* partial = (float*)workspace;
-    unsigned int* nvalid = (unsigned int*)(partial + 2 * 2048);
-    int g = (int)((npix / 4 + 255) / 256);
-    if (g > 2048) g = 2048;
-    const unsigned int* rows = (const unsigned int*)(partial + 2 * 2048 + 4);
-#define CE4T(KM_, T_) hipLaunchKernelGGL((ce4_kernel<KM_, T_>), dim3(g), dim3(256), 0, s, logits, labels, dlogits, partial, nvalid, B, K, HW, ignore_index, (float)grad_scale, (T_*)dl_nhwc, dl_ldc, rows)
-#define CE4K(T_) do { if (K <= 8) CE4T(8, T_); else if (K <= 16) CE4T(16, T_); else if (K <= 24) CE4T(24, T_); else CE4T(32, T_); } while (0)
-    if (!dl_nhwc) CE4K(ce_no_nhwc);
-    else if (dl_dtype == CLAMD_BF16) CE4K(bf16_t);
-    else if (dl_dtype == CLAMD_F32) CE4K(float);
-    else if (dl_dtype == CLAMD_SPLIT) CE4K(split_t);
-    else return clamd_fail("ce_fwd_bwd_counted: bad dtype");
-#undef CE4K
-#undef CE4T
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, g, nvalid, (float)(1.0 / (double)npix), 0.f, loss3, rows);
-    return clamd_check_launch("ce_fwd_bwd_counted");
-}
-
-int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
-                              float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
-                              int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream) {
-    if (!logits || !labels || !dlogits || !loss3 || !workspace || B <= 0 || H <= 0 || W <= 0) return clamd_fail("ce_unbiased: null pointer or empty shape");
-    if (K < 1 || K > 32) return clamd_fail("ce_unbiased: number of classes must be in [1, 32]");
-    if (c_old < 1 || c_old > K) return clamd_fail("ce_unbiased: c_old must be in [1, K]");
-    if (!(lam >= 0.0)) return clamd_fail("ce_unbiased: lam must be >= 0");
-    if (lam == 0.0) old_logits = nullptr;
-    if (old_logits && c_old > K_old_total) return clamd_fail("ce_unbiased: c_old exceeds the old model's class count K_old_total");
-    if (ws_bytes < clamd_ce_workspace_bytes()) return clamd_fail("ce: workspace too small");
-    if (((size_t)logits % 4) || ((size_t)dlogits % 4) || ((size_t)old_logits % 4) || ((size_t)labels % 8)) return clamd_fail("ce_unbiased: misaligned tensor");
-    if (dl_nhwc) {
-        if (dl_ldc < 32 || dl_ldc % 8 || ((size_t)dl_nhwc % 16)) return clamd_fail("ce_unbiased: the NHWC copy needs a pitch >= 32 channels, a multiple of 8, and a 16-byte aligned base");
-        if (dl_dtype != CLAMD_BF16 && dl_dtype != CLAMD_F32 && dl_dtype != CLAMD_SPLIT) return clamd_fail("ce_unbiased: bad dtype");
-        if (int e = clamd_check_split(dl_dtype, dl_nhwc, dl_ldc)) return e;
-    }
-    const long long HW = (long long)H * W, npix = (long long)B * HW;
-    hipStream_t s = (hipStream_t)stream;
-    float* partial = (float*)workspace;
-    unsigned int* nvalid = (unsigned int*)(partial + 2 * 2048);
-    const unsigned int* rows = (const unsigned int*)(partial + 2 * 2048 + 4);
-    const bool four = HW % 4 == 0 && ((size_t)logits % 16) == 0 && ((size_t)dlogits % 16) == 0 && ((size_t)old_logits % 16) == 0 && ((size_t)labels % 32) == 0;
-    int g = (int)(((four ? npix / 4 : npix) + 255) / 256);
-    if (g > 2048) g = 2048;
-    const float kd_scale = old_logits ? (float)(lam / ((double)c_old * (double)npix)) : 0.f;
-#define CEUL(NPX_, T_) ce_unbiased_launch<NPX_, T_>(g, s, logits, labels, old_logits, K_old_total, c_old, kd_scale, dlogits, partial, B, K, HW, ignore_index, (float)grad_scale, dl_nhwc, dl_ldc, rows)
-#define CEUN(NPX_) do { if (!dl_nhwc) CEUL(NPX_, ce_no_nhwc); else if (dl_dtype == CLAMD_BF16) CEUL(NPX_, bf16_t); else if (dl_dtype == CLAMD_F32) CEUL(NPX_, float); else CEUL(NPX_, split_t); } while (0)
-    if (four) CEUN(4); else CEUN(1);
-#undef CEUN
-#undef CEUL
-    // the kernel leaves sum_px of c_old * kd_px: the finalize multiplies by 1 / npix and by its `lam` argument
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, g, nvalid, (float)(1.0 / (double)npix),
-                       old_logits ? (float)(lam / (double)c_old) : 0.f, loss3, rows);
-    return clamd_check_launch("ce_unbiased_fwd_bwd");
 }
 
 int clamd_scale_by_device_scalar_nhwc(void* p, long long n, int dtype, const float* scale_dev, float* also_f32, long long n_f32, void* stream) {

@@ -23,65 +23,87 @@ from . import _lib
 from ._lib import call, ptr
 
 
-# d logits handed to the UNet's backward pass in the head data gradient's own layout (see _CEFn.forward); =0: the engine converts the NCHW
+# d logits handed to the UNet's backward pass in the head data gradient's own layout (see _forward); =0: the engine converts the NCHW
 # gradient as it does for any other loss (A/B measurements)
 HANDOVER = os.environ.get('CLAMD_LOSS_HANDOVER', '1') != '0'
+
+
+def _forward(ctx, holder, logits, labels, ignore_index, others, middle):
+    """What every loss forward shares: the checks, the allocation, and the bookkeeping behind the kernels.  `others`: the further tensors
+    the caller hands to the library.  ``middle(counted, logits, labels, dl, out3, ws, wsb)`` launches the loss: its own call on these
+    buffers, or ``counted(entry, lead, px_bytes)`` -- the training-step form."""
+    if not all(t.is_cuda for t in (logits, labels) + tuple(others) if t is not None):
+        raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
+    lib = _lib.load()
+    logits_in = logits
+    logits = logits.contiguous().float()
+    labels = labels.contiguous()
+    if labels.dtype != torch.int64:
+        raise TypeError('labels must be int64 (datasets/voc.py:72)')
+    B, K, H, W = logits.shape
+    if tuple(labels.shape) != (B, H, W):
+        raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
+    dl = torch.empty_like(logits)
+    out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+    wsb = lib.clamd_ce_workspace_bytes()
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
+    ctx.sink = None
+
+    def counted(entry, lead=(), px_bytes=0):
+        """clamd_ce_count, then `entry`(logits, labels, *lead, d logits, its NHWC copy, ...): the count of valid pixels as partial rows (no
+        memset, no atomics), and, when the logits come from this package's UNet, d logits written a second time in the layout (and dtype) its
+        1x1 head's data gradient reads -- the backward pass then starts without a conversion pass (unet._Engine.backward).
+        px_bytes: what the entry reads per pixel beyond the logits and the label."""
+        from . import unet as U
+        # (algorithmic bytes, SURVEY 8d: logits read + d logits written + the label; the counting pass reads the labels a second time)
+        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
+        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
+        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
+        U._hbm('loss', B * H * W * (2 * K * 4 + px_bytes + 8 + (ldc * eng.esize if eng is not None else 0)),
+               entry, ptr(logits), ptr(labels), *lead, ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb, B, K, H, W,
+               int(ignore_index), 1.0, _lib.stream_ptr())
+        if eng is not None:
+            ctx.sink = eng
+            # a STRONG reference: while the engine waits for this gradient its storage cannot be freed and handed to another
+            # tensor of the same shape (a second loss on the same logits would otherwise pass for this one by address)
+            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)
+
+    middle(counted, logits, labels, dl, out3, ws, wsb)
+    ctx.save_for_backward(dl)
+    ctx.parts = out3
+    # labels outside [0, K) that are not ignore_index: a device counter on the criterion (int(...) synchronises);
+    # torch's CrossEntropyLoss asserts on such labels, here they are left out of the mean and counted
+    off = lib.clamd_ce_bad_label_count_offset() // 4
+    holder.bad_labels = ws[off:off + 1].view(torch.int32)
+    holder.parts = out3
+    return out3[0]
+
+
+def _old_logits(old_logits, logits):
+    """-> (contiguous fp32 old_logits or None, its class count)"""
+    if old_logits is None:
+        return None, 0
+    old_logits = old_logits.contiguous().float()
+    B, _, H, W = logits.shape
+    if old_logits.dim() != 4 or old_logits.shape[0] != B or tuple(old_logits.shape[2:]) != (H, W):
+        raise ValueError('old_logits must be [B, K_old, H, W]')
+    return old_logits, old_logits.shape[1]
 
 
 class _CEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, old_logits, c_old, temperature, lam, ignore_index, holder):
-        if not logits.is_cuda:
-            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
-        lib = _lib.load()
-        logits_in = logits
-        logits = logits.contiguous().float()
-        labels = labels.contiguous()
-        if labels.dtype != torch.int64:
-            raise TypeError('labels must be int64 (datasets/voc.py:72)')
-        B, K, H, W = logits.shape
-        if tuple(labels.shape) != (B, H, W):
-            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
-        dl = torch.empty_like(logits)
-        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
-        wsb = lib.clamd_ce_workspace_bytes()
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
-        kold = 0
-        if old_logits is not None:
-            old_logits = old_logits.contiguous().float()
-            kold = old_logits.shape[1]
-            if old_logits.shape[0] != B or tuple(old_logits.shape[2:]) != (H, W):
-                raise ValueError('old_logits must be [B, K_old, H, W]')
-        ctx.sink = None
-        # the four-pixel kernels read 16 bytes of logits / 32 bytes of labels per lane: an odd storage offset takes the scalar kernel
-        aligned = logits.data_ptr() % 16 == 0 and dl.data_ptr() % 16 == 0 and labels.data_ptr() % 32 == 0
-        if old_logits is None and (H * W) % 4 == 0 and aligned:
-            # the training-step form: the count of valid pixels as partial rows (no memset, no atomics), and, when the logits come from this
-            # package's UNet, d logits written a second time in the layout (and dtype) its 1x1 head's data gradient reads -- the backward
-            # pass then starts without a conversion pass (unet._Engine.backward)
-            from . import unet as U
-            # (algorithmic bytes, SURVEY 8d: logits read + d logits written + the label; the counting pass reads the labels a second time)
-            U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
-            eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
-            nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
-            U._hbm('loss', B * H * W * (2 * K * 4 + 8 + (ldc * eng.esize if eng is not None else 0)),
-                   'clamd_ce_fwd_bwd_counted', ptr(logits), ptr(labels), ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb, B, K, H, W,
-                   int(ignore_index), 1.0, _lib.stream_ptr())
-            if eng is not None:
-                ctx.sink = eng
-                # a STRONG reference: while the engine waits for this gradient its storage cannot be freed and handed to another
-                # tensor of the same shape (a second loss on the same logits would otherwise pass for this one by address)
-                eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)
-        else:
-            call('clamd_ce_fwd_bwd', ptr(logits), ptr(labels), ptr(old_logits), kold, int(c_old), float(temperature),
-                 float(lam), ptr(dl), ptr(out3), ptr(ws), wsb, B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
-        ctx.save_for_backward(dl)
-        ctx.parts = out3
-        # labels outside [0, K) that are not ignore_index: a device counter on the criterion (int(...) synchronises);
-        # torch's CrossEntropyLoss asserts on such labels, here they are left out of the mean and counted
-        off = lib.clamd_ce_bad_label_count_offset() // 4
-        holder.bad_labels = ws[off:off + 1].view(torch.int32)
-        return out3[0]
+        def middle(counted, logits, labels, dl, out3, ws, wsb):
+            B, K, H, W = logits.shape
+            old, kold = _old_logits(old_logits, logits)
+            # the four-pixel kernels read 16 bytes of logits / 32 bytes of labels per lane: an odd storage offset takes the scalar kernel
+            aligned = logits.data_ptr() % 16 == 0 and dl.data_ptr() % 16 == 0 and labels.data_ptr() % 32 == 0
+            if old is None and (H * W) % 4 == 0 and aligned:
+                counted('clamd_ce_fwd_bwd_counted')
+            else:
+                call('clamd_ce_fwd_bwd', ptr(logits), ptr(labels), ptr(old), kold, int(c_old), float(temperature),
+                     float(lam), ptr(dl), ptr(out3), ptr(ws), wsb, B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
+        return _forward(ctx, holder, logits, labels, ignore_index, (old_logits,), middle)
 
     @staticmethod
     def backward(ctx, g):
@@ -127,46 +149,11 @@ class _UCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, old_logits, c_old, lam, ignore_index, holder):
-        if not logits.is_cuda or not labels.is_cuda or (old_logits is not None and not old_logits.is_cuda):
-            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
-        lib = _lib.load()
-        logits_in = logits
-        logits = logits.contiguous().float()
-        labels = labels.contiguous()
-        if labels.dtype != torch.int64:
-            raise TypeError('labels must be int64 (datasets/voc.py:72)')
-        B, K, H, W = logits.shape
-        if tuple(labels.shape) != (B, H, W):
-            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
-        kold = 0
-        if old_logits is not None:
-            old_logits = old_logits.contiguous().float()
-            kold = old_logits.shape[1]
-            if old_logits.dim() != 4 or old_logits.shape[0] != B or tuple(old_logits.shape[2:]) != (H, W):
-                raise ValueError('old_logits must be [B, K_old, H, W]')
-        dl = torch.empty_like(logits)
-        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
-        wsb = lib.clamd_ce_workspace_bytes()
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
-        from . import unet as U
-        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
-        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
-        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
-        kd = old_logits is not None and lam != 0
-        # algorithmic bytes: logits read, d logits written, the c_old old-model logits, the label, the NHWC copy
-        U._hbm('loss', B * H * W * ((2 * K + (c_old if kd else 0)) * 4 + 8 + (ldc * eng.esize if eng is not None else 0)),
-               'clamd_ce_unbiased_fwd_bwd', ptr(logits), ptr(labels), ptr(old_logits), kold, int(c_old), float(lam), ptr(dl), ptr(nh), ldc, dcode,
-               ptr(out3), ptr(ws), wsb, B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
-        ctx.sink = None
-        if eng is not None:
-            ctx.sink = eng
-            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)      # a strong reference, as in _CEFn.forward
-        ctx.save_for_backward(dl)
-        ctx.parts = out3
-        off = lib.clamd_ce_bad_label_count_offset() // 4
-        holder.bad_labels = ws[off:off + 1].view(torch.int32)
-        holder.parts = out3
-        return out3[0]
+        def middle(counted, logits, *_):
+            old, kold = _old_logits(old_logits, logits)
+            # algorithmic bytes: the c_old old-model logits on top of the plain loss's
+            counted('clamd_ce_unbiased_fwd_bwd', (ptr(old), kold, int(c_old), float(lam)), 4 * c_old if old is not None and lam != 0 else 0)
+        return _forward(ctx, holder, logits, labels, ignore_index, (old_logits,), middle)
 
     @staticmethod
     def backward(ctx, g):
@@ -178,41 +165,13 @@ class _WCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, image_weight, ignore_index, holder):
-        if not logits.is_cuda or not labels.is_cuda or not image_weight.is_cuda:
-            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
-        lib = _lib.load()
-        logits_in = logits
-        logits = logits.contiguous().float()
-        labels = labels.contiguous()
-        if labels.dtype != torch.int64:
-            raise TypeError('labels must be int64 (datasets/voc.py:72)')
-        B, K, H, W = logits.shape
-        if tuple(labels.shape) != (B, H, W):
-            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
-        if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
-            raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
-        image_weight = image_weight.contiguous()
-        dl = torch.empty_like(logits)
-        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
-        wsb = lib.clamd_ce_workspace_bytes()
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
-        from . import unet as U
-        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
-        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
-        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
-        # algorithmic bytes: as clamd_ce_fwd_bwd_counted (the B weights do not count)
-        U._hbm('loss', B * H * W * (2 * K * 4 + 8 + (ldc * eng.esize if eng is not None else 0)),
-               'clamd_ce_fwd_bwd_weighted', ptr(logits), ptr(labels), ptr(image_weight), ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb,
-               B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
-        ctx.sink = None
-        if eng is not None:
-            ctx.sink = eng
-            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)      # a strong reference, as in _CEFn.forward
-        ctx.save_for_backward(dl)
-        ctx.parts = out3
-        off = lib.clamd_ce_bad_label_count_offset() // 4
-        holder.bad_labels = ws[off:off + 1].view(torch.int32)
-        return out3[0]
+        def middle(counted, logits, *_):
+            B = logits.shape[0]
+            if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
+                raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
+            nu = image_weight.contiguous()
+            counted('clamd_ce_fwd_bwd_weighted', (ptr(nu),))      # algorithmic bytes: the plain loss's (the B weights do not count)
+        return _forward(ctx, holder, logits, labels, ignore_index, (image_weight,), middle)
 
     @staticmethod
     def backward(ctx, g):

@@ -356,7 +356,7 @@ int clamd_nhwc_to_nchw(const void* src, int ldc, float* dst, int B, int C, int H
 /* NCHW fp32 image -> NHWC with the 3x3 neighbourhood folded into channels: dst[p, c*9 + ky*3 + kx] (9*C <= Cp). */
 int clamd_nchw_im2col3(const float* src, void* dst, int ldc, int B, int C, int H, int W, int Cp, int dtype, void* stream);
 
-/* ---- parameters, loss, optimiser, metrics (misc.hip) ---------------------------------------------------------
+/* ---- parameters, optimiser, metrics (misc.hip); the loss (loss.hip) -------------------------------------------
  * clamd_pack: one fused launch re-packing every fp32 master parameter into the layouts above (job table built by
  * the host). */
 int clamd_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, void* stream);
@@ -394,7 +394,7 @@ int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float
 int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
                               float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
                               int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream);
-/* ---- pseudo-labelling of the old classes (pseudo.hip) --------------------------------------------------------
+/* ---- pseudo-labelling of the old classes (pseudo.hip; its loss clamd_ce_fwd_bwd_weighted: loss.hip) -----------
  * Build-defined, parity unpinned (the reference has no continual-learning code): the classification half of PLOP (Douillard et al.,
  * CVPR 2021, section 3.2).  In a task-2 batch every pixel of an old class is labelled 0; the frozen old model labels the background
  * pixels it is confident about, the others are ignored, and each image's loss is scaled by the accepted share of its background.

@@ -5,6 +5,7 @@ Tolerances: fp32 path (exact-fp32 MFMA) differs from the oracle only by summatio
 bf16 path: the oracle is run on bf16-rounded inputs/weights, so what remains is accumulation order plus the bf16
 rounding of the stored output (2^-9 relative per element) -> rel L2 < 6e-3.
 """
+import functools
 import os
 
 import numpy as np
@@ -1270,22 +1271,52 @@ def test_cross_entropy_edge_cases(C):
         crit(torch.randn(1, 33, 16, 16, device='cuda'), torch.zeros(1, 16, 16, dtype=torch.int64, device='cuda'))
 
 
-@pytest.mark.parametrize('name,dcode', DT)
-def test_cross_entropy_counted_form_and_nhwc_copy(C, name, dcode):
-    """clamd_ce_count + clamd_ce_fwd_bwd_counted (the training-step form: partial-row count, no memset / atomics) against
-    clamd_ce_fwd_bwd bit for bit -- loss, d logits, both counters -- for 5 / 21 / 32 classes with ignored and out-of-range labels; the
-    second copy of d logits (NHWC, compute dtype, channels K .. 31 zero) equals clamd_nchw_to_nhwc of the NCHW one bit for bit, and
-    clamd_scale_by_device_scalar_nhwc scales it as the fp32 kernel scales the NCHW tensor."""
-    lib, ptr, s = C._lib, C._lib.ptr, C._lib.stream_ptr()
-    L = lib.load()
+@functools.lru_cache(maxsize=None)
+def _ce_cases():
+    """(K, B, H, W, logits, labels, old_logits, ref) for 5 / 21 / 32 classes and an odd size (5 x 7: one pixel per thread), every one with
+    ignored and out-of-range labels.  ref: the float64 cross-entropy over the kept pixels (label a class) on the CPU -> loss, d logits;
+    numpy counts of the valid and of the bad (neither ignore_index nor a class) labels.  Computed once for the three dtypes."""
     rng = np.random.default_rng(21)
-    wsb = L.clamd_ce_workspace_bytes()
-    off = L.clamd_ce_bad_label_count_offset() // 4
-    for K, B, H, W in ((5, 2, 8, 12), (21, 3, 16, 20), (32, 1, 4, 4)):
-        z = dev(rnd(rng, B, K, H, W) * 4)
+    cases = []
+    for K, B, H, W in ((5, 2, 8, 12), (21, 3, 16, 20), (32, 1, 4, 4), (5, 2, 5, 7)):
+        z = rnd(rng, B, K, H, W) * 4
         y = rng.integers(0, K, (B, H, W))
         y[0, 0, :3] = -100; y[0, 1, 0] = K + 2; y[-1, -1, -1] = -7
-        yt = dev(y, torch.int64)
+        zo = rnd(np.random.default_rng(22), B, K, H, W) * 3          # a stream of its own: the cases above keep their draws
+        keep = (y >= 0) & (y < K)
+        z64 = torch.from_numpy(z.astype(np.float64)).requires_grad_()
+        loss = torch.nn.functional.cross_entropy(z64.permute(0, 2, 3, 1)[torch.from_numpy(keep)], torch.from_numpy(y[keep]))
+        loss.backward()
+        cases.append((K, B, H, W, z, y, zo, (float(loss.detach()), z64.grad.numpy(), int(keep.sum()), int(((y != -100) & ~keep).sum()))))
+    return cases
+
+
+def _ce_check(l3, d, ws, off, ref, what):
+    """loss and d logits against the float64 reference at test_cross_entropy_edge_cases' bounds; the two counters exactly"""
+    ref_l, ref_d, nvalid, nbad = ref
+    got_l, got_e = float(l3[1]), rel_l2(d.cpu().numpy(), ref_d)
+    counts = ws[off - 1:off + 1].view(torch.int32).tolist()
+    print(f'{what}: loss {got_l:.8f} ref {ref_l:.8f} |diff| {abs(got_l - ref_l):.2e}  d logits rel_l2 {got_e:.2e}  counters {counts} ref {[nvalid, nbad]}')
+    assert abs(got_l - ref_l) < 1e-5 * max(1, abs(ref_l)), what
+    assert got_e < 1e-5, what
+    assert counts == [nvalid, nbad], what
+
+
+@pytest.mark.parametrize('name,dcode', DT)
+def test_cross_entropy_counted_form_and_nhwc_copy(C, name, dcode):
+    """clamd_ce_count + clamd_ce_fwd_bwd_counted (the training-step form: partial-row count, four pixels per thread) against
+    clamd_ce_fwd_bwd bit for bit -- loss, d logits, both counters -- for 5 / 21 / 32 classes with ignored and out-of-range labels; the
+    second copy of d logits (NHWC, compute dtype, channels K .. 31 zero) equals clamd_nchw_to_nhwc of the NCHW one bit for bit, and
+    clamd_scale_by_device_scalar_nhwc scales it as the fp32 kernel scales the NCHW tensor.  Both entry points run one kernel at these
+    sizes, so loss, d logits and the counters are also held against a float64 cross-entropy and numpy counts (_ce_cases); so is the
+    one-pixel kernel of clamd_ce_fwd_bwd at an odd size, alone and with its distillation term (oracle, test_distillation_loss_vs_oracle's
+    bound)."""
+    lib, ptr, s = C._lib, C._lib.ptr, C._lib.stream_ptr()
+    L = lib.load()
+    wsb = L.clamd_ce_workspace_bytes()
+    off = L.clamd_ce_bad_label_count_offset() // 4
+    for K, B, H, W, z, y, _, ref in _ce_cases()[:3]:
+        z, yt = dev(z), dev(y, torch.int64)
         d0, l0, w0 = torch.empty_like(z), torch.empty(3, device='cuda'), torch.zeros(wsb // 4, device='cuda')
         lib.call('clamd_ce_fwd_bwd', ptr(z), ptr(yt), None, 0, 0, 1.0, 0.0, ptr(d0), ptr(l0), ptr(w0), wsb, B, K, H, W, -100, 1.0, s)
         d1, l1, w1 = torch.empty_like(z), torch.empty(3, device='cuda'), torch.full((wsb // 4,), float('nan'), device='cuda')
@@ -1293,6 +1324,8 @@ def test_cross_entropy_counted_form_and_nhwc_copy(C, name, dcode):
         lib.call('clamd_ce_count', ptr(yt), B, K, H, W, -100, ptr(w1), wsb, s)
         lib.call('clamd_ce_fwd_bwd_counted', ptr(z), ptr(yt), ptr(d1), ptr(nh), 32, dcode, ptr(l1), ptr(w1), wsb, B, K, H, W, -100, 1.0, s)
         sync()
+        _ce_check(l0, d0, w0, off, ref, f'ce_fwd_bwd K{K}')
+        _ce_check(l1, d1, w1, off, ref, f'ce_fwd_bwd_counted K{K}')
         assert torch.equal(d0, d1) and torch.equal(l0, l1)
         assert torch.equal(w0[off - 1:off + 1].view(torch.int32), w1[off - 1:off + 1].view(torch.int32)) and int(w1[off:off + 1].view(torch.int32)) == 2
         conv = C.ops.to_nhwc(d1, dcode, cp=32)
@@ -1313,6 +1346,22 @@ def test_cross_entropy_counted_form_and_nhwc_copy(C, name, dcode):
         assert torch.equal(before.view(torch.int16), nh.view(torch.int16))
     with pytest.raises(RuntimeError, match='H \\* W % 4'):
         lib.call('clamd_ce_fwd_bwd_counted', ptr(z), ptr(yt), ptr(d1), None, 0, 0, ptr(l1), ptr(w1), wsb, 1, 32, 1, 6, -100, 1.0, s)
+    # H * W = 35: clamd_ce_fwd_bwd's one-pixel kernel, which takes its count from the partial rows as well
+    K, B, H, W, z, y, zo, ref = _ce_cases()[3]
+    zd, yt, zod = dev(z), dev(y, torch.int64), dev(zo)
+    d0, l0, w0 = torch.empty_like(zd), torch.empty(3, device='cuda'), torch.full((wsb // 4,), float('nan'), device='cuda')
+    lib.call('clamd_ce_fwd_bwd', ptr(zd), ptr(yt), None, 0, 0, 1.0, 0.0, ptr(d0), ptr(l0), ptr(w0), wsb, B, K, H, W, -100, 1.0, s)
+    sync()
+    _ce_check(l0, d0, w0, off, ref, 'ce_fwd_bwd 5x7')
+    lib.call('clamd_ce_fwd_bwd', ptr(zd), ptr(yt), ptr(zod), K, 3, 2.0, 0.7, ptr(d0), ptr(l0), ptr(w0), wsb, B, K, H, W, -100, 1.0, s)
+    sync()
+    z64, kept = z.astype(np.float64), np.where((y >= 0) & (y < K), y, -100)      # the oracle knows ignore_index only
+    l_ce, d_ce = O.cross_entropy(z64, kept)
+    l_kd, d_kd = O.distill_kl(z64, zo.astype(np.float64), 3, 2.0, 0.7)
+    got_l, got_e = float(l0[0]), rel_l2(d0.cpu().numpy(), d_ce + d_kd)
+    print(f'ce_fwd_bwd 5x7 + KD: loss {got_l:.8f} ref {float(l_ce + l_kd):.8f} |diff| {abs(got_l - float(l_ce + l_kd)):.2e}  d logits rel_l2 {got_e:.2e}')
+    assert abs(got_l - float(l_ce + l_kd)) < 1e-5 and got_e < 1e-5
+    assert w0[off - 1:off + 1].view(torch.int32).tolist() == list(ref[2:])
 
 
 def test_distillation_loss_vs_oracle(C):

@@ -1,7 +1,7 @@
 """A/B of the class-incremental loss launch against the distillation path it replaces, alternated in one process (as tools/step_ab.py):
 
     new   clamd_ce_count + clamd_ce_unbiased_fwd_bwd (KD term, NHWC copy in the compute dtype)
-    old   clamd_ce_fwd_bwd with the KD term (scalar kernel, memset + atomics count) + the clamd_nchw_to_nhwc pass the backward then makes
+    old   clamd_ce_fwd_bwd with the KD term (scalar kernel) + the clamd_nchw_to_nhwc pass the backward then makes
 
 K = 21, c_old = 11, batch 16, 256 x 256; device events around 50 launches after warm-up, 5 rounds each (the spread of the same binary).
 Then the whole task-2 step (old-model forward + forward + loss + backward + Adam) of one grown UNet(11 -> 21, 3, 64), unbiased=True against

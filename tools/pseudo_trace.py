@@ -22,7 +22,7 @@ tr.begin_task2(c_old=c_old, distill_lambda=0, new_classes=K - c_old, pseudo_labe
 for _ in range(5):
     tr.train_step(x, y2)
 counts = tr.pseudo.counts
-tr.pseudo = None                      # the plain loss at 21 classes in the same trace: ce4_kernel<24> beside ce4w_kernel<24>
+tr.pseudo = None                      # the plain loss at 21 classes in the same trace: the plain ce4_kernel<24, 4> beside the weighted one
 for _ in range(5):
     tr.train_step(x, y2)
 torch.cuda.synchronize()
