@@ -86,14 +86,16 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
         float se = 0.f;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) se += k < K ? expf(v[k] - mx) : 0.f;
-        const float lse = mx + logf(se);
+        // log softmax_k = (z_k - max) - log(sum): the difference first.  z_k - (max + log(sum)) would round the log-sum-exp to an ulp of |max|
+        // (2^-17 at logits near 100), a relative error of that size in the softmax of the largest logits
+        const float lg = logf(se), lse = mx + lg;
         const long long lab = labels[i];
         const bool valid = lab != ignore_index && lab >= 0 && lab < K;
         float picked = 0.f;
         float g[KMAX];
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
-            const float sm = k < K ? expf(v[k] - lse) : 0.f;
+            const float sm = k < K ? expf((v[k] - mx) - lg) : 0.f;
             const bool hit = valid && k == (int)lab;
             picked = hit ? v[k] : picked;
             g[k] = valid ? (sm - (hit ? 1.f : 0.f)) * inv_valid : 0.f;
@@ -115,12 +117,12 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
                 so += k < c_old ? expf(o[k] - mo) : 0.f;
                 sn += k < c_old ? expf(v[k] * inv_temp - mn) : 0.f;
             }
-            const float lo = mo + logf(so), ln = mn + logf(sn);
+            const float lgo = logf(so), lgn = logf(sn);
             float kl = 0.f;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
                 if (k < c_old) {
-                    const float lp = o[k] - lo, lq = v[k] * inv_temp - ln;
+                    const float lp = (o[k] - mo) - lgo, lq = (v[k] * inv_temp - mn) - lgn;          // as above
                     const float pk = expf(lp);
                     kl += pk * (lp - lq);
                     g[k] += lam * inv_npix * inv_temp * (expf(lq) - pk);
@@ -479,15 +481,18 @@ __global__ void __launch_bounds__(256) ce4u_kernel(const float* __restrict__ log
             den[c] = yold[c] ? ce_at(sO, c) : 1.f;
             if constexpr (KD) {
                 rA = ((ok[c] ? gs : 0.f) + gk) / ce_at(se, c);
-                // LSE(bgnew) from z_0 and LSE(new) in the log domain: no second pass of exponentials, no underflow
-                const float lN = bN[c] + logf(ce_at(sN, c));                 // -inf when there is no new class
-                const float hi = fmaxf(ce_at(z0, c), lN), lo = fminf(ce_at(z0, c), lN);
-                const float lbg = hi + log1pf(expf(lo - hi));
+                // LSE(bgnew) from z_0 and LSE(new) in the log domain: no second pass of exponentials, no underflow.  Both relative to bN, the
+                // base of the new group's exponentials: bN + log(sum) would round LSE(new) to an ulp of |bN| (2^-17 at logits near 100), and
+                // exp(z - LSE(bgnew)) would carry that as a relative error into the gradient of the background and of every new class
+                const float lN = logf(ce_at(sN, c));                         // LSE(new) - bN; -inf when there is no new class
+                const float z0r = ce_at(z0, c) - bN[c];
+                const float hi = fmaxf(z0r, lN), lo = fminf(z0r, lN);
+                const float lbg = hi + log1pf(expf(lo - hi));                // LSE(bgnew) - bN
                 const float q0 = ce_at(o[0], c) * ce_at(rq, c);
-                if (live) kd_sum -= q0 * (lbg - ce_at(mx, c)) + ce_at(rq, c) * ce_at(dot, c) - logf(ce_at(se, c));
+                if (live) kd_sum -= q0 * (lbg + (bN[c] - ce_at(mx, c))) + ce_at(rq, c) * ce_at(dot, c) - logf(ce_at(se, c));
                 kq[c] = gk * ce_at(rq, c);
-                kb0[c] = gk * q0 * expf(ce_at(z0, c) - lbg);
-                kbN[c] = gk * q0 * expf(bN[c] - lbg);
+                kb0[c] = gk * q0 * expf(z0r - lbg);
+                kbN[c] = gk * q0 * expf(-lbg);
             }
             rAO[c] = rA * fO[c];
             rAN[c] = rA * fN[c];
