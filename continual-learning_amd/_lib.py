@@ -129,6 +129,8 @@ SIGNATURES = {
     'clamd_pseudo_entropy_hist': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     'clamd_pseudo_label': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _D, _I, _I, _I, _LL, _P]),
     'clamd_ce_fwd_bwd_weighted': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
+    'clamd_pod_workspace_bytes': (_SZ, [_I, _I, _I, _I, _I]),
+    'clamd_local_pod_fwd_bwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _SZ, _I, _I, _I, _D, _P]),
     'clamd_adam_step': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     'clamd_adam_step_consolidated': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),

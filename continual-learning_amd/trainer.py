@@ -15,7 +15,8 @@ every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0
 (``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py).
 Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
 of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
-confident predictions (build-defined, pseudo.py).
+confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`` adds Local POD distillation of the logits (build-defined,
+pod.py).
 """
 import os
 import warnings
@@ -30,6 +31,7 @@ from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam
 from .consolidate import Consolidation
 from .pseudo import PseudoLabeler
+from .pod import LocalPODLoss
 from . import syncbn
 from .unet import UNet
 
@@ -50,6 +52,8 @@ class Trainer:
         self.start_epoch = 0
         self.old_model = None
         self.pseudo = None                # pseudo.PseudoLabeler once begin_task2(pseudo_label=True) ran
+        self.pod = None                   # pod.LocalPODLoss once begin_task2(pod_lambda > 0) ran
+        self.pod_channels = 0
         self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
         self.ewc_lambda = 0.0
         self.build_model()
@@ -100,7 +104,8 @@ class Trainer:
 
     def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
                     importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background',
-                    pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None):
+                    pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None,
+                    pod_lambda=0.0, pod_levels=3):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
         still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
@@ -117,7 +122,18 @@ class Trainer:
         background pixels it is confident about, ignores the others, and (pseudo_adaptive) weights each image's loss by the accepted share.
         Not with unbiased=True (that criterion treats every label < c_old alike: pseudo-labels would change nothing), and pseudo_adaptive
         not with distill_lambda > 0 (DistillationCrossEntropy's kernel has no per-image weight).  The canonical setting is
-        begin_task2(c_old, distill_lambda=0, pseudo_label=True, pseudo_adaptive=True)."""
+        begin_task2(c_old, distill_lambda=0, pseudo_label=True, pseudo_adaptive=True).
+        Local POD (build-defined, pod.py): pod_lambda > 0 keeps LocalPODLoss(pod_levels, square=False, normalize=True, lam=pod_lambda); every
+        step then runs the old model's forward, also with distill_lambda == 0 and without pseudo-labels, and adds
+        pod(outputs, old, channels=c_old, merge_extra=True) to the criterion's loss -- the old background against the new background plus
+        the new classes.  It combines with every criterion above; PLOP's step is begin_task2(c_old, distill_lambda=0, pseudo_label=True,
+        pseudo_adaptive=True, pod_lambda=...).  pod_lambda == 0 leaves the step as it is."""
+        if not pod_lambda >= 0:
+            raise ValueError('pod_lambda must be >= 0')
+        if pod_lambda > 0 and int(pod_levels) not in (1, 2, 3):
+            raise ValueError('pod_levels must be 1, 2 or 3')
+        if pod_lambda > 0 and c_old < 1:
+            raise ValueError('pod_lambda > 0 needs c_old >= 1 (class 0, the background, is always an old class)')
         if pseudo_label and unbiased:
             raise ValueError('pseudo_label=True with unbiased=True: the unbiased cross-entropy treats every label below c_old alike, '
                              'so pseudo-labels would change nothing')
@@ -142,6 +158,8 @@ class Trainer:
             self.distill = UnbiasedDistillationCrossEntropy(c_old, distill_lambda)
         else:
             self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
+        self.pod = LocalPODLoss(pod_levels, square=False, normalize=True, lam=pod_lambda) if pod_lambda > 0 else None
+        self.pod_channels = int(c_old)
         self.pseudo = None
         if pseudo_label:
             self.pseudo = PseudoLabeler(c_old, bins=pseudo_bins, adaptive=pseudo_adaptive, min_factor=pseudo_min_factor,
@@ -263,7 +281,8 @@ class Trainer:
         outputs = self.model(inputs)
         self.reset_grad()
         distill = getattr(self, 'distill', None) if self.old_model is not None else None
-        if distill is not None or self.pseudo is not None:
+        pod = self.pod if self.old_model is not None else None
+        if distill is not None or self.pseudo is not None or pod is not None:
             with torch.no_grad():
                 old = self.old_model(inputs)
         nu = None
@@ -273,6 +292,8 @@ class Trainer:
             loss = distill(outputs, labels, old)
         else:
             loss = self.c_loss(outputs, labels, nu) if nu is not None else self.c_loss(outputs, labels)
+        if pod is not None:       # a second loss on the logits: the engine receives the summed NCHW gradient and converts it
+            loss = loss + pod(outputs, old, channels=self.pod_channels, merge_extra=True)
         loss.backward()
         self.optim.step()
         return outputs, loss

@@ -432,6 +432,40 @@ int clamd_pseudo_label(const float* old_logits, int K_old_total, int c_old, cons
 int clamd_ce_fwd_bwd_weighted(const float* logits, const long long* labels, const float* image_weight, float* dlogits, void* dl_nhwc,
                               int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W,
                               long long ignore_index, double grad_scale, void* stream);
+/* ---- Local POD distillation (pod.hip) -----------------------------------------------------------------------
+ * Build-defined, parity unpinned (the reference has no continual-learning code): the distillation half of PLOP (Douillard et al., CVPR
+ * 2021, section 3.1).  Multi-scale strip-pooled statistics of the new model's tensor are matched to the old model's.
+ * Inputs: a = new tensor [B, Ca, H, W], b = old tensor [B, Cb, H, W], both fp32 NCHW; C compared channels, 1 <= C <= min(Ca, Cb); flags
+ *   merge_extra, square, normalize; levels in {1, 2, 3}: k = 1, 2, 4 regions per side; H and W multiples of 2^(levels-1).
+ * Channel view: channel c < C of b is b_c, of a it is a_c, except that with merge_extra channel 0 of a is m = a_0 + sum_{k=C}^{Ca-1} a_k,
+ *   added in ascending k (the logits form: the old model's background against the new model's background plus its new classes).  Without
+ *   merge_extra the channels >= C of a take no part.
+ * Value: v = x^2 with square (for post-ReLU features; applied after the merge), else v = x.
+ * Embedding of image n: at each level s (k = 2^s, h = H / k, w = W / k) and channel c
+ *   row strips     r[s, c, y, j] = (1 / w) sum_{x in column segment j} v[c, y, x]        (H k values)
+ *   column strips  q[s, c, i, x] = (1 / h) sum_{y in row segment i} v[c, y, x]           (k W values)
+ *   concatenated over levels and channels: D = C (H + W) (2^levels - 1) entries.
+ * Normalisation: with normalize e = emb / max(||emb||_2, 1e-12) per image, else e = emb.
+ * Loss: loss1[0] = lam * (1 / B) sum_n ||e_a,n - e_b,n||_2.
+ * Gradient: da [B, Ca, H, W] = grad_scale * d loss / d a, exact, all Ca channels written (the caller needs no memset): the channels >= C
+ *   carry channel 0's gradient under merge_extra and zeros otherwise; an image whose distance is exactly 0 contributes gradient 0; none
+ *   is taken with respect to b.  da == NULL: the loss alone (the same bits), nothing else written outside the workspace.
+ * Three passes and a one-thread sum: the strip pass reads a and b once (16-byte accesses, four pixels per lane, when W % 4 == 0 and a, b
+ *   are 16-byte aligned; a one-element variant of the same arithmetic inside the same entry point for any other width or alignment) and
+ *   writes the finest level's unnormalised row sums per column slot and column sums per row band (a workgroup owns an image, a channel and
+ *   a band of rows; the band split depends on the shape only); the finalize pass forms the coarser levels as fixed-order sums of those,
+ *   the per-image norms, the distance (from the differences e_a - e_b, never from ||a||^2 + ||b||^2 - 2 a.b) and the normalisation
+ *   Jacobian's dot product in fp64, and writes two coefficient tables Grow [B, C, H, kmax], Gcol [B, C, kmax, W] that fold every level,
+ *   1 / w, 1 / h, the normalisation, lam / B and grad_scale; the gradient pass writes
+ *   da[n, c, y, x] = (Grow[n, c, y, seg(x)] + Gcol[n, c, seg(y), x]) * (square ? 2 * value : 1) and reads a only with square.
+ * No atomics, every element written whole with plain stores: bit-reproducible.  Enqueue only: no allocation, no synchronisation, the
+ * device is the stream's (graph-capturable).  workspace: 16-byte aligned, at least clamd_pod_workspace_bytes(B, C, H, W, levels) bytes
+ * (0 for an invalid shape), contents undefined afterwards.  levels outside 1..3, C outside [1, min(Ca, Cb)], a size that is not a
+ * multiple of 2^(levels-1), a workspace too small, B > 32767: an error, nothing launched. */
+size_t clamd_pod_workspace_bytes(int B, int C, int H, int W, int levels);
+int clamd_local_pod_fwd_bwd(const float* a, int Ca, const float* b, int Cb, int C, int merge_extra, int square, int normalize,
+                            int levels, double lam, float* da, float* loss1, void* workspace, size_t ws_bytes,
+                            int B, int H, int W, double grad_scale, void* stream);
 /* torch.optim.Adam.step over all parameters in one launch (trainer.py:108-110,176); hyper/step/derived live on the
  * device so a captured graph can be replayed with a new learning rate.  l2_accum_dev (optional, with the L2-to-old-weights
  * term): 1 + nchunks floats, [0] = sum ||theta - theta_old||^2 of this step, [1..] = per-workgroup partials added in a fixed

@@ -1,0 +1,307 @@
+"""CPU: Local POD distillation (include/clamd.h, csrc/pod.hip, pod.py) -- the restatement of the definition in torch that the GPU tests
+compare the kernels with, the closed-form gradient the kernels implement against autograd on that restatement, and the host-side argument
+handling.  No kernel is launched here."""
+import ctypes
+import itertools
+import math
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope='module')
+def C():
+    import continual_learning_amd as C
+    return C
+
+
+# ------------------------------------------------------------------------------------------------ the definition, restated in torch
+def pod_view(a, b, C, merge, square):
+    """The channel view and the value: -> (va, vb, base) with base the merged (unsquared) tensor of a's compared channels."""
+    base = a[:, :C]
+    if merge:
+        m = a[:, 0]
+        for k in range(C, a.shape[1]):          # ascending k
+            m = m + a[:, k]
+        base = torch.cat([m[:, None], a[:, 1:C]], 1)
+    vb = b[:, :C]
+    return (base * base, vb * vb, base) if square else (base, vb, base)
+
+
+def pod_embed(v, levels):
+    """[B, C, H, W] -> [B, D], D = C (H + W) (2^levels - 1): per level the row strips [C, H, k] then the column strips [C, k, W]."""
+    B, C, H, W = v.shape
+    parts = []
+    for s in range(levels):
+        k = 1 << s
+        parts.append((v.reshape(B, C, H, k, W // k).sum(-1) / (W // k)).reshape(B, -1))
+        parts.append((v.reshape(B, C, k, H // k, W).sum(3) / (H // k)).reshape(B, -1))
+    return torch.cat(parts, 1)
+
+
+def pod_loss(a, b, C, merge, square, normalize, levels, lam):
+    """The loss of include/clamd.h, differentiable in a (torch's norm has gradient 0 at distance 0)."""
+    va, vb, _ = pod_view(a, b, C, merge, square)
+    ea, eb = pod_embed(va, levels), pod_embed(vb, levels)
+    if normalize:
+        ea = ea / ea.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        eb = eb / eb.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    return lam * (ea - eb).norm(dim=1).mean()
+
+
+def pod_closed_form(a, b, C, merge, square, normalize, levels, lam):
+    """The loss and its gradient as the kernels form them, in a's dtype, without autograd: -> (loss, da [B, Ca, H, W], mag [B, Ca, H, W]),
+    mag = (|row table| + |column table|) * |2 value or 1|, the magnitude the two fp32 table entries of an element are rounded at."""
+    B, Ca, H, W = a.shape
+    va, vb, base = pod_view(a, b, C, merge, square)
+    ea, eb = pod_embed(va, levels), pod_embed(vb, levels)
+    ia = torch.ones(B, 1, dtype=a.dtype)
+    project = torch.zeros(B, 1, dtype=a.dtype)
+    if normalize:
+        na, nb = ea.norm(dim=1, keepdim=True), eb.norm(dim=1, keepdim=True)
+        ia = 1 / na.clamp_min(1e-12)
+        project = (na > 1e-12).to(a.dtype)
+        ea, eb = ea * ia, eb * (1 / nb.clamp_min(1e-12))
+    d = ea - eb
+    dist = d.norm(dim=1, keepdim=True)
+    u = torch.where(dist > 0, d / torch.where(dist > 0, dist, torch.ones_like(dist)), torch.zeros_like(d))
+    ge = (u - project * ea * (ea * u).sum(1, keepdim=True)) * ia * (lam / B)
+    row, col = torch.zeros(B, C, H, W, dtype=a.dtype), torch.zeros(B, C, H, W, dtype=a.dtype)
+    o = 0
+    for s in range(levels):
+        k = 1 << s
+        r = ge[:, o:o + C * H * k].reshape(B, C, H, k) / (W // k); o += C * H * k
+        q = ge[:, o:o + C * k * W].reshape(B, C, k, W) / (H // k); o += C * k * W
+        row = row + r.repeat_interleave(W // k, dim=3)
+        col = col + q.repeat_interleave(H // k, dim=2)
+    fac = 2 * base if square else torch.ones_like(base)
+    g, mag = (row + col) * fac, (row.abs() + col.abs()) * fac.abs()
+    da, full = torch.zeros_like(a), torch.zeros_like(a)
+    da[:, :C], full[:, :C] = g, mag
+    if merge:
+        da[:, C:], full[:, C:] = g[:, :1], mag[:, :1]
+    return lam * dist.mean(), da, full
+
+
+# ------------------------------------------------------------------------------------------------------------------------- the ABI
+def test_entry_points_in_header_table_and_library(C):
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'clamd.h')).read(), flags=re.S)
+    lib = ctypes.CDLL(C._lib.LIB_PATH)
+    for name in ('clamd_pod_workspace_bytes', 'clamd_local_pod_fwd_bwd'):
+        m = re.search(name + r'\s*\(([^;{]*?)\)\s*;', src)
+        assert m, f'{name} is not declared in include/clamd.h'
+        nargs = len([x for x in m.group(1).split(',') if x.strip()])
+        assert name in C._lib.SIGNATURES and len(C._lib.SIGNATURES[name][1]) == nargs, name
+        assert hasattr(lib, name), f'{name} is not exported by libclamd.so'
+    assert (5, 19) == tuple(len(C._lib.SIGNATURES[n][1]) for n in ('clamd_pod_workspace_bytes', 'clamd_local_pod_fwd_bwd'))
+    L = C._lib.load()
+    # the size query is host arithmetic: 0 for what the entry point refuses, and no smaller than the tables the definition names
+    assert L.clamd_pod_workspace_bytes(2, 3, 8, 12, 3) >= 4 * 2 * 3 * (8 * 4 + 4 * 12) * 3
+    for bad in ((2, 3, 8, 12, 0), (2, 3, 8, 12, 4), (2, 3, 6, 12, 3), (2, 3, 8, 10, 3), (0, 3, 8, 12, 1), (2, 0, 8, 12, 1)):
+        assert L.clamd_pod_workspace_bytes(*bad) == 0, bad
+
+
+# ---------------------------------------------------------------------------------------------------------------- the closed form
+FLAGS = list(itertools.product([False, True], repeat=3))
+
+
+@pytest.mark.parametrize('levels', [1, 2, 3])
+@pytest.mark.parametrize('merge,square,normalize', FLAGS)
+def test_closed_form_gradient_equals_autograd(levels, merge, square, normalize):
+    g = torch.Generator().manual_seed(levels + 10 * merge + 20 * square + 40 * normalize)
+    for (B, Ca, Cb, C, H, W) in ((3, 5, 6, 3, 8, 12), (1, 2, 2, 2, 4, 4), (2, 4, 1, 1, 12, 8)):
+        a = torch.randn(B, Ca, H, W, generator=g, dtype=torch.float64).requires_grad_()
+        b = torch.randn(B, Cb, H, W, generator=g, dtype=torch.float64)
+        loss = pod_loss(a, b, C, merge, square, normalize, levels, 0.7)
+        want, = torch.autograd.grad(loss, a)
+        got_loss, got, mag = pod_closed_form(a.detach(), b, C, merge, square, normalize, levels, 0.7)
+        assert float(got_loss) == pytest.approx(float(loss.detach()), rel=1e-13)
+        assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max()), (B, Ca, Cb, C, H, W)
+        assert bool((mag >= got.abs() * (1 - 1e-12)).all())
+        if not merge:
+            assert float(got[:, C:].abs().max() if Ca > C else 0.0) == 0.0
+
+
+def test_embedding_size_and_strip_values():
+    v = torch.arange(2 * 3 * 4 * 8, dtype=torch.float64).reshape(2, 3, 4, 8)
+    for levels in (1, 2, 3):
+        assert pod_embed(v, levels).shape == (2, 3 * (4 + 8) * ((1 << levels) - 1))
+    e = pod_embed(v, 2)[0]
+    assert float(e[0]) == float(v[0, 0, 0].mean())                                   # level 0, row strip of row 0
+    assert float(e[3 * 4]) == float(v[0, 0, :, 0].mean())                            # level 0, column strip of column 0
+    assert float(e[3 * 12 + 1]) == float(v[0, 0, 0, 4:].mean())                      # level 1, row 0, right half
+    assert float(e[3 * 12 + 3 * 8 + 8]) == float(v[0, 0, 2:, 0].mean())              # level 1, lower half, column 0
+
+
+@pytest.mark.parametrize('merge,square,normalize', FLAGS)
+def test_identical_inputs_give_zero(merge, square, normalize):
+    a = torch.randn(2, 3, 8, 8, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
+    if merge:                     # C = Ca = Cb: nothing to merge, the flag must change nothing
+        assert pod_view(a, a, 3, True, square)[0].equal(pod_view(a, a, 3, False, square)[0])
+    loss, da, _ = pod_closed_form(a, a.clone(), 3, merge, square, normalize, 3, 1.0)
+    assert float(loss) == 0.0 and float(da.abs().max()) == 0.0
+    x = a.clone().requires_grad_()
+    g, = torch.autograd.grad(pod_loss(x, a, 3, merge, square, normalize, 3, 1.0), x)
+    assert float(g.abs().max()) == 0.0
+
+
+# --------------------------------------------------------------------------------------------------------------------- the module
+def test_module_refuses_what_the_kernels_cannot_take(C):
+    assert C.LocalPODLoss is C.pod.LocalPODLoss
+    pod = C.LocalPODLoss()
+    assert (pod.levels, pod.square, pod.normalize, pod.lam) == (3, False, True, 1.0)
+    with pytest.raises(RuntimeError, match='runs only on GPU tensors: there is no CPU fallback'):
+        pod(torch.zeros(1, 2, 4, 4), torch.zeros(1, 2, 4, 4))
+    with pytest.raises(ValueError, match='levels'):
+        C.LocalPODLoss(levels=4)
+    with pytest.raises(ValueError, match='levels'):
+        C.LocalPODLoss(levels=0)
+    # the remaining checks come before anything touches the device: meta tensors claim to be elsewhere, so patch the device test only
+    check = C.pod._check
+
+    class OnGpu(torch.Tensor):
+        is_cuda = True
+
+    def t(*shape):
+        return torch.zeros(*shape).as_subclass(OnGpu)
+
+    with pytest.raises(ValueError, match='multiples of'):
+        check(t(1, 2, 6, 8), t(1, 2, 6, 8), None, 3)
+    with pytest.raises(ValueError, match='multiples of'):
+        check(t(1, 2, 8, 7), t(1, 2, 8, 7), None, 2)
+    check(t(1, 2, 5, 7), t(1, 2, 5, 7), None, 1)
+    for ch in (0, 3, -1):
+        with pytest.raises(ValueError, match='channels must be in'):
+            check(t(1, 4, 8, 8), t(1, 2, 8, 8), ch, 3)
+    assert check(t(1, 4, 8, 8), t(1, 2, 8, 8), None, 3)[5] == 2
+    with pytest.raises(ValueError, match='new and old must be'):
+        check(t(1, 4, 8, 8), t(2, 4, 8, 8), None, 3)
+    with pytest.raises(ValueError, match='new and old must be'):
+        check(t(1, 4, 8, 8), t(1, 4, 8, 4), None, 3)
+
+
+def test_begin_task2_pod_arguments(C, monkeypatch):
+    """Host only: the argument checks come first, and the kept module is what the issue names.  The model is never built: a stand-in
+    records what begin_task2 does after its checks."""
+    import inspect
+    sig = inspect.signature(C.Trainer.begin_task2)
+    assert sig.parameters['pod_lambda'].default == 0.0 and sig.parameters['pod_levels'].default == 3
+    tr = C.Trainer.__new__(C.Trainer)
+    for kw in (dict(pod_lambda=-1.0), dict(pod_lambda=float('nan')), dict(pod_lambda=0.5, pod_levels=4), dict(pod_lambda=0.5, pod_levels=0)):
+        with pytest.raises(ValueError, match='pod_'):
+            tr.begin_task2(3, distill_lambda=0, **kw)
+    with pytest.raises(ValueError, match='c_old'):
+        tr.begin_task2(0, distill_lambda=0, pod_lambda=0.5)
+
+    import torch.nn as nn
+
+    class FakeNet(nn.Module):                    # what begin_task2 asks of a model: the constructor arguments, a state, parameters
+        grad_sync = None
+
+        def __init__(self, num_classes, in_dim, conv_dim, compute_dtype='fp32'):
+            super().__init__()
+            self.num_classes, self.in_dim, self.conv_dim, self.compute_dtype = num_classes, in_dim, conv_dim, compute_dtype
+            self.w = nn.Parameter(torch.ones(2))
+
+    monkeypatch.setattr(C.trainer, 'UNet', FakeNet)
+    tr.model, tr.device, tr.consolidation, tr.c_loss = FakeNet(5, 3, 8), torch.device('cpu'), None, C.CrossEntropyLoss()
+    tr.begin_task2(3, distill_lambda=0, pod_lambda=0.5, pod_levels=2)
+    assert isinstance(tr.pod, C.LocalPODLoss) and tr.pod_channels == 3 and tr.distill is None and tr.pseudo is None
+    assert (tr.pod.levels, tr.pod.square, tr.pod.normalize, tr.pod.lam) == (2, False, True, 0.5)
+    tr.begin_task2(3, distill_lambda=1.0, pod_lambda=0.25)                       # beside output distillation; default levels
+    assert tr.pod.levels == 3 and tr.pod.lam == 0.25 and isinstance(tr.distill, C.DistillationCrossEntropy)
+    tr.begin_task2(3, distill_lambda=0, pod_lambda=0.0, pod_levels=7)            # off: pod_levels is not looked at, nothing is kept
+    assert tr.pod is None
+
+
+# ------------------------------------------------------------------------------- the cases of tests/test_pod_gpu.py and their bound
+# (name, B, Ca, Cb, C, H, W, levels, merge flags to run, storage offset of a in floats).  What each is there for: test_pod_gpu.py.
+CASES = [
+    ('4x4', 2, 3, 3, 3, 4, 4, 3, (False,), 0),
+    ('8x12', 2, 3, 3, 3, 8, 12, 3, (False,), 0),
+    ('12x8', 2, 3, 3, 3, 12, 8, 3, (False,), 0),
+    ('16x20', 2, 3, 3, 3, 16, 20, 3, (False,), 0),
+    ('6x6-l2', 2, 3, 3, 3, 6, 6, 2, (False,), 0),
+    ('5x7-l1', 2, 3, 3, 3, 5, 7, 1, (False,), 0),
+    ('8x12-offset', 2, 3, 3, 3, 8, 12, 3, (False,), 1),
+    ('8x16-offset', 2, 5, 3, 3, 8, 16, 3, (True,), 1),
+    ('8x16-l2', 2, 3, 3, 3, 8, 16, 2, (False,), 0),
+    ('16x32', 2, 4, 3, 2, 16, 32, 3, (False, True), 0),
+    ('b1', 1, 3, 3, 3, 8, 12, 3, (False,), 0),
+    ('b3', 3, 3, 3, 3, 8, 12, 3, (False,), 0),
+    ('c1', 2, 3, 3, 1, 8, 12, 3, (False, True), 0),
+    ('ca=c+2', 2, 5, 3, 3, 8, 12, 3, (False, True), 0),
+    ('cb=c+3', 2, 3, 6, 3, 8, 12, 3, (False,), 0),
+    ('k21-23', 2, 23, 21, 21, 64, 96, 3, (True,), 0),
+    ('4x2048', 1, 2, 1, 1, 4, 2048, 3, (True,), 0),
+    ('4x1032', 1, 1, 1, 1, 4, 1032, 3, (False,), 0),
+    ('2x261-l1', 1, 1, 1, 1, 2, 261, 1, (False,), 0),
+]
+FAMILIES = ['normal1', 'normal10', 'close']
+EPS = 2.0 ** -24
+# largest ratio of the float32 restatement (pod_closed_form on the float32 inputs, on the host) against the float64 one over CASES, every
+# flag combination: {family class: (d a, loss)}; test_fp32_restatement_stays_within_its_bound evaluates all of them again
+RESTATEMENT_MAX = {'independent': (14.2, 4.1), 'close': (4127.0, 302.6)}
+# ... times 4, rounded up to a power of two: (64, 32) and (32768, 2048)
+C_BOUND = {k: tuple(2.0 ** math.ceil(math.log2(4.0 * x)) for x in v) for k, v in RESTATEMENT_MAX.items()}
+
+
+def family_class(family):
+    return 'close' if family == 'close' else 'independent'
+
+
+def pod_inputs(case, family, merge):
+    """float32 host tensors a [B, Ca, H, W], b [B, Cb, H, W] of a case.  close: a's compared channels are b's plus 1e-3 noise (the merged
+    extras 1e-3 noise, so the merged background stays close as well)."""
+    name, B, Ca, Cb, C, H, W = case[:7]
+    g = torch.Generator().manual_seed(sum(map(ord, name + family)) + int(merge))
+    scale = 10.0 if family == 'normal10' else 1.0
+    a = torch.randn(B, Ca, H, W, generator=g) * scale
+    b = torch.randn(B, Cb, H, W, generator=g) * scale
+    if family == 'close':
+        noise = 1e-3 * torch.randn(B, Ca, H, W, generator=g)
+        a[:, :C] = b[:, :C] + noise[:, :C]
+        if merge:
+            a[:, C:] = noise[:, C:]
+    return a, b
+
+
+def pod_ratios(got_loss, got_da, ref_loss, ref_da):
+    """(max over the elements of |d a - ref| / (2^-24 max_n |ref|), |loss - ref| / (2^-24 |ref|)); an image (or a loss) whose reference is
+    exactly 0 must be exactly 0 (ratio 0, else inf)."""
+    B = ref_da.shape[0]
+    scale = ref_da.abs().reshape(B, -1).amax(1).reshape(B, 1, 1, 1)
+    err = (got_da.double() - ref_da).abs()
+    r = torch.where(scale > 0, err / (EPS * torch.where(scale > 0, scale, torch.ones_like(scale))),
+                    torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+    el = abs(float(got_loss) - float(ref_loss))
+    rl = el / (EPS * abs(float(ref_loss))) if float(ref_loss) != 0 else (0.0 if el == 0 else float('inf'))
+    return float(r.max()), rl
+
+
+def restatement_ratios():
+    """-> {family class: (largest d a ratio, largest loss ratio)} of the float32 restatement over CASES."""
+    worst = {'independent': [0.0, 0.0], 'close': [0.0, 0.0]}
+    for case in CASES:
+        levels = case[7]
+        for merge, family, square, normalize in itertools.product(case[8], FAMILIES, (False, True), (False, True)):
+            a, b = pod_inputs(case, family, merge)
+            l64, d64, _ = pod_closed_form(a.double(), b.double(), case[4], merge, square, normalize, levels, 0.7)
+            l32, d32, _ = pod_closed_form(a, b, case[4], merge, square, normalize, levels, 0.7)
+            assert bool(torch.isfinite(d32).all()) and math.isfinite(float(l32)), (case[0], family)
+            rd, rl = pod_ratios(l32, d32, l64, d64)
+            w = worst[family_class(family)]
+            w[0], w[1] = max(w[0], rd), max(w[1], rl)
+    return {k: tuple(v) for k, v in worst.items()}
+
+
+def test_fp32_restatement_stays_within_its_bound():
+    """The float32 restatement is finite on every case and no worse than the recorded maxima the GPU bound is derived from."""
+    got = restatement_ratios()
+    print('float32 restatement ratios (d a, loss):', got, 'recorded:', RESTATEMENT_MAX, 'bounds c:', C_BOUND)
+    for k, (rd, rl) in got.items():
+        assert rd <= RESTATEMENT_MAX[k][0] and rl <= RESTATEMENT_MAX[k][1], (k, rd, rl)
