@@ -131,6 +131,9 @@ SIGNATURES = {
     'clamd_ce_fwd_bwd_weighted': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
     'clamd_pod_workspace_bytes': (_SZ, [_I, _I, _I, _I, _I]),
     'clamd_local_pod_fwd_bwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _SZ, _I, _I, _I, _D, _P]),
+    'clamd_class_pixel_counts': (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _P]),
+    'clamd_replay_store': (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _LL, _P]),
+    'clamd_replay_mix': (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _LL, _P]),
     'clamd_adam_step': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     'clamd_adam_step_consolidated': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),

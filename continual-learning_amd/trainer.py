@@ -16,7 +16,8 @@ every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0
 Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
 of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
 confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`` adds Local POD distillation of the logits (build-defined,
-pod.py).
+pod.py); ``begin_task2(replay=M, replay_batch=R)`` keeps M exemplars of the finished task in an on-device memory and mixes R of them into
+every batch (build-defined, replay.py).
 """
 import os
 import warnings
@@ -32,6 +33,7 @@ from .optim import FusedAdam
 from .consolidate import Consolidation
 from .pseudo import PseudoLabeler
 from .pod import LocalPODLoss
+from .replay import ReplayMemory
 from . import syncbn
 from .unet import UNet
 
@@ -56,6 +58,9 @@ class Trainer:
         self.pod_channels = 0
         self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
         self.ewc_lambda = 0.0
+        self.replay = None                # replay.ReplayMemory once begin_task2(replay > 0) ran
+        self.replay_batch = 0             # exemplars mixed into every batch
+        self.replay_boundary = None       # c_old of the last call that added a segment: the next segment's first class
         self.build_model()
 
     def build_model(self):
@@ -105,7 +110,8 @@ class Trainer:
     def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
                     importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background',
                     pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None,
-                    pod_lambda=0.0, pod_levels=3):
+                    pod_lambda=0.0, pod_levels=3, replay=0, replay_batch=0, replay_loader=None, replay_storage='uint8', replay_flip=True,
+                    replay_min_pixels=1, replay_seed=0):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
         still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
@@ -127,7 +133,21 @@ class Trainer:
         step then runs the old model's forward, also with distill_lambda == 0 and without pseudo-labels, and adds
         pod(outputs, old, channels=c_old, merge_extra=True) to the criterion's loss -- the old background against the new background plus
         the new classes.  It combines with every criterion above; PLOP's step is begin_task2(c_old, distill_lambda=0, pseudo_label=True,
-        pseudo_adaptive=True, pod_lambda=...).  pod_lambda == 0 leaves the step as it is."""
+        pseudo_adaptive=True, pod_lambda=...).  pod_lambda == 0 leaves the step as it is.
+        Exemplar replay (build-defined, replay.py): replay > 0 adds a segment of that many slots to ``self.replay`` (a ReplayMemory with
+        replay_storage, replay_flip and replay_seed, created on first use) for the FINISHED task's own classes -- [1, c_old) on the first
+        call, [c_old of the previous such call, c_old) later -- and fills it from replay_loader (default: the training loader, with the
+        same meaning as importance_loader) by the class-balanced policy with replay_min_pixels, before the snapshot, the criterion switch
+        and the growing of the head.  Every step then starts with ``inputs, labels = self.replay.mix(inputs, labels, replay_batch)``
+        (replay_batch >= 1 is required): the old model's forward, the pseudo-labels, the distillation terms and the loss all see the
+        B + replay_batch rows, and so do the returned outputs; the caller's batch is rows [0, B).  replay == 0 leaves a memory from earlier
+        calls (and its replay_batch, unless a new one >= 1 is given) in place and adds nothing.  Data parallelism: each rank keeps its own
+        memory, filled from its own shard and sampled with replay_seed + rank; the gradients are averaged as always, no collective is
+        added."""
+        if replay < 0 or replay_batch < 0:
+            raise ValueError('replay and replay_batch must be >= 0')
+        if replay > 0 and replay_batch < 1:
+            raise ValueError('replay > 0 needs replay_batch >= 1 (the number of exemplars mixed into every batch)')
         if not pod_lambda >= 0:
             raise ValueError('pod_lambda must be >= 0')
         if pod_lambda > 0 and int(pod_levels) not in (1, 2, 3):
@@ -140,6 +160,11 @@ class Trainer:
         if pseudo_label and pseudo_adaptive and distill_lambda > 0:
             raise ValueError('pseudo_adaptive=True with distill_lambda > 0: DistillationCrossEntropy has no per-image weight '
                              '(use distill_lambda=0, or pseudo_adaptive=False)')
+        if replay > 0:
+            self._fill_replay(c_old, replay, self.train_data_loader if replay_loader is None else replay_loader, replay_storage, replay_flip,
+                              replay_min_pixels, replay_seed)
+        if replay_batch >= 1:
+            self.replay_batch = int(replay_batch)
         if ewc_lambda > 0:
             cons = self.estimate_importance(self.train_data_loader if importance_loader is None else importance_loader)
             cons.gamma = float(ewc_gamma)
@@ -178,6 +203,25 @@ class Trainer:
             for mod in m.modules():
                 if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
                     mod.eval()
+
+    def _fill_replay(self, c_old, capacity, loader, storage, flip, min_pixels, seed):
+        """One more segment of the exemplar memory for the classes [previous boundary or 1, c_old), filled from `loader`."""
+        lo = 1 if self.replay_boundary is None else self.replay_boundary
+        rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+        mem = self.replay
+        for images, masks in loader:
+            x, y = images.to(self.device, non_blocking=True), masks.to(self.device, non_blocking=True)
+            if mem is None:       # the image shape is the data's
+                mem = ReplayMemory(c_old, tuple(x.shape[1:]), storage=storage, ignore_index=self.c_loss.ignore_index, flip=flip,
+                                   seed=int(seed) + rank)
+            if mem.open is None:
+                mem.num_classes = max(mem.num_classes, int(c_old))      # the head has grown since the memory was created
+                mem.add_task((lo, c_old), capacity, min_pixels)
+            mem.observe(x, y)
+        if mem is None or mem.open is None:
+            raise ValueError('begin_task2(replay > 0): the replay loader gave no batch')
+        self.replay = mem.finish()
+        self.replay_boundary = int(c_old)
 
     def grow_head(self, n, init='background'):
         """UNet.expand_classes on the trained model with the optimiser state, the anchors and the consolidation carried over; cfg.num_classes
@@ -235,18 +279,26 @@ class Trainer:
                 cons_host = {'anchor': {n: t.to('cpu', non_blocking=True) for n, t in cs['anchor'].items()},
                              'importance': {n: t.to('cpu', non_blocking=True) for n, t in cs['importance'].items()},
                              'lambda': self.ewc_lambda, 'gamma': cs['gamma'], 'n_batches': cs['n_batches']}
+            replay_host = None
+            if self.replay is not None:              # a second optional key
+                rs = self.replay.state_dict()
+                replay_host = {k: (v.to('cpu', non_blocking=True) if torch.is_tensor(v) and v.is_cuda else v) for k, v in rs.items()}
+                replay_host.update(batch=self.replay_batch, boundary=self.replay_boundary)
             done = torch.cuda.Event()
             done.record(st)
         snap = {'epoch': epoch + 1, 'model_state': host, 'optimizer_state': opt_host,
                 'scheduler_state': self.scheduler.state_dict(), '_event': done}
         if cons_host is not None:
             snap['consolidation_state'] = cons_host
+        if replay_host is not None:
+            snap['replay_state'] = replay_host
         return snap
 
     def save_network(self, network_label, epoch_label, epoch, save_dir):
         """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/
         scheduler_state (loadable by the reference's load_network and by torch.optim.Adam); with elastic weight consolidation
-        active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores."""
+        active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores; with an exemplar memory
+        replay_state (ReplayMemory.state_dict() on the host, replay_batch and the class boundary), ignored by the reference too."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -265,7 +317,17 @@ class Trainer:
         self.optim.load_state_dict(ck['optimizer_state'])
         self.scheduler.load_state_dict(ck['scheduler_state'])
         self.load_consolidation_state(ck.get('consolidation_state'))
+        self.load_replay_state(ck.get('replay_state'))
         return True
+
+    def load_replay_state(self, state):
+        """Restores what snapshot() stored under 'replay_state' (None, e.g. a checkpoint without the key: nothing changes)."""
+        if state is None:
+            return
+        mem = ReplayMemory(state['num_classes'], state['image_shape'], storage=state['storage'], ignore_index=state['ignore_index'],
+                           flip=state['flip'], seed=state['seed'])
+        self.replay = mem.load_state_dict(state, device=self.device)
+        self.replay_batch, self.replay_boundary = int(state['batch']), state['boundary']
 
     def load_consolidation_state(self, state):
         """Restores what snapshot() stored under 'consolidation_state' (None, e.g. a checkpoint without the key: nothing changes)."""
@@ -277,7 +339,10 @@ class Trainer:
         self._apply_consolidation()
 
     def train_step(self, inputs, labels):
-        """trainer.py:172-176."""
+        """trainer.py:172-176.  With an exemplar memory the batch is first extended by replay_batch exemplars: everything below, and the
+        returned outputs, cover B + replay_batch rows, the caller's batch being rows [0, B)."""
+        if self.replay is not None and self.replay_batch > 0:
+            inputs, labels = self.replay.mix(inputs, labels, self.replay_batch)
         outputs = self.model(inputs)
         self.reset_grad()
         distill = getattr(self, 'distill', None) if self.old_model is not None else None
@@ -327,7 +392,10 @@ class Trainer:
             labels = masks.to(self.device, non_blocking=True)
             outputs, loss = self.train_step(inputs, labels)
             if i % self.cfg.stats_every == 0:
-                c, _ = argmax_confusion(outputs.detach(), labels, self.cfg.num_classes)
+                out = outputs.detach()
+                if out.shape[0] != labels.shape[0]:      # replayed rows behind the caller's batch
+                    out = out[:labels.shape[0]]
+                c, _ = argmax_confusion(out, labels, self.cfg.num_classes)
                 conf = c if conf is None else conf + c
                 losses.append(loss.detach())
         stats = {}

@@ -466,6 +466,44 @@ size_t clamd_pod_workspace_bytes(int B, int C, int H, int W, int levels);
 int clamd_local_pod_fwd_bwd(const float* a, int Ca, const float* b, int Cb, int C, int merge_extra, int square, int normalize,
                             int levels, double lam, float* da, float* loss1, void* workspace, size_t ws_bytes,
                             int B, int H, int W, double grad_scale, void* stream);
+/* ---- exemplar replay (replay.hip) ----------------------------------------------------------------------------
+ * Build-defined, parity unpinned (the reference has no continual-learning code): rehearsal -- a small on-device memory of exemplars from
+ * finished tasks, mixed into every batch of the new task.  Which image goes to which slot is the host's policy (replay.assign_slots); the
+ * three entries count, store and assemble.  Notation: K = number of classes, 1 <= K <= 255; ign = ignore_index; images fp32 NCHW
+ * [B, C, H, W], labels int64 [B, H, W]; the store holds `cap` slots: store_images [cap, C, H, W] as uint8 (store_fp32 == 0) or fp32
+ * (store_fp32 == 1), store_labels uint8 [cap, H, W].
+ * Stored label: ign -> 255; a label in [0, K) -> itself; anything else -> 255 and counted in *bad.  Read back: 255 -> ign, else itself.
+ * Stored uint8 pixel, in fp32 arithmetic: u = clamp(rintf((x * 0.5f + 0.5f) * 255.f), 0, 255) (round to nearest even; a NaN gives 0).
+ *   Read back with clamd_voc_prepare's arithmetic: v = (float)u / 255.f; x = (v - 0.5f) / 0.5f.  encode(decode(u)) == u for every byte, so
+ *   an image that came from clamd_voc_prepare survives the store bit for bit; any other x in [-1, 1] comes back within 1 / 255 (half a
+ *   quantisation step in x units).  fp32 storage copies the bits.
+ * clamd_class_pixel_counts: counts = int [B][K], cleared by the entry point itself; counts[b][k] = number of pixels of image b with label
+ *   k.  Labels equal to ign are skipped; any other label outside [0, K) is skipped and ADDED to *bad (unsigned int [1], the caller zeroes
+ *   it).  A workgroup takes (image, chunk of pixels) jobs with a histogram in LDS and adds it to the image's row with integer atomics: the
+ *   result does not depend on the order.  32-byte label loads when H * W % 4 == 0 and labels is 32-byte aligned, one label per load else.
+ * clamd_replay_store: store slot slot[r] = batch image src[r] (pixels and labels, encoded as above) for r in [0, n); src and slot are DEVICE
+ *   int [n], 1 <= n <= cap.  The slots of one call must be distinct (two rows writing one slot would interleave), which the host checks
+ *   before the launch along with 0 <= src[r] < B and 0 <= slot[r] < cap; the kernel moves nothing for an r that violates the ranges and adds
+ *   1 to *bad for it.  *bad also takes the labels that were neither ign nor in [0, K).  The images and labels are not modified.
+ * clamd_replay_mix: out_images [B + R, C, H, W], out_labels [B + R, H, W].  Rows [0, B) are bit-copies of cur_images / cur_labels.  Row
+ *   B + r is exemplar slots[r] (DEVICE long long [R]) read back as above and flipped by flips[r] (DEVICE int [R], or NULL for no flips):
+ *   bit 0 reverses W, bit 1 reverses H, for the image and the labels alike.  A slot outside [0, cap) gives a zero image and all-ign labels
+ *   and adds 1 to *bad: a guard, not an expected path.  B == 0 with NULL cur_images / cur_labels is the plain gather; R == 0 the plain
+ *   copy; B + R >= 1.  out must not overlap any input.
+ * The two copies: a lane handles four consecutive pixels (one 4-byte access per uint8 channel, 16 bytes per fp32 channel, two 16-byte label
+ *   accesses; a W flip reverses the four pixels inside the lane and mirrors the group index) when W % 4 == 0 and the bases are aligned --
+ *   fp32 tensors 16 bytes, int64 labels 32 bytes, uint8 tensors 4 bytes --; a one-pixel variant of the same arithmetic inside the same entry
+ *   point for any other width or alignment (fp32 needs 4, int64 8 bytes at least).
+ * All three: enqueue only, no allocation, no host synchronisation, device taken from the stream; integer atomics only, no float atomics:
+ * bit-reproducible. */
+int clamd_class_pixel_counts(const long long* labels, int* counts, unsigned int* bad, int B, int K, int H, int W, long long ignore_index,
+                             void* stream);
+int clamd_replay_store(const float* images, const long long* labels, const int* src, const int* slot, int n, void* store_images,
+                       unsigned char* store_labels, int store_fp32, int cap, unsigned int* bad, int B, int C, int H, int W, int K,
+                       long long ignore_index, void* stream);
+int clamd_replay_mix(const float* cur_images, const long long* cur_labels, int B, const void* store_images, const unsigned char* store_labels,
+                     int store_fp32, int cap, const long long* slots, const int* flips, int R, float* out_images, long long* out_labels,
+                     unsigned int* bad, int C, int H, int W, long long ignore_index, void* stream);
 /* torch.optim.Adam.step over all parameters in one launch (trainer.py:108-110,176); hyper/step/derived live on the
  * device so a captured graph can be replayed with a new learning rate.  l2_accum_dev (optional, with the L2-to-old-weights
  * term): 1 + nchunks floats, [0] = sum ||theta - theta_old||^2 of this step, [1..] = per-workgroup partials added in a fixed
