@@ -887,6 +887,9 @@ int clamd_bn_finalize(const float* stats, int stat_rows, const float* gamma, con
                       int Cp, int C, double count, double momentum, double eps, long long* num_batches_tracked, void* stream) {
     if (Cp <= 0 || Cp % 8 || C > Cp) return clamd_fail("bn_finalize: bad channel counts");
     if (stats && stat_rows <= 0) return clamd_fail("bn_finalize: stat_rows must be the row count the producing launch wrote");
+    if (!scale || !shift || !save_mean || !save_istd || (C > 0 && (!gamma || !beta))) return clamd_fail("bn_finalize: null argument");
+    if (!stats && C > 0 && (!running_mean || !running_var)) return clamd_fail("bn_finalize: eval mode (stats == NULL) needs the running statistics");
+    if (!running_mean != !running_var) return clamd_fail("bn_finalize: running_mean and running_var go together");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, (hipStream_t)stream, stats, stat_rows, gamma,
                        beta, running_mean, running_var, scale, shift, save_mean, save_istd, Cp, C, count, momentum, eps, num_batches_tracked);
     return clamd_check_launch("bn_finalize");
@@ -920,7 +923,10 @@ int clamd_bn_finalize_total(const double* reduce, const float* gamma, const floa
 int clamd_bn_apply(const void* y, int y_ldc, const float* scale, const float* shift, void* out, int out_ldc,
                    void* pooled, int p_ldc, int B, int H, int W, int Cp, int dtype, void* stream) {
     if (!pow2_channels(Cp)) return clamd_fail("bn_apply: physical channels must be a power of two in [32,2048]");
+    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_apply: bad sizes");
     if (pooled && ((H | W) & 1)) return clamd_fail("bn_apply: pooling needs even H, W");
+    if (!y || !scale || !shift || !out) return clamd_fail("bn_apply: null argument");
+    if (y_ldc < Cp || out_ldc < Cp || (pooled && p_ldc < Cp)) return clamd_fail("bn_apply: pitches must be >= Cp");
     if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
     if (int e = clamd_check_split(dtype, out, out_ldc)) return e;
     if (int e = clamd_check_split(dtype, pooled, p_ldc)) return e;
@@ -975,6 +981,10 @@ int clamd_bn_bwd_reduce(const void* ga, int ga_ldc, const void* gp, int gp_ldc, 
                         int dtype, const clamd_tuning* tune, void* stream) {
     if (!pow2_channels(Cp)) return clamd_fail("bn_bwd_reduce: physical channels must be a power of two in [32,2048]");
     if (!gp && !ga) return clamd_fail("bn_bwd_reduce: no gradient source");
+    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_reduce: bad sizes");
+    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_reduce: pooling needs even H, W");
+    if (!y || !sums || (gp && (!scale || !shift))) return clamd_fail("bn_bwd_reduce: null argument");
+    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp) return clamd_fail("bn_bwd_reduce: pitches must be >= Cp");
     if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
     if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
     if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
@@ -998,6 +1008,7 @@ int clamd_bn_bwd_finalize(const float* sums, int sum_rows, const float* gamma, c
                           void* stream) {
     if (Cp <= 0 || Cp % 8 || C > Cp) return clamd_fail("bn_bwd_finalize: bad channel counts");
     if (sum_rows <= 0) return clamd_fail("bn_bwd_finalize: sum_rows must be the row count the producing launch wrote");
+    if (!sums || !save_mean || !save_istd || !k012 || (C > 0 && (!gamma || !dgamma || !dbeta))) return clamd_fail("bn_bwd_finalize: null argument");
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, (hipStream_t)stream, sums, sum_rows,
                        gamma, save_mean, save_istd, k012, dgamma, dbeta, dbias, Cp, C, count);
     return clamd_check_launch("bn_bwd_finalize");
@@ -1017,6 +1028,11 @@ int clamd_bn_bwd_apply(const void* ga, int ga_ldc, const void* gp, int gp_ldc, c
                        const float* scale, const float* shift, const float* k012, void* gz, int gz_ldc, int B,
                        int H, int W, int Cp, int dtype, void* stream) {
     if (!pow2_channels(Cp)) return clamd_fail("bn_bwd_apply: physical channels must be a power of two in [32,2048]");
+    if (!gp && !ga) return clamd_fail("bn_bwd_apply: no gradient source");
+    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_apply: bad sizes");
+    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_apply: pooling needs even H, W");
+    if (!y || !k012 || !gz || (gp && (!scale || !shift))) return clamd_fail("bn_bwd_apply: null argument");
+    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp || gz_ldc < Cp) return clamd_fail("bn_bwd_apply: pitches must be >= Cp");
     if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
     if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
     if (int e = clamd_check_split(dtype, y, y_ldc)) return e;

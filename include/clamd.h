@@ -271,7 +271,12 @@ int clamd_wgrad(int mode, const void* a, int a_ldc, const void* b, int b_ldc, fl
  * nn.BatchNorm2d train mode (unet.py:15): partial rows stats[stat_rows][2][Cp] -> scale/shift (+ running stats,
  * momentum 0.1, unbiased var); rows are added in a fixed order in fp64, mean/variance formed in fp64.
  * stats == NULL: eval mode, normalise with the running statistics.  num_batches_tracked (optional, int64 scalar): nn.BatchNorm2d's
- * counter, incremented in train mode (stats != NULL). */
+ * counter, incremented in train mode (stats != NULL).
+ * Checked on the host, before any launch (status -1, clamd_last_error() names the check), for clamd_bn_finalize, clamd_bn_apply,
+ * clamd_bn_bwd_reduce, clamd_bn_bwd_finalize and clamd_bn_bwd_apply: every pointer the selected kernel reads or writes is non-NULL, every
+ * pitch of a tensor that is passed is >= Cp, B, H, W > 0, pooling has even H and W.  Optional (may be NULL): stats (eval mode, which then
+ * needs running_mean and running_var), running_mean / running_var in train mode (both or neither), num_batches_tracked, pooled, gp, ga
+ * where gp is given, dbias, and scale / shift of the backward launches without gp. */
 int clamd_bn_finalize(const float* stats, int stat_rows, const float* gamma, const float* beta, float* running_mean,
                       float* running_var, float* scale, float* shift, float* save_mean, float* save_istd,
                       int Cp, int C, double count, double momentum, double eps, long long* num_batches_tracked, void* stream);

@@ -269,6 +269,93 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
         assert needle in lib.clamd_last_error().decode()
 
 
+def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):
+    """clamd_bn_finalize / _apply / _bwd_reduce / _bwd_finalize / _bwd_apply: a null pointer the selected kernel would dereference, a pitch
+    below Cp, a non-positive B / H / W are refused by a host check -- status -1 (clamd_fail) and that check's message, never -2 (a launch
+    that was tried).  The optional pointers stay optional: those calls are not made here, the GPU suite makes them."""
+    import ctypes
+    lib = C._lib.load()
+    p = ctypes.c_void_p(0x1000)          # never dereferenced: every case below fails its checks on the host
+
+    def refused(name, needle, order, base, **kw):
+        a = dict(base)
+        a.update(kw)
+        rc = getattr(lib, name)(*[a[k] for k in order])
+        msg = lib.clamd_last_error().decode()
+        assert rc == -1 and msg.startswith(name[len('clamd_'):] + ': ') and needle in msg, (name, kw, rc, msg)
+
+    fin = 'stats stat_rows gamma beta running_mean running_var scale shift save_mean save_istd Cp C count momentum eps nbt stream'.split()
+    base = dict(stats=p, stat_rows=4, gamma=p, beta=p, running_mean=p, running_var=p, scale=p, shift=p, save_mean=p, save_istd=p, Cp=64, C=60,
+                count=8.0, momentum=0.1, eps=1e-5, nbt=None, stream=None)
+    for k in ('gamma', 'beta', 'scale', 'shift', 'save_mean', 'save_istd'):
+        refused('clamd_bn_finalize', 'null argument', fin, base, **{k: None})
+    refused('clamd_bn_finalize', 'running_mean and running_var go together', fin, base, running_var=None)
+    refused('clamd_bn_finalize', 'running_mean and running_var go together', fin, base, running_mean=None)
+    refused('clamd_bn_finalize', 'needs the running statistics', fin, base, stats=None, stat_rows=0, running_mean=None, running_var=None)
+    refused('clamd_bn_finalize', 'bad channel counts', fin, base, Cp=60)
+    refused('clamd_bn_finalize', 'bad channel counts', fin, base, C=65)
+
+    app = 'y y_ldc scale shift out out_ldc pooled p_ldc B H W Cp dtype stream'.split()
+    base = dict(y=p, y_ldc=64, scale=p, shift=p, out=p, out_ldc=128, pooled=None, p_ldc=0, B=2, H=8, W=6, Cp=64, dtype=0, stream=None)
+    for k in ('y', 'scale', 'shift', 'out'):
+        refused('clamd_bn_apply', 'null argument', app, base, **{k: None})
+        refused('clamd_bn_apply', 'null argument', app, base, pooled=p, p_ldc=64, **{k: None})
+    for kw in (dict(y_ldc=56), dict(out_ldc=32), dict(out_ldc=0), dict(pooled=p, p_ldc=32), dict(y_ldc=-64)):
+        refused('clamd_bn_apply', 'pitches must be >= Cp', app, base, **kw)
+    for kw in (dict(B=0), dict(H=0), dict(W=-2), dict(B=-1, pooled=p, p_ldc=64)):
+        refused('clamd_bn_apply', 'bad sizes', app, base, **kw)
+    refused('clamd_bn_apply', 'pooling needs even H, W', app, base, pooled=p, p_ldc=64, W=7)
+    refused('clamd_bn_apply', 'power of two', app, base, Cp=48)
+    refused('clamd_bn_apply', 'bad dtype', app, base, dtype=5)
+
+    red = 'ga ga_ldc gp gp_ldc y y_ldc scale shift sums sum_rows B H W Cp dtype tune stream'.split()
+    rows = lib.clamd_stat_rows(C._lib.OP_BN_BWD_REDUCE, 2, 8, 6, 0, 64, 0, 0, None)
+    rows_p = lib.clamd_stat_rows(C._lib.OP_BN_BWD_REDUCE, 2, 8, 6, 1, 64, 0, 0, None)
+    assert rows > 0 and rows_p > 0
+    base = dict(ga=p, ga_ldc=64, gp=None, gp_ldc=0, y=p, y_ldc=64, scale=None, shift=None, sums=p, sum_rows=rows, B=2, H=8, W=6, Cp=64, dtype=0,
+                tune=None, stream=None)
+    pooled = dict(gp=p, gp_ldc=64, scale=p, shift=p, sum_rows=rows_p)
+    refused('clamd_bn_bwd_reduce', 'no gradient source', red, base, ga=None)
+    for k in ('y', 'sums'):
+        refused('clamd_bn_bwd_reduce', 'null argument', red, base, **{k: None})
+        refused('clamd_bn_bwd_reduce', 'null argument', red, base, **{**pooled, k: None})
+    for k in ('scale', 'shift'):                                       # read by the pooled kernel only
+        refused('clamd_bn_bwd_reduce', 'null argument', red, base, **{**pooled, k: None})
+    for kw in (dict(ga_ldc=32), dict(y_ldc=63), {**pooled, 'gp_ldc': 32}, {**pooled, 'ga_ldc': 8}):
+        refused('clamd_bn_bwd_reduce', 'pitches must be >= Cp', red, base, **kw)
+    for kw in (dict(B=0), dict(H=-8), dict(W=0)):
+        refused('clamd_bn_bwd_reduce', 'bad sizes', red, base, **kw)
+    refused('clamd_bn_bwd_reduce', 'pooling needs even H, W', red, base, **{**pooled, 'H': 7})
+    refused('clamd_bn_bwd_reduce', 'sum_rows does not match', red, base, sum_rows=rows + 1)
+    refused('clamd_bn_bwd_reduce', 'bad dtype', red, base, dtype=3)
+
+    bfin = 'sums sum_rows gamma save_mean save_istd k012 dgamma dbeta dbias Cp C count stream'.split()
+    base = dict(sums=p, sum_rows=4, gamma=p, save_mean=p, save_istd=p, k012=p, dgamma=p, dbeta=p, dbias=None, Cp=64, C=60, count=8.0, stream=None)
+    for k in ('sums', 'gamma', 'save_mean', 'save_istd', 'k012', 'dgamma', 'dbeta'):
+        refused('clamd_bn_bwd_finalize', 'null argument', bfin, base, **{k: None})
+        refused('clamd_bn_bwd_finalize', 'null argument', bfin, base, dbias=p, **{k: None})
+    refused('clamd_bn_bwd_finalize', 'sum_rows must be', bfin, base, sum_rows=0)
+    refused('clamd_bn_bwd_finalize', 'bad channel counts', bfin, base, Cp=60)
+    refused('clamd_bn_bwd_finalize', 'bad channel counts', bfin, base, C=65)
+
+    bapp = 'ga ga_ldc gp gp_ldc y y_ldc scale shift k012 gz gz_ldc B H W Cp dtype stream'.split()
+    base = dict(ga=p, ga_ldc=64, gp=None, gp_ldc=0, y=p, y_ldc=64, scale=None, shift=None, k012=p, gz=p, gz_ldc=64, B=2, H=8, W=6, Cp=64, dtype=0,
+                stream=None)
+    pooled = dict(gp=p, gp_ldc=64, scale=p, shift=p)
+    refused('clamd_bn_bwd_apply', 'no gradient source', bapp, base, ga=None)
+    for k in ('y', 'k012', 'gz'):
+        refused('clamd_bn_bwd_apply', 'null argument', bapp, base, **{k: None})
+        refused('clamd_bn_bwd_apply', 'null argument', bapp, base, **{**pooled, k: None})
+    for k in ('scale', 'shift'):
+        refused('clamd_bn_bwd_apply', 'null argument', bapp, base, **{**pooled, k: None})
+    for kw in (dict(ga_ldc=32), dict(y_ldc=0), dict(gz_ldc=56), {**pooled, 'gp_ldc': 32}):
+        refused('clamd_bn_bwd_apply', 'pitches must be >= Cp', bapp, base, **kw)
+    for kw in (dict(B=0), dict(H=0), dict(W=-1)):
+        refused('clamd_bn_bwd_apply', 'bad sizes', bapp, base, **kw)
+    refused('clamd_bn_bwd_apply', 'pooling needs even H, W', bapp, base, **{**pooled, 'W': 5})
+    refused('clamd_bn_bwd_apply', 'bad dtype', bapp, base, dtype=-1)
+
+
 def test_bf16x3_plane_layout_helpers_roundtrip():
     """ops.split_encode / split_decode (host-side mirror of csrc/common.hip.h Vec8<split_t>): per 16-channel group 16 bf16 hi then 16
     bf16 lo in the bytes of the fp32 tensor; hi = rne_bf16(x), hi + lo reproduces x to ~2^-17 and is a fixed point of decode(encode(.)); a

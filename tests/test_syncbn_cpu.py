@@ -112,16 +112,27 @@ def test_sync_entry_points_exported_declared_and_bound(C):
 
 
 def test_sync_launchers_reject_bad_arguments_before_launching(C):
+    """Every case is refused by a host check: status -1 (clamd_fail) with that check's own message.  A case that passed the checks would
+    return -2 from the failed launch on a machine without a device, and fails here instead of reaching a kernel where there is one."""
     lib = C._lib.load()
     p = ctypes.c_void_p(0x1000)          # never dereferenced: every case below fails its checks on the host
-    for rows, nrows, nk, Cp, count, tot, red in [(p, 4, 3, 64, 8., p, p), (p, 4, 4, 64, 8., p, p), (p, 0, 2, 64, 8., p, p),
-                                                 (None, 4, 2, 64, 8., p, p), (p, 4, 2, 60, 8., p, p), (p, 4, 5, 64, 8., None, None),
-                                                 (p, 4, 2, 64, 0., None, p)]:
-        assert lib.clamd_bn_rows_total(rows, nrows, nk, Cp, count, tot, red, None) != 0, (nk, nrows, Cp, count)
-        assert 'bn_rows_total' in lib.clamd_last_error().decode()
-    for red, Cp, C_, rm, rv in [(None, 64, 64, p, p), (p, 60, 60, p, p), (p, 64, 65, p, p), (p, 64, 0, p, p), (p, 64, 64, p, None)]:
-        assert lib.clamd_bn_finalize_total(red, p, p, rm, rv, p, p, p, p, Cp, C_, 0.1, 1e-5, None, None) != 0, (Cp, C_)
-        assert 'bn_finalize_total' in lib.clamd_last_error().decode()
-    for tot, red, Cp, C_ in [(None, p, 64, 64), (p, None, 64, 64), (p, p, 48, 48), (p, p, 64, 65)]:
-        assert lib.clamd_bn_bwd_finalize_total(tot, red, p, p, p, p, p, p, None, Cp, C_, None) != 0, (Cp, C_)
-        assert 'bn_bwd_finalize_total' in lib.clamd_last_error().decode()
+
+    def refused(name, needle, *args):
+        rc = getattr(lib, name)(*args)
+        msg = lib.clamd_last_error().decode()
+        assert rc == -1 and msg.startswith(name[len('clamd_'):] + ': ') and needle in msg, (name, args, rc, msg)
+
+    for needle, rows, nrows, nk, Cp, count, tot, red in [('nk must be', p, 4, 3, 64, 8., p, p), ('nk must be', p, 4, 4, 64, 8., p, p),
+                                                         ('nrows must be', p, 0, 2, 64, 8., p, p), ('nrows must be', None, 4, 2, 64, 8., p, p),
+                                                         ('bad channel count', p, 4, 2, 60, 8., p, p),
+                                                         ('nothing to write', p, 4, 5, 64, 8., None, None),
+                                                         ('count must be positive', p, 4, 2, 64, 0., None, p)]:
+        refused('clamd_bn_rows_total', needle, rows, nrows, nk, Cp, count, tot, red, None)
+    for needle, red, Cp, C_, rm, rv in [('null argument', None, 64, 64, p, p), ('bad channel counts', p, 60, 60, p, p),
+                                        ('bad channel counts', p, 64, 65, p, p), ('bad channel counts', p, 64, 0, p, p),
+                                        ('running_mean and running_var go together', p, 64, 64, p, None)]:
+        refused('clamd_bn_finalize_total', needle, red, p, p, rm, rv, p, p, p, p, Cp, C_, 0.1, 1e-5, None, None)
+    # Cp = 48 is no case: the kernel is right for every multiple of 8 and the launcher takes it
+    for needle, tot, red, Cp, C_ in [('null argument', None, p, 64, 64), ('null argument', p, None, 64, 64), ('bad channel counts', p, p, 60, 60),
+                                     ('bad channel counts', p, p, 64, 65)]:
+        refused('clamd_bn_bwd_finalize_total', needle, tot, red, p, p, p, p, p, p, None, Cp, C_, None)
