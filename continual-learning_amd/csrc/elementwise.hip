@@ -3,6 +3,8 @@
 // (+ fused max-pool backward routing), layout conversion, per-channel sums.
 // All activations are NHWC with an explicit channel pitch (ldc) so a tensor can be a channel slice of a
 // concat buffer; every thread moves 8 channels (16 B bf16 / 32 B f32) per pixel, lanes along channels first.
+#include <initializer_list>
+#include <type_traits>
 #include "common.hip.h"
 #include "clamd_internal.h"
 
@@ -132,6 +134,55 @@ __global__ void __launch_bounds__(256) bn_finalize_total_kernel(const double* __
 }
 
 // ------------------------------------------------------------------------------------------------
+// Pieces shared by the streaming passes below.
+// The 2x2 window of pooled pixel `pix` in a [B][H][W] image: at(q), q = 0..3 row-major, is the pixel index of its q-th member.
+struct PoolWindow {
+    int b, py, px, H, W;
+    __device__ PoolWindow(long long pix, int H_, int W_) : H(H_), W(W_) {
+        const int w2 = W / 2, h2 = H / 2;
+        px = (int)(pix % w2); py = (int)((pix / w2) % h2); b = (int)(pix / ((long long)w2 * h2));
+    }
+    __device__ long long at(int q) const { return ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1); }
+    __device__ long long cell() const { return ((long long)b * (H / 2) + py) * (W / 2) + px; }      // = pix
+};
+
+// Block reduction of NS sum kinds over the threads that share a channel group (tid = r * G + cg, r = 0..rows-1): this workgroup's
+// partial row dst[NS][Cp].  One sum kind at a time through red[256 * 8]; channel c's contributions live at red[(r*G + c/8)*8 + c%8]
+// and are added in ascending r, so a row depends only on the data: deterministic, no atomics.
+template <int NS>
+__device__ inline void reduce_block_rows(const float (&acc)[NS][8], float* red, float* dst, int G, int Cp, int rows) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s) __syncthreads();                     // red is reused
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[s][j];
+        __syncthreads();
+        for (int c = tid; c < Cp; c += 256) {
+            const int g8 = c >> 3, j = c & 7;
+            float t = 0.f;
+            for (int r = 0; r < rows; ++r) t += red[(r * G + g8) * 8 + j];
+            dst[s * Cp + c] = t;
+        }
+    }
+}
+
+// The two-pixels-per-trip load of the unpooled reductions: pixel `pix` and, where there is one, the pixel one grid stride on (returns
+// whether; pix1 = its index, else pix) -- four 16-byte loads in flight per thread instead of two, which brought bf16 storage from
+// 3.0 TB/s to the rate of the 4-byte dtypes (whose Vec8 loads are two instructions each).  The callers add the terms of g[0] before those of g[1]: pixel order.
+template <typename T>
+__device__ inline bool load_pixel_pair(const T* ga, int ga_ldc, const T* y, int y_ldc, long long pix, long long stride, long long npix,
+                                       int cg, long long& pix1, float (&g)[2][8], float (&v)[2][8]) {
+    const bool two = pix + stride < npix;
+    pix1 = two ? pix + stride : pix;
+    Vec8<T>::load(ga + pix * ga_ldc + cg * 8, g[0]);
+    Vec8<T>::load(y + pix * y_ldc + cg * 8, v[0]);
+    Vec8<T>::load(ga + pix1 * ga_ldc + cg * 8, g[1]);
+    Vec8<T>::load(y + pix1 * y_ldc + cg * 8, v[1]);
+    return two;
+}
+
+// ------------------------------------------------------------------------------------------------
 // BN apply: out = y*scale + shift (written into `out` with its own pitch: possibly a concat slice), and
 // optionally pooled = max over the 2x2 window of `out` (nn.MaxPool2d(2,2), models/unet.py:12,80).
 template <typename T, bool POOL>
@@ -157,12 +208,11 @@ __global__ void bn_apply_kernel(const T* __restrict__ y, int y_ldc, const float*
             for (int j = 0; j < 8; ++j) v[j] = __fmaf_rn(v[j], sc[j], sh[j]);
             Vec8<T>::store(out + pix * out_ldc + cg * 8, v);
         } else {
-            const int w2 = W / 2, h2 = H / 2;
-            const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
+            const PoolWindow win(pix, H, W);
             float m[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
+                const long long p = win.at(q);
                 float v[8];
                 Vec8<T>::load(y + p * y_ldc + cg * 8, v);
 #pragma unroll
@@ -188,12 +238,12 @@ __global__ void __launch_bounds__(256) maxpool2x2_kernel(const T* __restrict__ x
                                                         const T* __restrict__ gp, int gp_ldc, const float* __restrict__ sign,
                                                         int B, int H, int W, int Cp) {
     PASS_PRIO();
-    const int G = Cp >> 3, w2 = W / 2, h2 = H / 2;
-    const long long nitem = (long long)B * h2 * w2 * G;
+    const int G = Cp >> 3;
+    const long long nitem = (long long)B * (H / 2) * (W / 2) * G;
     for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < nitem; it += (long long)gridDim.x * blockDim.x) {
         const int cg = (int)(it % G);
         const long long pix = it / G;
-        const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
+        const PoolWindow win(pix, H, W);
         float m[8], v[4][8];
         int arg[8];
         bool neg[8];
@@ -201,8 +251,7 @@ __global__ void __launch_bounds__(256) maxpool2x2_kernel(const T* __restrict__ x
         for (int j = 0; j < 8; ++j) neg[j] = sign != nullptr && sign[cg * 8 + j] < 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
-            Vec8<T>::load(x + p * x_ldc + cg * 8, v[q]);
+            Vec8<T>::load(x + win.at(q) * x_ldc + cg * 8, v[q]);
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (q == 0 || (neg[j] ? v[q][j] < m[j] : v[q][j] > m[j])) { m[j] = v[q][j]; arg[j] = q; }
@@ -213,11 +262,10 @@ __global__ void __launch_bounds__(256) maxpool2x2_kernel(const T* __restrict__ x
             Vec8<T>::load(gp + pix * gp_ldc + cg * 8, g);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
                 float o[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = arg[j] == q ? g[j] : 0.f;
-                Vec8<T>::store(out + p * o_ldc + cg * 8, o);
+                Vec8<T>::store(out + win.at(q) * o_ldc + cg * 8, o);
             }
         }
     }
@@ -231,13 +279,13 @@ __global__ void __launch_bounds__(256) maxpool2x2_kernel(const T* __restrict__ x
 // The window arg-max is recomputed bit-identically to bn_apply_kernel (same fmaf, first max wins).
 template <typename T>
 __device__ inline void load_gu(const T* ga, int ga_ldc, const T* gp, int gp_ldc, const T* y, int y_ldc,
-                               const float (&sc)[8], const float (&sh)[8], int b, int py, int px, int H, int W,
+                               const float (&sc)[8], const float (&sh)[8], const PoolWindow& win,
                                int cg, float (&g)[4][8], float (&yy)[4][8]) {
     float best[8];
     int arg[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
+        const long long p = win.at(q);
         Vec8<T>::load(y + p * y_ldc + cg * 8, yy[q]);
         if (ga) Vec8<T>::load(ga + p * ga_ldc + cg * 8, g[q]);
         else {
@@ -251,8 +299,7 @@ __device__ inline void load_gu(const T* ga, int ga_ldc, const T* gp, int gp_ldc,
         }
     }
     float gpv[8];
-    const long long pp = ((long long)b * (H / 2) + py) * (W / 2) + px;
-    Vec8<T>::load(gp + pp * gp_ldc + cg * 8, gpv);
+    Vec8<T>::load(gp + win.cell() * gp_ldc + cg * 8, gpv);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -260,6 +307,16 @@ __device__ inline void load_gu(const T* ga, int ga_ldc, const T* gp, int gp_ldc,
 }
 
 constexpr int NSUM = 5;
+
+// one pixel's terms of s0..s4 for the thread's 8 channels
+__device__ inline void add_five_sums(float (&acc)[NSUM][8], const float (&g)[8], const float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float pos = v[j] > 0.f ? 1.f : 0.f;
+        acc[0][j] += g[j]; acc[1][j] += g[j] * v[j]; acc[2][j] += g[j] * pos;
+        acc[3][j] += pos; acc[4][j] += v[j];
+    }
+}
 
 template <typename T, bool POOL>
 __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict__ ga, int ga_ldc,
@@ -286,11 +343,14 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
             for (int j = 0; j < 8; ++j) { sc[j] = scale[cg * 8 + j]; sh[j] = shift[cg * 8 + j]; }
         }
         const long long npix = POOL ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
-        // !POOL: two pixels per trip -- four 16-byte loads in flight per thread instead of two (bf16 storage: 3.0 -> TB/s of the 4-byte
-        // dtypes, whose Vec8 loads are two instructions each); the terms are still added in pixel order
         const long long stride = (long long)gridDim.x * rows;
         for (long long pix = (long long)blockIdx.x * rows + prow; pix < npix; pix += POOL ? stride : 2 * stride) {
             if constexpr (!POOL) {
+                // This path keeps the pair load (load_pixel_pair), the five-sum step (add_five_sums) and, below, the block reduction
+                // (reduce_block_rows) in its own lines, instruction for instruction the code it had before those were shared: through
+                // them bn_bwd_reduce_kernel<bf16_t, false> measured 170.63 us per bf16 train step at 16 x 256 x 256 against 168.21 /
+                // 169.35 us in two runs of this form, and with only the reduction inline 171.15 against 168.99 / 170.42 -- both
+                // times past the difference of the two runs (72 VGPRs and 7 waves per SIMD in every form).
                 float g[2][8], v[2][8];
                 const bool two = pix + stride < npix;
                 const long long pix1 = two ? pix + stride : pix;
@@ -309,35 +369,29 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
                     }
                 }
             } else {
-                const int w2 = W / 2, h2 = H / 2;
-                const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
                 float g[4][8], v[4][8];
-                load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, b, py, px, H, W, cg, g, v);
+                load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, PoolWindow(pix, H, W), cg, g, v);
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float pos = v[q][j] > 0.f ? 1.f : 0.f;
-                        acc[0][j] += g[q][j]; acc[1][j] += g[q][j] * v[q][j]; acc[2][j] += g[q][j] * pos;
-                        acc[3][j] += pos; acc[4][j] += v[q][j];
-                    }
+                for (int q = 0; q < 4; ++q) add_five_sums(acc, g[q], v[q]);
             }
         }
     }
-    // block reduction over the threads that share a channel group, one sum kind at a time; this block's partial row
     float* dst = sums + (size_t)blockIdx.x * NSUM * Cp;
+    if constexpr (POOL) reduce_block_rows<NSUM>(acc, red, dst, G, Cp, rows);
+    else {
+        // reduce_block_rows<NSUM>, inline (see above)
 #pragma unroll
-    for (int s = 0; s < NSUM; ++s) {
-        __syncthreads();
+        for (int s = 0; s < NSUM; ++s) {
+            __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[s][j];
-        __syncthreads();
-        // channel c's contributions live at red[(r*G + c/8)*8 + c%8], r = 0..rows-1
-        for (int c = tid; c < Cp; c += 256) {
-            const int g8 = c >> 3, j = c & 7;
-            float t = 0.f;
-            for (int r = 0; r < rows; ++r) t += red[(r * G + g8) * 8 + j];
-            dst[s * Cp + c] = t;
+            for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[s][j];
+            __syncthreads();
+            for (int c = tid; c < Cp; c += 256) {
+                const int g8 = c >> 3, j = c & 7;
+                float t = 0.f;
+                for (int r = 0; r < rows; ++r) t += red[(r * G + g8) * 8 + j];
+                dst[s * Cp + c] = t;
+            }
         }
     }
 }
@@ -401,6 +455,19 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_total_kernel(const double
 // write the same bits
 __device__ inline float bn_bwd_gz(float k0, float k1, float k2, float g, float y) { return fmaf(k0, g, fmaf(k1, y, k2)); }
 
+// The gate around it, `y > 0 ? bn_bwd_gz(...) : 0`, stays spelled out at its three sites: behind a function of its own the compiler
+// forms the select earlier and allocates bn_bwd_apply_kernel / bn_bwd_apply_sums_kernel differently (VGPRs, spelled out -> helper:
+// plain apply 52 / 68 / 58 -> 62 / 62 / 68 for bf16 / fp32 / bf16x3, the last 8 -> 7 waves per SIMD; apply_sums fp32 74 -> 60, bf16x3
+// 72 -> 74 and 7 -> 6 waves; pooled apply scratch 88 / 108 / 108 -> 116 / 92 / 124 bytes per lane).
+
+// the coefficients k0, k1, k2 of a channel group
+__device__ inline void load_k012(const float* k012, int Cp, int cg, float (&k0)[8], float (&k1)[8], float (&k2)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        k0[j] = k012[cg * 8 + j]; k1[j] = k012[Cp + cg * 8 + j]; k2[j] = k012[2 * Cp + cg * 8 + j];
+    }
+}
+
 template <typename T, bool POOL>
 __global__ void bn_bwd_apply_kernel(const T* __restrict__ ga, int ga_ldc, const T* __restrict__ gp, int gp_ldc,
                                     const T* __restrict__ y, int y_ldc, const float* __restrict__ scale,
@@ -409,17 +476,14 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ ga, int ga_ldc, const 
     PASS_PRIO();
     const int G = Cp >> 3;
     const long long nitem = POOL ? (long long)B * (H / 2) * (W / 2) * G : (long long)B * H * W * G;
+    const long long it0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    float k0[8], k1[8], k2[8];
     if constexpr (!POOL) {
         // channel group fixed per thread (see bn_apply_kernel): k0, k1, k2 are loaded once, not per 16-byte item
         // (34 -> 27 us per launch in bf16).  The pooled variant below keeps them per item: hoisted, its 40 extra live
         // registers next to g[4][8], v[4][8] cost occupancy (62 -> 74 us).
-        const long long it0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
         const int cg = (int)(it0 % G);
-        float k0[8], k1[8], k2[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            k0[j] = k012[cg * 8 + j]; k1[j] = k012[Cp + cg * 8 + j]; k2[j] = k012[2 * Cp + cg * 8 + j];
-        }
+        load_k012(k012, Cp, cg, k0, k1, k2);
         for (long long it = it0; it < nitem; it += (long long)gridDim.x * blockDim.x) {
             const long long pix = it / G;
             float g[8], v[8];
@@ -429,39 +493,22 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ ga, int ga_ldc, const 
             for (int j = 0; j < 8; ++j) g[j] = v[j] > 0.f ? bn_bwd_gz(k0[j], k1[j], k2[j], g[j], v[j]) : 0.f;
             Vec8<T>::store(gz + pix * gz_ldc + cg * 8, g);
         }
-        return;
-    }
-    for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < nitem;
-         it += (long long)gridDim.x * blockDim.x) {
-        const int cg = (int)(it % G);
-        const long long pix = it / G;
-        float k0[8], k1[8], k2[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            k0[j] = k012[cg * 8 + j]; k1[j] = k012[Cp + cg * 8 + j]; k2[j] = k012[2 * Cp + cg * 8 + j];
-        }
-        if constexpr (!POOL) {
-            float g[8], v[8];
-            Vec8<T>::load(ga + pix * ga_ldc + cg * 8, g);
-            Vec8<T>::load(y + pix * y_ldc + cg * 8, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = v[j] > 0.f ? bn_bwd_gz(k0[j], k1[j], k2[j], g[j], v[j]) : 0.f;
-            Vec8<T>::store(gz + pix * gz_ldc + cg * 8, g);
-        } else {
+    } else {
+        for (long long it = it0; it < nitem; it += (long long)gridDim.x * blockDim.x) {
+            const int cg = (int)(it % G);
+            const long long pix = it / G;
+            load_k012(k012, Cp, cg, k0, k1, k2);
             float sc[8], sh[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { sc[j] = scale[cg * 8 + j]; sh[j] = shift[cg * 8 + j]; }
-            const int w2 = W / 2, h2 = H / 2;
-            const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
+            const PoolWindow win(pix, H, W);
             float g[4][8], v[4][8];
-            load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, b, py, px, H, W, cg, g, v);
+            load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, win, cg, g, v);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
 #pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    g[q][j] = v[q][j] > 0.f ? bn_bwd_gz(k0[j], k1[j], k2[j], g[q][j], v[q][j]) : 0.f;
-                Vec8<T>::store(gz + p * gz_ldc + cg * 8, g[q]);
+                for (int j = 0; j < 8; ++j) g[q][j] = v[q][j] > 0.f ? bn_bwd_gz(k0[j], k1[j], k2[j], g[q][j], v[q][j]) : 0.f;
+                Vec8<T>::store(gz + win.at(q) * gz_ldc + cg * 8, g[q]);
             }
         }
     }
@@ -471,23 +518,19 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ ga, int ga_ldc, const 
 // partial row per workgroup: the launches whose producing data-gradient kernel takes only sum g and sum g y (igemm_pws.hip, CLM = 3) get
 // the bias gradient here, where g_z exists anyway, instead of from three more running sums in the MFMA kernel's epilogue.
 // A thread's channel group is fixed (grid stride % G == 0: G is a power of two <= 256); the 256 / G threads of a group are added in
-// thread order through LDS: deterministic.
+// thread order through LDS (reduce_block_rows).
 template <typename T>
 __global__ void __launch_bounds__(256) bn_bwd_apply_sums_kernel(const T* __restrict__ ga, int ga_ldc, const T* __restrict__ y, int y_ldc,
                                                                 const float* __restrict__ k012, T* gz, int gz_ldc, float* rows,
                                                                 long long npix, int Cp) {
     PASS_PRIO();
     __shared__ float red[256 * 8];
-    const int G = Cp >> 3, tid = threadIdx.x;
+    const int G = Cp >> 3;
     const long long nitem = npix * G;
-    const long long it0 = (long long)blockIdx.x * 256 + tid;
+    const long long it0 = (long long)blockIdx.x * 256 + threadIdx.x;
     const int cg = (int)(it0 % G);
-    float k0[8], k1[8], k2[8], acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        k0[j] = k012[cg * 8 + j]; k1[j] = k012[Cp + cg * 8 + j]; k2[j] = k012[2 * Cp + cg * 8 + j];
-        acc[j] = 0.f;
-    }
+    float k0[8], k1[8], k2[8], acc[1][8] = {};
+    load_k012(k012, Cp, cg, k0, k1, k2);
     for (long long it = it0; it < nitem; it += (long long)gridDim.x * 256) {
         const long long pix = it / G;
         float g[8], v[8];
@@ -496,20 +539,11 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_sums_kernel(const T* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             g[j] = v[j] > 0.f ? bn_bwd_gz(k0[j], k1[j], k2[j], g[j], v[j]) : 0.f;
-            acc[j] += g[j];
+            acc[0][j] += g[j];
         }
         Vec8<T>::store(gz + pix * gz_ldc + cg * 8, g);
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[j];
-    __syncthreads();
-    const int per = 256 / G;                       // threads per channel group: tid = q * G + cg
-    for (int c = tid; c < Cp; c += 256) {
-        const int g8 = c >> 3, j = c & 7;
-        float t = 0.f;
-        for (int q = 0; q < per; ++q) t += red[(q * G + g8) * 8 + j];
-        rows[(size_t)blockIdx.x * Cp + c] = t;
-    }
+    reduce_block_rows<1>(acc, red, rows + (size_t)blockIdx.x * Cp, G, Cp, 256 / G);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -522,6 +556,17 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_sums_kernel(const T* __restr
 // bn_bwd_reduce_kernel (channel group cg = tid % G fixed per thread, 256 / G pixels per block trip); one partial row [3][Cp] per block,
 // the pixels of a block added in thread order through LDS: deterministic.
 constexpr int NSUM_EVAL = 3;
+
+// one pixel's terms of the three rows for the thread's 8 channels; its g_u becomes g_z in place.  The unpooled path calls it; the
+// pooled path keeps the same lines inline (bn_bwd_eval_kernel<bf16_t, true>: 160 VGPRs inline, 158 through this function).
+__device__ inline void add_eval_sums(float (&acc)[NSUM_EVAL][8], const float (&sc)[8], int nlive, float (&g)[8], const float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float o = (v[j] > 0.f && j < nlive) ? sc[j] * g[j] : 0.f;
+        acc[0][j] += g[j]; acc[1][j] += g[j] * v[j]; acc[2][j] += o;
+        g[j] = o;
+    }
+}
 
 template <typename T, bool POOL>
 __global__ void __launch_bounds__(256) bn_bwd_eval_kernel(const T* __restrict__ ga, int ga_ldc, const T* __restrict__ gp, int gp_ldc,
@@ -543,63 +588,38 @@ __global__ void __launch_bounds__(256) bn_bwd_eval_kernel(const T* __restrict__ 
     const long long npix = POOL ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
     const long long stride = (long long)gridDim.x * per;
     if constexpr (!POOL) {
-        // two pixels per trip, as bn_bwd_reduce_kernel: four 16-byte loads in flight per thread; the terms are added in pixel order
         for (long long pix = (long long)blockIdx.x * per + prow; pix < npix; pix += 2 * stride) {
             float g[2][8], v[2][8];
-            const bool two = pix + stride < npix;
-            const long long pix1 = two ? pix + stride : pix;
-            Vec8<T>::load(ga + pix * ga_ldc + cg * 8, g[0]);
-            Vec8<T>::load(y + pix * y_ldc + cg * 8, v[0]);
-            Vec8<T>::load(ga + pix1 * ga_ldc + cg * 8, g[1]);
-            Vec8<T>::load(y + pix1 * y_ldc + cg * 8, v[1]);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (u == 1 && !two) break;
-                float o[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    o[j] = (v[u][j] > 0.f && j < nlive) ? sc[j] * g[u][j] : 0.f;
-                    acc[0][j] += g[u][j]; acc[1][j] += g[u][j] * v[u][j]; acc[2][j] += o[j];
-                }
-                Vec8<T>::store(gz + (u ? pix1 : pix) * gz_ldc + cg * 8, o);
+            long long pix1;
+            const bool two = load_pixel_pair<T>(ga, ga_ldc, y, y_ldc, pix, stride, npix, cg, pix1, g, v);
+            add_eval_sums(acc, sc, nlive, g[0], v[0]);
+            Vec8<T>::store(gz + pix * gz_ldc + cg * 8, g[0]);
+            if (two) {
+                add_eval_sums(acc, sc, nlive, g[1], v[1]);
+                Vec8<T>::store(gz + pix1 * gz_ldc + cg * 8, g[1]);
             }
         }
     } else {
         float sh[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) sh[j] = shift[cg * 8 + j];
-        const int w2 = W / 2, h2 = H / 2;
         for (long long pix = (long long)blockIdx.x * per + prow; pix < npix; pix += stride) {
-            const int px = (int)(pix % w2), py = (int)((pix / w2) % h2), b = (int)(pix / ((long long)w2 * h2));
+            const PoolWindow win(pix, H, W);
             float g[4][8], v[4][8];
-            load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, b, py, px, H, W, cg, g, v);
+            load_gu<T>(ga, ga_ldc, gp, gp_ldc, y, y_ldc, sc, sh, win, cg, g, v);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const long long p = ((long long)b * H + 2 * py + (q >> 1)) * W + 2 * px + (q & 1);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float o = (v[q][j] > 0.f && j < nlive) ? sc[j] * g[q][j] : 0.f;
                     acc[0][j] += g[q][j]; acc[1][j] += g[q][j] * v[q][j]; acc[2][j] += o;
                     g[q][j] = o;
                 }
-                Vec8<T>::store(gz + p * gz_ldc + cg * 8, g[q]);
+                Vec8<T>::store(gz + win.at(q) * gz_ldc + cg * 8, g[q]);
             }
         }
     }
-    float* dst = rows + (size_t)blockIdx.x * NSUM_EVAL * Cp;
-#pragma unroll
-    for (int s = 0; s < NSUM_EVAL; ++s) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[s][j];
-        __syncthreads();
-        for (int c = tid; c < Cp; c += 256) {       // channel c's contributions: red[(r*G + c/8)*8 + c%8], r = 0..per-1
-            const int g8 = c >> 3, j = c & 7;
-            float t = 0.f;
-            for (int r = 0; r < per; ++r) t += red[(r * G + g8) * 8 + j];
-            dst[s * Cp + c] = t;
-        }
-    }
+    reduce_block_rows<NSUM_EVAL>(acc, red, rows + (size_t)blockIdx.x * NSUM_EVAL * Cp, G, Cp, per);
 }
 
 // Partial rows of an eval-mode BatchNorm backward -> d gamma, d beta, d conv-bias (fixed-order fp64 row sums, sum_partial_rows).
@@ -638,22 +658,14 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const T* __restrict__ 
     __shared__ float red[256 * 8];
     const int G = Cp >> 3, tid = threadIdx.x;
     const int cg = tid % G, rows = 256 / G, prow = tid / G;
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float acc[1][8] = {};
     for (long long pix = (long long)blockIdx.x * rows + prow; pix < npix; pix += (long long)gridDim.x * rows) {
         float v[8];
         Vec8<T>::load(g + pix * ldc + cg * 8, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += v[j];
+        for (int j = 0; j < 8; ++j) acc[0][j] += v[j];
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[j];
-    __syncthreads();
-    for (int c = tid; c < G * 8; c += 256) {
-        const int g8 = c >> 3, j = c & 7;
-        float t = 0.f;
-        for (int r = 0; r < rows; ++r) t += red[(r * G + g8) * 8 + j];
-        partial[(size_t)blockIdx.x * Cp + c] = t;
-    }
+    reduce_block_rows<1>(acc, red, partial + (size_t)blockIdx.x * Cp, G, Cp, rows);
 }
 
 __global__ void __launch_bounds__(FIN_THREADS) channel_sum_final_kernel(const float* __restrict__ partial, int nrows, float* out, int Cp, int C) {
@@ -865,20 +877,71 @@ static inline long long reduce_grid_cap(int forced, int Cp, int lo, int hi, int 
 
 using namespace clamd;
 
-static inline int ew_grid(long long nitem, int cap = 4096) {
-    long long g = (nitem + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+// workgroups (= partial rows) of a launch: one per `per` items, at least one, at most `cap`
+static inline long long grid_rows(long long items, long long per, long long cap) {
+    const long long g = (items + per - 1) / per;
+    return g > cap ? cap : (g < 1 ? 1 : g);
 }
+static inline int ew_grid(long long nitem, int cap = 4096) { return (int)grid_rows(nitem, 256, cap); }
 static bool pow2_channels(int Cp) { return Cp >= 32 && Cp <= 2048 && (Cp & (Cp - 1)) == 0; }
+static const char POW2_RULE[] = "physical channels must be a power of two in [32,2048]";
+// pixels (plain) or 2x2 windows (pooled) of an image batch, and the pixel rows of a 256-thread workgroup whose threads take 8 channels each
+static inline long long pass_pixels(int B, int H, int W, bool pooled) { return pooled ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W; }
+static inline int pixel_rows(int Cp) { return 256 / (Cp / 8) > 0 ? 256 / (Cp / 8) : 1; }
 
 long long clamd_bn_bwd_reduce_rows(int B, int H, int W, int Cp, bool pooled, const clamd_tuning& tn) {
-    const int rows = 256 / (Cp / 8) > 0 ? 256 / (Cp / 8) : 1;
-    const long long npix = pooled ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
-    const long long gb = (npix + rows - 1) / rows;
-    const long long cap = reduce_grid_cap(tn.bn_reduce_blocks, Cp, 256, 1024, 131072);
-    return gb > cap ? cap : (gb < 1 ? 1 : gb);
+    return grid_rows(pass_pixels(B, H, W, pooled), pixel_rows(Cp), reduce_grid_cap(tn.bn_reduce_blocks, Cp, 256, 1024, 131072));
 }
 constexpr int CHSUM_MAX_BLOCKS = 1024;
+
+// Dtype code, and a flag that selects a second template argument (pooled / backward), -> f(Tag<T>, std::bool_constant<flag>).
+// false, with nothing called, for an unknown dtype: the entry points answer "<name>: bad dtype" before any launch.
+template <typename T> struct Tag { using type = T; };
+template <typename F>
+static bool dispatch(int dtype, bool flag, F&& f) {
+    auto with_flag = [&](auto tag) { if (flag) f(tag, std::true_type{}); else f(tag, std::false_type{}); };
+    if (dtype == CLAMD_BF16) with_flag(Tag<bf16_t>{});
+    else if (dtype == CLAMD_F32) with_flag(Tag<float>{});
+    else if (dtype == CLAMD_SPLIT) with_flag(Tag<split_t>{});
+    else return false;
+    return true;
+}
+template <typename F>
+static bool dispatch(int dtype, F&& f) { return dispatch(dtype, false, [&](auto tag, auto) { f(tag); }); }
+
+// "<name>: <text>" through clamd_fail, which copies the string into the library's own per-thread buffer
+static int fail(const char* name, const char* text) {
+    static thread_local char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", name, text);
+    return clamd_fail(msg);
+}
+
+// The argument check of the streaming launchers, before any launch: 0, or -1 with "<name>: <reason>" recorded.
+//   channels_ok / channel_rule: the entry point's rule for Cp (and C) and its text; B, H, W positive, H and W even with a pooled source;
+//   tensors: REQUIRED pointers non-null, at least one of the SOURCE pointers non-null, every pitch of a present tensor >= Cp
+//   (NO_PITCH: a float vector, not an activation) and the bf16x3 layout of every present activation.
+enum Need { OPTIONAL, REQUIRED, SOURCE };
+constexpr int NO_PITCH = 0x7fffffff;
+struct TensorArg { const void* p; int ldc; Need need; };
+static int check_streaming(const char* name, bool channels_ok, const char* channel_rule, int Cp, long long B, long long H, long long W,
+                           bool pooled, int dtype, std::initializer_list<TensorArg> tensors) {
+    if (!channels_ok) return fail(name, channel_rule);
+    if (B <= 0 || H <= 0 || W <= 0) return fail(name, "bad sizes");
+    if (pooled && ((H | W) & 1)) return fail(name, "pooling needs even H, W");
+    bool has_source = false, any_source = false;
+    for (const TensorArg& t : tensors) {
+        if (t.need == REQUIRED && !t.p) return fail(name, "null argument");
+        if (t.need == SOURCE) { any_source = true; has_source |= t.p != nullptr; }
+    }
+    // tests match "no gradient source" (bn_bwd_reduce, bn_bwd_apply) and "null argument" (bn_bwd_eval) in this message: keep both
+    if (any_source && !has_source) return fail(name, "no gradient source (ga and gp are both a null argument)");
+    for (const TensorArg& t : tensors)
+        if (t.p && t.ldc < Cp) return fail(name, "pitches must be >= Cp");
+    for (const TensorArg& t : tensors)
+        if (t.ldc != NO_PITCH)
+            if (int e = clamd_check_split(dtype, t.p, t.ldc)) return e;
+    return 0;
+}
 
 extern "C" {
 
@@ -922,85 +985,60 @@ int clamd_bn_finalize_total(const double* reduce, const float* gamma, const floa
 
 int clamd_bn_apply(const void* y, int y_ldc, const float* scale, const float* shift, void* out, int out_ldc,
                    void* pooled, int p_ldc, int B, int H, int W, int Cp, int dtype, void* stream) {
-    if (!pow2_channels(Cp)) return clamd_fail("bn_apply: physical channels must be a power of two in [32,2048]");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_apply: bad sizes");
-    if (pooled && ((H | W) & 1)) return clamd_fail("bn_apply: pooling needs even H, W");
-    if (!y || !scale || !shift || !out) return clamd_fail("bn_apply: null argument");
-    if (y_ldc < Cp || out_ldc < Cp || (pooled && p_ldc < Cp)) return clamd_fail("bn_apply: pitches must be >= Cp");
-    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
-    if (int e = clamd_check_split(dtype, out, out_ldc)) return e;
-    if (int e = clamd_check_split(dtype, pooled, p_ldc)) return e;
-    const long long nitem = (pooled ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W) * (Cp / 8);
-    dim3 g(ew_grid(nitem, 8192)), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T, P) hipLaunchKernelGGL((bn_apply_kernel<T, P>), g, b, 0, s, (const T*)y, y_ldc, scale, shift, \
-                                        (T*)out, out_ldc, (T*)pooled, p_ldc, B, H, W, Cp)
-    if (dtype == CLAMD_BF16) { if (pooled) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false); }
-    else if (dtype == CLAMD_F32) { if (pooled) LAUNCH(float, true); else LAUNCH(float, false); }
-    else if (dtype == CLAMD_SPLIT) { if (pooled) LAUNCH(split_t, true); else LAUNCH(split_t, false); }
-    else return clamd_fail("bn_apply: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("bn_apply");
+    if (int e = check_streaming("bn_apply", pow2_channels(Cp), POW2_RULE, Cp, B, H, W, pooled != nullptr, dtype,
+                                {{y, y_ldc, REQUIRED}, {scale, NO_PITCH, REQUIRED}, {shift, NO_PITCH, REQUIRED}, {out, out_ldc, REQUIRED},
+                                 {pooled, p_ldc, OPTIONAL}}))
+        return e;
+    const dim3 g(ew_grid(pass_pixels(B, H, W, pooled != nullptr) * (Cp / 8), 8192)), b(256);
+    const bool ok = dispatch(dtype, pooled != nullptr, [&](auto tag, auto pool) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_apply_kernel<T, decltype(pool)::value>), g, b, 0, (hipStream_t)stream, (const T*)y, y_ldc, scale, shift,
+                           (T*)out, out_ldc, (T*)pooled, p_ldc, B, H, W, Cp);
+    });
+    return ok ? clamd_check_launch("bn_apply") : fail("bn_apply", "bad dtype");
 }
 
-static int launch_maxpool(bool bwd, const void* x, int x_ldc, void* out, int o_ldc, const void* gp, int gp_ldc, const float* sign, int B, int H,
-                          int W, int Cp, int dtype, void* stream) {
-    if (!x || !out || (bwd && !gp)) return clamd_fail("maxpool2x2: null argument");
-    if (B <= 0 || H <= 0 || W <= 0 || ((H | W) & 1)) return clamd_fail("maxpool2x2: needs even H, W");
-    if (Cp % 8 || x_ldc < Cp || o_ldc < Cp || (bwd && gp_ldc < Cp)) return clamd_fail("maxpool2x2: bad channel counts / pitches");
-    if (int e = clamd_check_split(dtype, x, x_ldc)) return e;
-    if (int e = clamd_check_split(dtype, out, o_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
-    const long long nitem = (long long)B * (H / 2) * (W / 2) * (Cp / 8);
-    dim3 g(ew_grid(nitem, 8192)), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T)                                                                                                                   \
-    do {                                                                                                                            \
-        if (bwd) hipLaunchKernelGGL((maxpool2x2_kernel<T, true>), g, b, 0, s, (const T*)x, x_ldc, (T*)out, o_ldc, (const T*)gp, gp_ldc, sign, B, H, W, Cp); \
-        else hipLaunchKernelGGL((maxpool2x2_kernel<T, false>), g, b, 0, s, (const T*)x, x_ldc, (T*)out, o_ldc, (const T*)nullptr, 0, sign, B, H, W, Cp);   \
-    } while (0)
-    if (dtype == CLAMD_BF16) LAUNCH(bf16_t);
-    else if (dtype == CLAMD_F32) LAUNCH(float);
-    else if (dtype == CLAMD_SPLIT) LAUNCH(split_t);
-    else return clamd_fail("maxpool2x2: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("maxpool2x2");
+static int launch_maxpool(const char* name, bool bwd, const void* x, int x_ldc, void* out, int o_ldc, const void* gp, int gp_ldc,
+                          const float* sign, int B, int H, int W, int Cp, int dtype, void* stream) {
+    // Cp % 8 == 0, not the power-of-two rule: the stand-alone pool runs at widths that rule would refuse
+    if (int e = check_streaming(name, Cp > 0 && Cp % 8 == 0, "physical channels must be a positive multiple of 8", Cp, B, H, W, true, dtype,
+                                {{x, x_ldc, REQUIRED}, {out, o_ldc, REQUIRED}, {gp, gp_ldc, bwd ? REQUIRED : OPTIONAL}}))
+        return e;
+    const dim3 g(ew_grid(pass_pixels(B, H, W, true) * (Cp / 8), 8192)), b(256);
+    const bool ok = dispatch(dtype, bwd, [&](auto tag, auto back) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((maxpool2x2_kernel<T, decltype(back)::value>), g, b, 0, (hipStream_t)stream, (const T*)x, x_ldc, (T*)out, o_ldc,
+                           (const T*)gp, gp_ldc, sign, B, H, W, Cp);
+    });
+    return ok ? clamd_check_launch(name) : fail(name, "bad dtype");
 }
 
 int clamd_maxpool2x2(const void* x, int x_ldc, const float* sign, void* pooled, int p_ldc, int B, int H, int W, int Cp, int dtype, void* stream) {
-    return launch_maxpool(false, x, x_ldc, pooled, p_ldc, nullptr, 0, sign, B, H, W, Cp, dtype, stream);
+    return launch_maxpool("maxpool2x2", false, x, x_ldc, pooled, p_ldc, nullptr, 0, sign, B, H, W, Cp, dtype, stream);
 }
 
 int clamd_maxpool2x2_bwd(const void* x, int x_ldc, const float* sign, const void* gp, int gp_ldc, void* gx, int gx_ldc, int B, int H, int W, int Cp,
                          int dtype, void* stream) {
-    return launch_maxpool(true, x, x_ldc, gx, gx_ldc, gp, gp_ldc, sign, B, H, W, Cp, dtype, stream);
+    return launch_maxpool("maxpool2x2_bwd", true, x, x_ldc, gx, gx_ldc, gp, gp_ldc, sign, B, H, W, Cp, dtype, stream);
 }
 
 int clamd_bn_bwd_reduce(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc,
                         const float* scale, const float* shift, float* sums, int sum_rows, int B, int H, int W, int Cp,
                         int dtype, const clamd_tuning* tune, void* stream) {
-    if (!pow2_channels(Cp)) return clamd_fail("bn_bwd_reduce: physical channels must be a power of two in [32,2048]");
-    if (!gp && !ga) return clamd_fail("bn_bwd_reduce: no gradient source");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_reduce: bad sizes");
-    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_reduce: pooling needs even H, W");
-    if (!y || !sums || (gp && (!scale || !shift))) return clamd_fail("bn_bwd_reduce: null argument");
-    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp) return clamd_fail("bn_bwd_reduce: pitches must be >= Cp");
-    if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
-    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
+    const Need pool_only = gp ? REQUIRED : OPTIONAL;                   // read by the pooled kernel only
+    if (int e = check_streaming("bn_bwd_reduce", pow2_channels(Cp), POW2_RULE, Cp, B, H, W, gp != nullptr, dtype,
+                                {{ga, ga_ldc, SOURCE}, {gp, gp_ldc, SOURCE}, {y, y_ldc, REQUIRED}, {sums, NO_PITCH, REQUIRED},
+                                 {scale, NO_PITCH, pool_only}, {shift, NO_PITCH, pool_only}}))
+        return e;
     if (int e = clamd_check_tuning(tune)) return e;
     const long long nrows = clamd_bn_bwd_reduce_rows(B, H, W, Cp, gp != nullptr, clamd_tune(tune));
-    if (sum_rows != nrows) return clamd_fail("bn_bwd_reduce: sum_rows does not match clamd_stat_rows(CLAMD_OP_BN_BWD_REDUCE, ...)");
-    dim3 g((unsigned)nrows), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T, P) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, P>), g, b, 0, s, (const T*)ga, ga_ldc, \
-                                        (const T*)gp, gp_ldc, (const T*)y, y_ldc, scale, shift, sums, B, H, W, Cp)
-    if (dtype == CLAMD_BF16) { if (gp) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false); }
-    else if (dtype == CLAMD_F32) { if (gp) LAUNCH(float, true); else LAUNCH(float, false); }
-    else if (dtype == CLAMD_SPLIT) { if (gp) LAUNCH(split_t, true); else LAUNCH(split_t, false); }
-    else return clamd_fail("bn_bwd_reduce: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("bn_bwd_reduce");
+    if (sum_rows != nrows) return fail("bn_bwd_reduce", "sum_rows does not match clamd_stat_rows(CLAMD_OP_BN_BWD_REDUCE, ...)");
+    const bool ok = dispatch(dtype, gp != nullptr, [&](auto tag, auto pool) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, decltype(pool)::value>), dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)ga, ga_ldc, (const T*)gp, gp_ldc, (const T*)y, y_ldc, scale, shift, sums, B, H, W, Cp);
+    });
+    return ok ? clamd_check_launch("bn_bwd_reduce") : fail("bn_bwd_reduce", "bad dtype");
 }
 
 int clamd_bn_bwd_finalize(const float* sums, int sum_rows, const float* gamma, const float* save_mean, const float* save_istd,
@@ -1027,33 +1065,21 @@ int clamd_bn_bwd_finalize_total(const double* totals, const double* reduce, cons
 int clamd_bn_bwd_apply(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc,
                        const float* scale, const float* shift, const float* k012, void* gz, int gz_ldc, int B,
                        int H, int W, int Cp, int dtype, void* stream) {
-    if (!pow2_channels(Cp)) return clamd_fail("bn_bwd_apply: physical channels must be a power of two in [32,2048]");
-    if (!gp && !ga) return clamd_fail("bn_bwd_apply: no gradient source");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_apply: bad sizes");
-    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_apply: pooling needs even H, W");
-    if (!y || !k012 || !gz || (gp && (!scale || !shift))) return clamd_fail("bn_bwd_apply: null argument");
-    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp || gz_ldc < Cp) return clamd_fail("bn_bwd_apply: pitches must be >= Cp");
-    if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
-    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gz, gz_ldc)) return e;
-    const long long nitem = (gp ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W) * (Cp / 8);
-    dim3 g(ew_grid(nitem, 8192)), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T, P) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, P>), g, b, 0, s, (const T*)ga, ga_ldc, \
-                                        (const T*)gp, gp_ldc, (const T*)y, y_ldc, scale, shift, k012, (T*)gz, gz_ldc, B, H, W, Cp)
-    if (dtype == CLAMD_BF16) { if (gp) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false); }
-    else if (dtype == CLAMD_F32) { if (gp) LAUNCH(float, true); else LAUNCH(float, false); }
-    else if (dtype == CLAMD_SPLIT) { if (gp) LAUNCH(split_t, true); else LAUNCH(split_t, false); }
-    else return clamd_fail("bn_bwd_apply: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("bn_bwd_apply");
+    const Need pool_only = gp ? REQUIRED : OPTIONAL;
+    if (int e = check_streaming("bn_bwd_apply", pow2_channels(Cp), POW2_RULE, Cp, B, H, W, gp != nullptr, dtype,
+                                {{ga, ga_ldc, SOURCE}, {gp, gp_ldc, SOURCE}, {y, y_ldc, REQUIRED}, {k012, NO_PITCH, REQUIRED},
+                                 {gz, gz_ldc, REQUIRED}, {scale, NO_PITCH, pool_only}, {shift, NO_PITCH, pool_only}}))
+        return e;
+    const dim3 g(ew_grid(pass_pixels(B, H, W, gp != nullptr) * (Cp / 8), 8192)), b(256);
+    const bool ok = dispatch(dtype, gp != nullptr, [&](auto tag, auto pool) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, decltype(pool)::value>), g, b, 0, (hipStream_t)stream, (const T*)ga, ga_ldc,
+                           (const T*)gp, gp_ldc, (const T*)y, y_ldc, scale, shift, k012, (T*)gz, gz_ldc, B, H, W, Cp);
+    });
+    return ok ? clamd_check_launch("bn_bwd_apply") : fail("bn_bwd_apply", "bad dtype");
 }
 
-static long long apply_sums_rows(long long npix, int Cp) {
-    const long long g = (npix * (Cp / 8) + 255) / 256;
-    return g < 1 ? 1 : (g > 2048 ? 2048 : g);
-}
+static long long apply_sums_rows(long long npix, int Cp) { return grid_rows(npix * (Cp / 8), 256, 2048); }
 
 int clamd_bn_bwd_apply_sums_rows(int B, int H, int W, int Cp) {
     if (B <= 0 || H <= 0 || W <= 0 || !pow2_channels(Cp)) return clamd_fail("bn_bwd_apply_sums_rows: bad sizes");
@@ -1062,32 +1088,24 @@ int clamd_bn_bwd_apply_sums_rows(int B, int H, int W, int Cp) {
 
 int clamd_bn_bwd_apply_sums(const void* ga, int ga_ldc, const void* y, int y_ldc, const float* k012, void* gz, int gz_ldc,
                             float* gz_rows, int nrows, int B, int H, int W, int Cp, int dtype, void* stream) {
-    if (!pow2_channels(Cp)) return clamd_fail("bn_bwd_apply_sums: physical channels must be a power of two in [32,2048]");
-    if (!ga || !y || !k012 || !gz || !gz_rows) return clamd_fail("bn_bwd_apply_sums: null argument");
-    if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
-    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gz, gz_ldc)) return e;
+    if (int e = check_streaming("bn_bwd_apply_sums", pow2_channels(Cp), POW2_RULE, Cp, B, H, W, false, dtype,
+                                {{ga, ga_ldc, REQUIRED}, {y, y_ldc, REQUIRED}, {k012, NO_PITCH, REQUIRED}, {gz, gz_ldc, REQUIRED},
+                                 {gz_rows, NO_PITCH, REQUIRED}}))
+        return e;
     const long long npix = (long long)B * H * W;
-    if (nrows != apply_sums_rows(npix, Cp)) return clamd_fail("bn_bwd_apply_sums: nrows must be clamd_bn_bwd_apply_sums_rows(B, H, W, Cp)");
-    dim3 g((unsigned)nrows), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T) hipLaunchKernelGGL((bn_bwd_apply_sums_kernel<T>), g, b, 0, s, (const T*)ga, ga_ldc, (const T*)y, y_ldc, k012, (T*)gz, gz_ldc, gz_rows, npix, Cp)
-    if (dtype == CLAMD_BF16) LAUNCH(bf16_t);
-    else if (dtype == CLAMD_F32) LAUNCH(float);
-    else if (dtype == CLAMD_SPLIT) LAUNCH(split_t);
-    else return clamd_fail("bn_bwd_apply_sums: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("bn_bwd_apply_sums");
+    if (nrows != apply_sums_rows(npix, Cp)) return fail("bn_bwd_apply_sums", "nrows must be clamd_bn_bwd_apply_sums_rows(B, H, W, Cp)");
+    const bool ok = dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_bwd_apply_sums_kernel<T>), dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, (const T*)ga, ga_ldc,
+                           (const T*)y, y_ldc, k012, (T*)gz, gz_ldc, gz_rows, npix, Cp);
+    });
+    return ok ? clamd_check_launch("bn_bwd_apply_sums") : fail("bn_bwd_apply_sums", "bad dtype");
 }
 
 // rows of clamd_bn_bwd_eval: one per workgroup; the grid stops growing at ~1 MB of rows (the finalize adds them on the critical chain of
 // the fused-sum units and beside a weight gradient elsewhere) and at 2048 workgroups (8 per CU: the pass streams at full rate well below)
 static long long eval_rows(int B, int H, int W, int Cp, bool pooled) {
-    const int per = 256 / (Cp / 8);
-    const long long npix = pooled ? (long long)B * (H / 2) * (W / 2) : (long long)B * H * W;
-    const long long gb = (npix + per - 1) / per;
-    const long long cap = reduce_grid_cap(0, Cp, 256, 2048, 262144);
-    return gb > cap ? cap : (gb < 1 ? 1 : gb);
+    return grid_rows(pass_pixels(B, H, W, pooled), pixel_rows(Cp), reduce_grid_cap(0, Cp, 256, 2048, 262144));
 }
 
 int clamd_bn_bwd_eval_rows(int B, int H, int W, int Cp, int pooled) {
@@ -1098,26 +1116,18 @@ int clamd_bn_bwd_eval_rows(int B, int H, int W, int Cp, int pooled) {
 
 int clamd_bn_bwd_eval(const void* ga, int ga_ldc, const void* gp, int gp_ldc, const void* y, int y_ldc, const float* scale, const float* shift,
                       void* gz, int gz_ldc, float* rows, int nrows, int B, int H, int W, int Cp, int C, int dtype, void* stream) {
-    if (!pow2_channels(Cp) || C <= 0 || C > Cp) return clamd_fail("bn_bwd_eval: physical channels must be a power of two in [32,2048], 0 < C <= Cp");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("bn_bwd_eval: bad sizes");
-    if (!y || !scale || !gz || !rows || (!ga && !gp) || (gp && !shift)) return clamd_fail("bn_bwd_eval: null argument");
-    if (gp && ((H | W) & 1)) return clamd_fail("bn_bwd_eval: pooling needs even H, W");
-    if ((ga && ga_ldc < Cp) || (gp && gp_ldc < Cp) || y_ldc < Cp || gz_ldc < Cp) return clamd_fail("bn_bwd_eval: pitches must be >= Cp");
-    if (int e = clamd_check_split(dtype, ga, ga_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gp, gp_ldc)) return e;
-    if (int e = clamd_check_split(dtype, y, y_ldc)) return e;
-    if (int e = clamd_check_split(dtype, gz, gz_ldc)) return e;
-    if (nrows != eval_rows(B, H, W, Cp, gp != nullptr)) return clamd_fail("bn_bwd_eval: nrows must be clamd_bn_bwd_eval_rows(B, H, W, Cp, gp != NULL)");
-    dim3 g((unsigned)nrows), b(256);
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(T, P) hipLaunchKernelGGL((bn_bwd_eval_kernel<T, P>), g, b, 0, s, (const T*)ga, ga_ldc, (const T*)gp, gp_ldc, (const T*)y, y_ldc, \
-                                        scale, shift, (T*)gz, gz_ldc, rows, B, H, W, Cp, C)
-    if (dtype == CLAMD_BF16) { if (gp) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false); }
-    else if (dtype == CLAMD_F32) { if (gp) LAUNCH(float, true); else LAUNCH(float, false); }
-    else if (dtype == CLAMD_SPLIT) { if (gp) LAUNCH(split_t, true); else LAUNCH(split_t, false); }
-    else return clamd_fail("bn_bwd_eval: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("bn_bwd_eval");
+    if (int e = check_streaming("bn_bwd_eval", pow2_channels(Cp) && C > 0 && C <= Cp,
+                                "physical channels must be a power of two in [32,2048], 0 < C <= Cp", Cp, B, H, W, gp != nullptr, dtype,
+                                {{ga, ga_ldc, SOURCE}, {gp, gp_ldc, SOURCE}, {y, y_ldc, REQUIRED}, {scale, NO_PITCH, REQUIRED},
+                                 {gz, gz_ldc, REQUIRED}, {rows, NO_PITCH, REQUIRED}, {shift, NO_PITCH, gp ? REQUIRED : OPTIONAL}}))
+        return e;
+    if (nrows != eval_rows(B, H, W, Cp, gp != nullptr)) return fail("bn_bwd_eval", "nrows must be clamd_bn_bwd_eval_rows(B, H, W, Cp, gp != NULL)");
+    const bool ok = dispatch(dtype, gp != nullptr, [&](auto tag, auto pool) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_bwd_eval_kernel<T, decltype(pool)::value>), dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)ga, ga_ldc, (const T*)gp, gp_ldc, (const T*)y, y_ldc, scale, shift, (T*)gz, gz_ldc, rows, B, H, W, Cp, C);
+    });
+    return ok ? clamd_check_launch("bn_bwd_eval") : fail("bn_bwd_eval", "bad dtype");
 }
 
 int clamd_bn_bwd_eval_finalize(const float* rows, int nrows, int nsums, const float* scale, const float* save_mean, const float* save_istd,
@@ -1146,25 +1156,20 @@ size_t clamd_channel_sum_workspace_bytes(int Cp) { return (size_t)CHSUM_MAX_BLOC
 
 int clamd_channel_sum(const void* g, int ldc, float* out, long long npix, int Cp, int C, int dtype, float* workspace,
                       size_t ws_bytes, const clamd_tuning* tune, void* stream) {
-    if (!pow2_channels(Cp)) return clamd_fail("channel_sum: physical channels must be a power of two in [32,2048]");
-    if (C > Cp || npix <= 0) return clamd_fail("channel_sum: bad sizes");
-    if (int e = clamd_check_split(dtype, g, ldc)) return e;
+    if (pow2_channels(Cp) && C > Cp) return clamd_fail("channel_sum: bad sizes");      // the channel rule answers first
+    if (int e = check_streaming("channel_sum", pow2_channels(Cp), POW2_RULE, Cp, 1, 1, npix, false, dtype,
+                                {{g, ldc, REQUIRED}, {out, NO_PITCH, REQUIRED}}))
+        return e;
     if (int e = clamd_check_tuning(tune)) return e;
-    const int rows = 256 / (Cp / 8) > 0 ? 256 / (Cp / 8) : 1;
-    long long gb = (npix + rows - 1) / rows;
     // partial rows, no atomics: more blocks stream faster (tools/bn_reduce_ab.py: 128 channels @128^2 23.8 us at 256 blocks, 16.1 at 1024)
-    const long long cap = reduce_grid_cap(clamd_tune(tune).chsum_blocks, Cp, 256, CHSUM_MAX_BLOCKS, 131072);
-    if (gb > cap) gb = cap;
+    const long long gb = grid_rows(npix, pixel_rows(Cp), reduce_grid_cap(clamd_tune(tune).chsum_blocks, Cp, 256, CHSUM_MAX_BLOCKS, 131072));
     if (!workspace || (size_t)gb * Cp * sizeof(float) > ws_bytes) return clamd_fail("channel_sum: workspace too small (clamd_channel_sum_workspace_bytes)");
-    dim3 gr((unsigned)gb), b(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CLAMD_BF16)
-        hipLaunchKernelGGL(channel_sum_kernel<bf16_t>, gr, b, 0, s, (const bf16_t*)g, ldc, workspace, npix, Cp);
-    else if (dtype == CLAMD_F32)
-        hipLaunchKernelGGL(channel_sum_kernel<float>, gr, b, 0, s, (const float*)g, ldc, workspace, npix, Cp);
-    else if (dtype == CLAMD_SPLIT)
-        hipLaunchKernelGGL(channel_sum_kernel<split_t>, gr, b, 0, s, (const split_t*)g, ldc, workspace, npix, Cp);
-    else return clamd_fail("channel_sum: bad dtype");
+    const bool ok = dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(channel_sum_kernel<T>, dim3((unsigned)gb), dim3(256), 0, s, (const T*)g, ldc, workspace, npix, Cp);
+    });
+    if (!ok) return fail("channel_sum", "bad dtype");
     hipLaunchKernelGGL(channel_sum_final_kernel, dim3(Cp / FIN_CH), dim3(FIN_THREADS), 0, s, workspace, (int)gb, out, Cp, C);
     return clamd_check_launch("channel_sum");
 }
@@ -1179,21 +1184,17 @@ int clamd_nchw_to_nhwc(const float* src, void* dst, int ldc, int B, int C, int H
     hipStream_t s = (hipStream_t)stream;
     if (Cp == 32 && ((long long)H * W) % 4 == 0 && ((size_t)src % 16) == 0) {
         const dim3 g4(ew_grid(nitem / 4, 8192));
-#define LAUNCH4(T) hipLaunchKernelGGL((nchw_to_nhwc4_kernel<T, 32>), g4, b, 0, s, src, (T*)dst, ldc, B, C, H, W, (float)mul)
-        if (dtype == CLAMD_BF16) LAUNCH4(bf16_t);
-        else if (dtype == CLAMD_F32) LAUNCH4(float);
-        else if (dtype == CLAMD_SPLIT) LAUNCH4(split_t);
-        else return clamd_fail("nchw_to_nhwc: bad dtype");
-#undef LAUNCH4
-        return clamd_check_launch("nchw_to_nhwc");
+        const bool ok = dispatch(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((nchw_to_nhwc4_kernel<T, 32>), g4, b, 0, s, src, (T*)dst, ldc, B, C, H, W, (float)mul);
+        });
+        return ok ? clamd_check_launch("nchw_to_nhwc") : clamd_fail("nchw_to_nhwc: bad dtype");
     }
-#define LAUNCH(T) hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, g, b, 0, s, src, (T*)dst, ldc, B, C, H, W, Cp, (float)mul)
-    if (dtype == CLAMD_BF16) LAUNCH(bf16_t);
-    else if (dtype == CLAMD_F32) LAUNCH(float);
-    else if (dtype == CLAMD_SPLIT) LAUNCH(split_t);
-    else return clamd_fail("nchw_to_nhwc: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("nchw_to_nhwc");
+    const bool ok = dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, g, b, 0, s, src, (T*)dst, ldc, B, C, H, W, Cp, (float)mul);
+    });
+    return ok ? clamd_check_launch("nchw_to_nhwc") : clamd_fail("nchw_to_nhwc: bad dtype");
 }
 
 int clamd_nchw_im2col3(const float* src, void* dst, int ldc, int B, int C, int H, int W, int Cp, int dtype, void* stream) {
@@ -1208,46 +1209,37 @@ int clamd_nchw_im2col3(const float* src, void* dst, int ldc, int B, int C, int H
     // exchange (the piece kernel's 8 scalar gathers per 16 bytes of output cost more than they save there: 42 us against 36)
     if (C <= 3 && Cp == 32 && (dtype != CLAMD_BF16 || W % 4 || ((size_t)src % 16))) {
         const dim3 gp(ew_grid(nitem * 4, 16384));
-#define LAUNCHP(T) hipLaunchKernelGGL(nchw_im2col3p_kernel<T>, gp, b, 0, s, src, (T*)dst, ldc, B, C, H, W)
-        if (dtype == CLAMD_BF16) LAUNCHP(bf16_t);
-        else if (dtype == CLAMD_F32) LAUNCHP(float);
-        else if (dtype == CLAMD_SPLIT) LAUNCHP(split_t);
-        else return clamd_fail("nchw_im2col3: bad dtype");
-#undef LAUNCHP
-        return clamd_check_launch("nchw_im2col3");
+        const bool ok = dispatch(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(nchw_im2col3p_kernel<T>, gp, b, 0, s, src, (T*)dst, ldc, B, C, H, W);
+        });
+        return ok ? clamd_check_launch("nchw_im2col3") : clamd_fail("nchw_im2col3: bad dtype");
     }
 #endif
     if (C <= 3 && Cp == 32 && W % 4 == 0 && ((size_t)src % 16) == 0) {
         const dim3 g4(ew_grid(nitem / 4, 8192));
-#define LAUNCH4(T) hipLaunchKernelGGL(nchw_im2col3x4_kernel<T>, g4, b, 0, s, src, (T*)dst, ldc, B, C, H, W)
-        if (dtype == CLAMD_BF16) LAUNCH4(bf16_t);
-        else if (dtype == CLAMD_F32) LAUNCH4(float);
-        else if (dtype == CLAMD_SPLIT) LAUNCH4(split_t);
-        else return clamd_fail("nchw_im2col3: bad dtype");
-#undef LAUNCH4
-        return clamd_check_launch("nchw_im2col3");
+        const bool ok = dispatch(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(nchw_im2col3x4_kernel<T>, g4, b, 0, s, src, (T*)dst, ldc, B, C, H, W);
+        });
+        return ok ? clamd_check_launch("nchw_im2col3") : clamd_fail("nchw_im2col3: bad dtype");
     }
-#define LAUNCH(T) hipLaunchKernelGGL(nchw_im2col3_kernel<T>, g, b, 0, s, src, (T*)dst, ldc, B, C, H, W, Cp)
-    if (dtype == CLAMD_BF16) LAUNCH(bf16_t);
-    else if (dtype == CLAMD_F32) LAUNCH(float);
-    else if (dtype == CLAMD_SPLIT) LAUNCH(split_t);
-    else return clamd_fail("nchw_im2col3: bad dtype");
-#undef LAUNCH
-    return clamd_check_launch("nchw_im2col3");
+    const bool ok = dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nchw_im2col3_kernel<T>, g, b, 0, s, src, (T*)dst, ldc, B, C, H, W, Cp);
+    });
+    return ok ? clamd_check_launch("nchw_im2col3") : clamd_fail("nchw_im2col3: bad dtype");
 }
 
 int clamd_nhwc_to_nchw(const void* src, int ldc, float* dst, int B, int C, int H, int W, int dtype, void* stream) {
     const long long n = (long long)B * C * H * W;
     dim3 g(ew_grid(n, 8192)), b(256);
     if (int e = clamd_check_split(dtype, src, ldc)) return e;
-    if (dtype == CLAMD_BF16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, g, b, 0, (hipStream_t)stream, (const bf16_t*)src, ldc, dst, B, C, H, W);
-    else if (dtype == CLAMD_F32)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, g, b, 0, (hipStream_t)stream, (const float*)src, ldc, dst, B, C, H, W);
-    else if (dtype == CLAMD_SPLIT)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<split_t>, g, b, 0, (hipStream_t)stream, (const split_t*)src, ldc, dst, B, C, H, W);
-    else return clamd_fail("nhwc_to_nchw: bad dtype");
-    return clamd_check_launch("nhwc_to_nchw");
+    const bool ok = dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, g, b, 0, (hipStream_t)stream, (const T*)src, ldc, dst, B, C, H, W);
+    });
+    return ok ? clamd_check_launch("nhwc_to_nchw") : clamd_fail("nhwc_to_nchw: bad dtype");
 }
 
 }  // extern "C"

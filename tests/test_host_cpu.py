@@ -270,8 +270,8 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
 
 
 def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):
-    """clamd_bn_finalize / _apply / _bwd_reduce / _bwd_finalize / _bwd_apply: a null pointer the selected kernel would dereference, a pitch
-    below Cp, a non-positive B / H / W are refused by a host check -- status -1 (clamd_fail) and that check's message, never -2 (a launch
+    """clamd_bn_finalize / _apply / _bwd_reduce / _bwd_finalize / _bwd_apply / _bwd_apply_sums / _bwd_eval, clamd_maxpool2x2[_bwd] and
+    clamd_channel_sum: a null pointer the selected kernel would dereference, a pitch below Cp, a non-positive B / H / W are refused by a host check -- status -1 (clamd_fail) and that check's message, never -2 (a launch
     that was tried).  The optional pointers stay optional: those calls are not made here, the GPU suite makes them."""
     import ctypes
     lib = C._lib.load()
@@ -354,6 +354,110 @@ def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):
         refused('clamd_bn_bwd_apply', 'bad sizes', bapp, base, **kw)
     refused('clamd_bn_bwd_apply', 'pooling needs even H, W', bapp, base, **{**pooled, 'W': 5})
     refused('clamd_bn_bwd_apply', 'bad dtype', bapp, base, dtype=-1)
+
+    # the other streaming launchers go through the same check: every required pointer, every pitch, each size, the channel rule, the dtype
+    # and the row count / workspace the caller sized
+    asum = 'ga ga_ldc y y_ldc k012 gz gz_ldc gz_rows nrows B H W Cp dtype stream'.split()
+    nr = lib.clamd_bn_bwd_apply_sums_rows(2, 8, 6, 64)
+    assert nr > 0
+    base = dict(ga=p, ga_ldc=64, y=p, y_ldc=64, k012=p, gz=p, gz_ldc=128, gz_rows=p, nrows=nr, B=2, H=8, W=6, Cp=64, dtype=0, stream=None)
+    for k in ('ga', 'y', 'k012', 'gz', 'gz_rows'):
+        refused('clamd_bn_bwd_apply_sums', 'null argument', asum, base, **{k: None})
+    for kw in (dict(ga_ldc=63), dict(y_ldc=63), dict(gz_ldc=63), dict(gz_ldc=0), dict(y_ldc=-64)):
+        refused('clamd_bn_bwd_apply_sums', 'pitches must be >= Cp', asum, base, **kw)
+    for kw in (dict(B=0), dict(H=0), dict(W=0), dict(H=-8)):
+        refused('clamd_bn_bwd_apply_sums', 'bad sizes', asum, base, **kw)
+    for cp in (48, 16, 4096):
+        refused('clamd_bn_bwd_apply_sums', 'power of two', asum, base, Cp=cp)
+    refused('clamd_bn_bwd_apply_sums', 'bad dtype', asum, base, dtype=3)
+    for d in (-1, 1):
+        refused('clamd_bn_bwd_apply_sums', 'nrows must be', asum, base, nrows=nr + d)
+
+    ev = 'ga ga_ldc gp gp_ldc y y_ldc scale shift gz gz_ldc rows nrows B H W Cp C dtype stream'.split()
+    nr, nrp = lib.clamd_bn_bwd_eval_rows(2, 8, 6, 64, 0), lib.clamd_bn_bwd_eval_rows(2, 8, 6, 64, 1)
+    assert nr > 0 and nrp > 0
+    base = dict(ga=p, ga_ldc=64, gp=None, gp_ldc=0, y=p, y_ldc=64, scale=p, shift=None, gz=p, gz_ldc=64, rows=p, nrows=nr, B=2, H=8, W=6, Cp=64, C=60,
+                dtype=0, stream=None)
+    pooled = dict(gp=p, gp_ldc=64, shift=p, nrows=nrp)
+    refused('clamd_bn_bwd_eval', 'no gradient source', ev, base, ga=None)
+    for k in ('y', 'scale', 'gz', 'rows'):
+        refused('clamd_bn_bwd_eval', 'null argument', ev, base, **{k: None})
+        refused('clamd_bn_bwd_eval', 'null argument', ev, base, **{**pooled, k: None})
+    refused('clamd_bn_bwd_eval', 'null argument', ev, base, **{**pooled, 'shift': None})          # read by the pooled kernel only
+    for kw in (dict(ga_ldc=63), dict(y_ldc=63), dict(gz_ldc=63), {**pooled, 'gp_ldc': 63}, {**pooled, 'ga': None, 'gp_ldc': 32}):
+        refused('clamd_bn_bwd_eval', 'pitches must be >= Cp', ev, base, **kw)
+    for kw in (dict(B=0), dict(H=0), dict(W=0), {**pooled, 'B': -1}):
+        refused('clamd_bn_bwd_eval', 'bad sizes', ev, base, **kw)
+    for kw in (dict(H=7), dict(W=5)):
+        refused('clamd_bn_bwd_eval', 'pooling needs even H, W', ev, base, **{**pooled, **kw})
+    for kw in (dict(Cp=48), dict(Cp=4096, C=60), dict(C=0), dict(C=65)):
+        refused('clamd_bn_bwd_eval', '0 < C <= Cp', ev, base, **kw)
+    refused('clamd_bn_bwd_eval', 'bad dtype', ev, base, dtype=3)
+    refused('clamd_bn_bwd_eval', 'nrows must be', ev, base, nrows=nr + 1)
+    refused('clamd_bn_bwd_eval', 'nrows must be', ev, base, **{**pooled, 'nrows': nrp - 1})
+
+    # the stand-alone pool takes any multiple of 8 channels (Cp = 24 passes the channel rule and is refused for its pitch below)
+    mp = 'x x_ldc sign pooled p_ldc B H W Cp dtype stream'.split()
+    base = dict(x=p, x_ldc=64, sign=None, pooled=p, p_ldc=64, B=2, H=8, W=6, Cp=64, dtype=0, stream=None)
+    mpb = 'x x_ldc sign gp gp_ldc gx gx_ldc B H W Cp dtype stream'.split()
+    base_b = dict(x=p, x_ldc=64, sign=None, gp=p, gp_ldc=64, gx=p, gx_ldc=64, B=2, H=8, W=6, Cp=64, dtype=0, stream=None)
+    for name, order, b, ptrs, pitches in (('clamd_maxpool2x2', mp, base, ('x', 'pooled'), ('x_ldc', 'p_ldc')),
+                                          ('clamd_maxpool2x2_bwd', mpb, base_b, ('x', 'gp', 'gx'), ('x_ldc', 'gp_ldc', 'gx_ldc'))):
+        for k in ptrs:
+            refused(name, 'null argument', order, b, **{k: None})
+        for k in pitches:
+            refused(name, 'pitches must be >= Cp', order, b, **{k: 63})
+            refused(name, 'pitches must be >= Cp', order, b, Cp=24, **{k: 16})
+        for kw in (dict(B=0), dict(H=0), dict(W=0), dict(W=-2)):
+            refused(name, 'bad sizes', order, b, **kw)
+        for kw in (dict(H=7), dict(W=5)):
+            refused(name, 'pooling needs even H, W', order, b, **kw)
+        for cp in (60, 4, 0, -8):
+            refused(name, 'multiple of 8', order, b, Cp=cp)
+        refused(name, 'bad dtype', order, b, dtype=3)
+
+    cs = 'g ldc out npix Cp C dtype workspace ws_bytes tune stream'.split()
+    base = dict(g=p, ldc=64, out=p, npix=96, Cp=64, C=60, dtype=0, workspace=p, ws_bytes=3 * 64 * 4, tune=None, stream=None)      # 3 rows of 32 pixels
+    for k in ('g', 'out'):
+        refused('clamd_channel_sum', 'null argument', cs, base, **{k: None})
+    for ldc in (63, 0, -64):
+        refused('clamd_channel_sum', 'pitches must be >= Cp', cs, base, ldc=ldc)
+    for kw in (dict(npix=0), dict(npix=-1), dict(C=65)):
+        refused('clamd_channel_sum', 'bad sizes', cs, base, **kw)
+    for cp in (48, 16, 4096):
+        refused('clamd_channel_sum', 'power of two', cs, base, Cp=cp, C=8)
+    refused('clamd_channel_sum', 'power of two', cs, base, Cp=48)                                   # C = 60 > 48 too: the channel rule answers first
+    refused('clamd_channel_sum', 'bad dtype', cs, base, dtype=3)
+    refused('clamd_channel_sum', 'workspace too small', cs, base, ws_bytes=3 * 64 * 4 - 1)
+    refused('clamd_channel_sum', 'workspace too small', cs, base, workspace=None)
+
+
+def test_bn_row_counts_follow_one_rule(C):
+    """The partial-row counts of the three reducing passes, restated: clamp(ceil(items / per), 1, cap) with cap = the forced grid or
+    clamp(budget // Cp, lo, hi).  bn_bwd_reduce and bn_bwd_eval: items = pixels (2x2 windows when pooled), per = the 256 / (Cp / 8) pixel
+    rows of a workgroup, (lo, hi, budget) = (256, 1024, 131072) and (256, 2048, 262144); bn_bwd_apply_sums: 16-byte items, 256 per
+    workgroup, a flat cap of 2048.  The callers size their buffers with these counts and the launchers refuse any other."""
+    L = C._lib
+    lib = L.load()
+
+    def rule(items, per, cap):
+        return min(max(-(-items // per), 1), cap)
+
+    def cap_of(forced, cp, lo, hi, budget):
+        return forced or min(max(budget // cp, lo), hi)
+
+    for cp in (32, 64, 256, 1024, 2048):
+        per = max(256 // (cp // 8), 1)
+        for B, H, W in ((1, 2, 2), (2, 6, 10), (16, 16, 16), (16, 256, 256), (32, 512, 512)):
+            for pooled in (0, 1):
+                npix = B * (H // 2) * (W // 2) if pooled else B * H * W
+                for forced in (0, 3):
+                    got = L.stat_rows(L.OP_BN_BWD_REDUCE, B, H, W, pooled, cp, L.F32, tuning=L.Tuning(bn_reduce_blocks=forced))
+                    assert got == rule(npix, per, cap_of(forced, cp, 256, 1024, 131072)), ('reduce', cp, B, H, W, pooled, forced, got)
+                got = lib.clamd_bn_bwd_eval_rows(B, H, W, cp, pooled)
+                assert got == rule(npix, per, cap_of(0, cp, 256, 2048, 262144)), ('eval', cp, B, H, W, pooled, got)
+            got = lib.clamd_bn_bwd_apply_sums_rows(B, H, W, cp)
+            assert got == rule(B * H * W * (cp // 8), 256, 2048), ('apply_sums', cp, B, H, W, got)
 
 
 def test_bf16x3_plane_layout_helpers_roundtrip():
