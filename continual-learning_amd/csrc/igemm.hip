@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IgemmParams p) {
         if (p.pred) {
             // arg-max fused into the head (trainer.py:279 `torch.max(outputs, 1)`): lane = class, register = pixel; a butterfly
             // over the 32 lanes of a half-wave on (value, class) pairs, ties to the LOWER class (first maximum, as torch).
-            // Only the first 64-class slab takes part (num_classes <= 64 is checked by the launcher; tn == 0 here).
+            // One 64-class slab takes part (the launcher checks num_classes <= 64 and Np <= 64, so ntn == 1 and n0 == 0 here).
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -608,6 +608,8 @@ int clamd_conv1x1_argmax(const void* x, int x_ldc, const void* w_packed, const f
     if (int e = check_common(p, "conv1x1_argmax", dtype, false)) return e;
     if (!pred) return clamd_fail("conv1x1_argmax: pred is null");
     if (num_classes < 1 || num_classes > Cout_p || num_classes > 64) return clamd_fail("conv1x1_argmax: num_classes must be in [1, min(64, padded Cout)]");
+    // one 64-channel slab per pixel tile: a workgroup of a second slab would see -inf in every lane and write pred = 64 over the first slab's result
+    if (Cout_p > 64) return clamd_fail("conv1x1_argmax: padded Cout must be 32 or 64 (the arg-max runs inside one 64-channel slab)");
     return launch<MODE_PW, EPI_NCHW>(p, dtype, (hipStream_t)stream);
 }
 

@@ -243,7 +243,8 @@ int clamd_conv1x1(const void* x, int x_ldc, const void* w_packed, const float* b
 int clamd_conv1x1_logits(const void* x, int x_ldc, const void* w_packed, const float* bias, float* logits_nchw,
                          int B, int H, int W, int Cin_p, int Cout_p, int num_classes, int dtype, void* stream);
 /* The head with the arg-max over classes fused into its epilogue (eval forward, trainer.py:279 `torch.max(outputs, 1)`;
- * SURVEY.md §8f row 4): pred int64 [B,H,W], first maximum wins; logits_nchw may be NULL (the logits are then never written). */
+ * SURVEY.md §8f row 4): pred int64 [B,H,W], first maximum wins; logits_nchw may be NULL (the logits are then never written).
+ * num_classes <= 64 and Cout_p <= 64 (the arg-max runs inside one 64-channel slab); anything else is refused with status -1, nothing launched. */
 int clamd_conv1x1_argmax(const void* x, int x_ldc, const void* w_packed, const float* bias, long long* pred, float* logits_nchw,
                          int B, int H, int W, int Cin_p, int Cout_p, int num_classes, int dtype, void* stream);
 /* nn.ConvTranspose2d(k2,s2)+bias (unet.py:34): x [B,h,w,Cin_p] -> y [B,2h,2w,(ldc)] channels [0,Cout_p) of the

@@ -1,0 +1,107 @@
+"""Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py): poisoned buffers with guard
+bands, the two-runs check, the storage rounding of the three dtypes and the per-element comparison against a float64 reference."""
+import math
+
+import numpy as np
+import torch
+
+DEV = torch.device('cuda', 0)
+EPS = 2.0 ** -24
+STORE_REL = {0: 0.0, 1: 2.0 ** -8, 2: 2.0 ** -16 + EPS * (1 + 2.0 ** -16)}
+POISON = 7.5                                  # exact in bf16 too
+GUARD = 64                                    # elements: 256 bytes of fp32 (a bf16x3 base stays 64-byte aligned), 128 of bf16
+EXTRA_ROWS = 3
+RATIOS = {}                                   # (kernel, dtype) -> largest error / bound seen (printed by every case)
+
+
+def _raw(t):
+    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+class Act:
+    """`npix` pixels x `cp` channels at pitch `ldc` in the storage of dtype code `dcode`, inside a buffer poisoned in front, behind and in
+    the pitch gap.  Filled with `values` (fp32 [npix, cp], values the storage holds exactly) or NaN."""
+
+    def __init__(self, C, npix, cp, ldc, dcode, values=None):
+        self.C, self.npix, self.cp, self.ldc, self.dcode = C, npix, cp, ldc, dcode
+        self.buf = torch.full((2 * GUARD + npix * ldc,), POISON, dtype=C.ops.TORCH_DT[dcode], device=DEV)
+        self.view = self.buf[GUARD:GUARD + npix * ldc].view(npix, ldc)
+        assert DEV.type != 'cuda' or self.view.data_ptr() % 64 == 0
+        v = torch.full((npix, cp), float('nan'), device=DEV) if values is None else values.to(DEV, torch.float32)
+        self.view[:, :cp] = C.ops.split_encode(v) if dcode == 2 else v.to(self.buf.dtype)
+        self.before = self.buf.clone()
+
+    @property
+    def ptr(self):
+        return self.view.data_ptr()
+
+    def get(self):
+        s = self.view[:, :self.cp]
+        return self.C.ops.split_decode(s) if self.dcode == 2 else s.float()
+
+    def guards_intact(self):
+        a = self.buf.clone()
+        a[GUARD:GUARD + self.npix * self.ldc].view(self.npix, self.ldc)[:, :self.cp] = self.view_of(self.before)[:, :self.cp]
+        return torch.equal(_raw(a), _raw(self.before))
+
+    def view_of(self, buf):
+        return buf[GUARD:GUARD + self.npix * self.ldc].view(self.npix, self.ldc)
+
+    def zero_bits(self):
+        """[npix, cp] bool: the stored element is +0 (all bits clear; bf16x3: hi and lo)."""
+        s = self.view[:, :self.cp].contiguous()
+        if self.dcode != 2:
+            return _raw(s) == 0
+        r = s.view(torch.int16).reshape(self.npix, self.cp // 16, 2, 16)
+        return ((r[:, :, 0] == 0) & (r[:, :, 1] == 0)).reshape(self.npix, self.cp)
+
+
+class Rows:
+    """fp32 [n, *shape] (partial rows, or a C-sized vector with n = C) with guard bands and, behind the n rows, EXTRA_ROWS poisoned rows."""
+
+    def __init__(self, n, *shape, fill=float('nan'), dtype=torch.float32):
+        per = math.prod(shape) if shape else 1
+        self.n, self.per = n, per
+        self.buf = torch.full((2 * GUARD + (n + EXTRA_ROWS) * per,), POISON if dtype.is_floating_point else int(POISON), dtype=dtype, device=DEV)
+        self.view = self.buf[GUARD:GUARD + n * per].view(n, *shape)
+        self.view.fill_(fill)
+        self.before = self.buf.clone()
+
+    @property
+    def ptr(self):
+        return self.view.data_ptr()
+
+    def guards_intact(self):
+        a = self.buf.clone()
+        a[GUARD:GUARD + self.n * self.per] = self.before[GUARD:GUARD + self.n * self.per]
+        return torch.equal(_raw(a), _raw(self.before))
+
+
+def _twice(what, launch):
+    """launch() -> list of Act / Rows it wrote (synchronised).  Twice: the same bits; guard bands intact."""
+    a, b = launch(), launch()
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert x.guards_intact() and y.guards_intact(), f'{what}: output {i}: a store outside the written region'
+        assert torch.equal(_raw(x.buf), _raw(y.buf)), f'{what}: output {i}: two runs differ'
+    return a
+
+
+def _store_round(x, dcode):
+    """The fp32 value that the storage of `dcode` holds for the fp32 value x (Vec8<T>::store, then Vec8<T>::load)."""
+    if dcode == 0:
+        return x.clone()
+    hi = x.to(torch.bfloat16).float()
+    return hi if dcode == 1 else hi + (x - hi).to(torch.bfloat16).float()
+
+
+def _per_element(what, key, got, ref, bound):
+    """|got - ref| <= bound for every element; the worst element's index and error / bound on failure (and printed always)."""
+    err = (got.double() - ref).abs()
+    ratio = torch.where(err <= bound, err / bound.clamp_min(1e-300), torch.full_like(err, float('inf')))
+    ratio = torch.where(err == 0, torch.zeros_like(err), ratio)
+    worst = float(ratio.max())
+    idx = np.unravel_index(int(ratio.argmax()), tuple(ratio.shape))
+    RATIOS[key] = max(RATIOS.get(key, 0.0), worst)
+    print(f'{what}: worst error / bound {worst:.3f} at {idx} (largest so far for {key}: {RATIOS[key]:.3f})')
+    assert worst <= 1.0, (f'{what}: element {idx}: got {float(got[idx])!r}, reference {float(ref[idx])!r}, bound {float(bound[idx]):.3e}, '
+                          f'error / bound {worst:.3f}')
