@@ -96,8 +96,12 @@ int clamd_stat_rows(int op, int B, int H, int W, int Cin_p, int Cout_p, int dtyp
  *   w_packed: [9][Cout_p][Cin_p] compute dtype, Cin innermost (see clamd_pack).  m_fastest: block order hint.
  *   bn_y/bn_sums (optional, data-gradient launches): when y of THIS launch is the gradient w.r.t. a BatchNorm output,
  *   also accumulate the five per-channel sums of clamd_bn_bwd_reduce (bn_y = that unit's saved activation
- *   [B,H,W,Cout_p], bn_sums = [row][5][Cout_p]) in the epilogue, so the separate reduce pass is not needed.
- *   stat_rows = clamd_stat_rows(CLAMD_OP_CONV3X3, ...) (ignored when neither stats nor bn_sums is given).
+ *   [B,H,W,Cout_p], bn_sums = [row][5][Cout_p]) in the epilogue, so the separate reduce pass is not needed.  bn_y has no pitch
+ *   argument: it is read dense, at pitch Cout_p (a saved activation of its own, never a slice of a concat buffer).
+ *   stat_rows = clamd_stat_rows(CLAMD_OP_CONV3X3, ...) (ignored when neither stats nor bn_sums is given).  With fused_bn that query
+ *   describes the PLAIN data-gradient launch (no bias, ReLU, statistics), as clamd_conv3x3_bn_sums does: a bf16 launch that passes bn_y
+ *   together with one of those is declined by the persistent kernel and writes one row per 256-pixel tile (or per tile of the
+ *   producer/consumer kernel igemm_ws names); a stat_rows that does not match is refused, never mis-summed.
  *   relu: bit 0 = apply ReLU; bit 1 (CLAMD_BIAS_BORDER_CLASSES, forward launches behind a folded BatchNorm, see
  *   clamd_bn_fold_bias below) = `bias` is a [9][Cout_p] table indexed by the border class of the output pixel.  Bit 1 is taken by
  *   clamd_conv3x3 where clamd_conv3x3_border_bias_ok() says so (the persistent kernel), by clamd_conv3x3_winograd24 and by

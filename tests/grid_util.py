@@ -1,5 +1,6 @@
-"""Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py): poisoned buffers with guard
-bands, the two-runs check, the storage rounding of the three dtypes and the per-element comparison against a float64 reference."""
+"""Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py, test_conv3_grid_gpu.py): poisoned
+buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit expectations, the two-runs check, the
+storage rounding of the three dtypes and the per-element comparison against a float64 reference."""
 import math
 
 import numpy as np
@@ -105,3 +106,94 @@ def _per_element(what, key, got, ref, bound):
     print(f'{what}: worst error / bound {worst:.3f} at {idx} (largest so far for {key}: {RATIOS[key]:.3f})')
     assert worst <= 1.0, (f'{what}: element {idx}: got {float(got[idx])!r}, reference {float(ref[idx])!r}, bound {float(bound[idx]):.3e}, '
                           f'error / bound {worst:.3f}')
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ buffers
+class ActAt(Act):
+    """An Act whose `cp` channels start at channel `c0` of the pitch: the second half of a concat buffer, the first half poisoned."""
+
+    def __init__(self, C, npix, cp, ldc, dcode, c0=0, values=None):
+        super().__init__(C, npix, cp, ldc, dcode, values)
+        self.c0 = c0
+        if c0:
+            filled = self.view[:, :cp].clone()
+            self.buf.fill_(POISON)
+            self.view = self.view_of(self.buf)
+            self.view[:, :cp] = filled
+            self.before = self.buf.clone()
+
+    def view_of(self, buf):
+        return buf.as_strided((self.npix, self.ldc - self.c0), (self.ldc, 1), GUARD + self.c0)
+
+    def guards_intact(self):
+        a = self.buf.clone()
+        self.view_of(a)[:, :self.cp] = self.view_of(self.before)[:, :self.cp]
+        return torch.equal(_raw(a), _raw(self.before))
+
+
+def _half(C, npix, cp, mult, dcode, values=None):
+    """mult 1: the tensor at its own pitch; 2: the second half of a buffer of pitch 2 cp."""
+    return ActAt(C, npix, cp, mult * cp, dcode, (mult - 1) * cp, values)
+
+
+def _expect_bits(what, out, exp32):
+    """The stored bits of `out` are storage(exp32) (fp32 [npix, cp]); the worst element on failure."""
+    exp = out.C.ops.split_encode(exp32.contiguous()) if out.dcode == 2 else exp32.to(out.buf.dtype)
+    got = out.view[:, :out.cp].contiguous()
+    if torch.equal(_raw(got), _raw(exp)):
+        return
+    gv, ev = out.get().double(), _store_round(exp32, out.dcode).double()
+    d = torch.nan_to_num((gv - ev).abs(), nan=float('inf'))
+    idx = np.unravel_index(int(d.argmax()), tuple(d.shape))
+    raise AssertionError(f'{what}: {int((d != 0).sum())} elements differ from storage(exact result); worst at (pixel, channel) {idx}: '
+                         f'got {float(gv[idx])!r}, expected {float(ev[idx])!r}' + (' (the values agree: a sign of zero)' if not bool(d.any()) else ''))
+
+
+def _expect_rows(what, rows, exp):
+    """fp32 / int64 rows equal `exp` bit for bit; the worst element on failure."""
+    got = rows.view.reshape(exp.shape)
+    if torch.equal(_raw(got.contiguous()), _raw(exp.to(got.dtype).contiguous())):
+        return
+    d = torch.nan_to_num((got.double() - exp.double()).abs(), nan=float('inf'))
+    idx = np.unravel_index(int(d.argmax()), tuple(d.shape))
+    raise AssertionError(f'{what}: {int((d != 0).sum())} elements differ; worst at {idx}: got {float(got[idx])!r}, expected {float(exp[idx])!r}')
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- inputs
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _ints(rng, shape, amax, zeros):
+    """Integers in [-amax, amax] with `zeros` of them cleared on top of the uniform share: about a quarter zeros in all."""
+    v = rng.integers(-amax, amax + 1, size=shape)
+    v[rng.random(shape) < zeros] = 0
+    return _dev(v.astype(np.float32))
+
+
+def _normal(rng, shape, dcode, zeros=0.25):
+    """Standard normal, a quarter exact zeros, rounded to what the storage holds; bf16x3: lo = rne(x - hi) kept where |lo| <= 2^-9 |x|."""
+    x = torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
+    x[torch.from_numpy(rng.random(shape) < zeros)] = 0.0
+    if dcode:
+        hi = x.to(torch.bfloat16).float()
+        lo = (x - hi).to(torch.bfloat16).float()
+        x = hi if dcode == 1 else hi + torch.where(lo.abs() <= 2.0 ** -9 * (hi + lo).abs(), lo, torch.zeros(()))
+    x = x.to(DEV)
+    assert torch.equal(_store_round(x, dcode), x)
+    if dcode == 2:
+        hi = x.to(torch.bfloat16).float()
+        assert bool((x != hi).any()) and bool(((x - hi).abs() <= 2.0 ** -9 * x.abs()).all())
+    return x
+
+
+def _pad2(w, n, k):
+    out = torch.zeros(n, k, device=w.device, dtype=w.dtype)
+    out[:w.shape[0], :w.shape[1]] = w
+    return out
+
+
+def _operand(C, w, dcode):
+    """fp32 [..., K] in a documented packed layout -> the device operand of the compute dtype (bf16x3: split on the innermost dimension)."""
+    w = w.contiguous()
+    return C.ops.split_encode(w) if dcode == 2 else w.to(C.ops.TORCH_DT[dcode])

@@ -244,6 +244,12 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
     below must fail validation (null pointers are never dereferenced)."""
     lib = C._lib.load()
     call = C._lib.call
+    keep = []                            # Tuning objects passed by address stay alive until the test ends
+
+    def tref(**kw):
+        keep.append(C._lib.Tuning(**kw))
+        return keep[-1].ref()
+
     cases = [
         ('empty problem', 'clamd_conv3x3', (None, 32, None, None, None, 32, None, None, None, 0, 0, 16, 16, 32, 32, 1, 0, 0, None, None)),
         ('padded', 'clamd_conv3x3', (None, 32, None, None, None, 32, None, None, None, 0, 1, 16, 16, 24, 32, 1, 0, 0, None, None)),
@@ -261,12 +267,72 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
         ('sum_rows', 'clamd_bn_bwd_reduce', (1, 32, None, 0, 1, 32, None, None, 1, 3, 1, 16, 16, 32, 0, None, None)),
         ('workspace too small', 'clamd_channel_sum', (1, 32, 1, 64, 32, 32, 0, None, 0, None, None)),
         ('empty job table', 'clamd_wino_pack', (None, 0, 0, None)),
+        ('bad relu flags', 'clamd_conv3x3', (None, 32, None, None, None, 32, None, None, None, 0, 1, 16, 16, 32, 32, 4, 0, 0, None, None)),
+        ('bn_y and bn_sums go together', 'clamd_conv3x3', (None, 32, None, None, None, 32, None, 0x1000, None, 0, 1, 16, 16, 32, 32, 0, 0, 0, None, None)),
+        ('bn_y and bn_sums go together', 'clamd_conv3x3', (None, 32, None, None, None, 32, None, None, 0x1000, 4, 1, 16, 16, 32, 32, 0, 0, 0, None, None)),
+        ('padded', 'clamd_conv3x3', (None, 36, None, None, None, 32, None, None, None, 0, 1, 16, 16, 32, 32, 1, 0, 0, None, None)),
+        ('padded', 'clamd_conv3x3', (None, 32, None, None, None, 36, None, None, None, 0, 1, 16, 16, 32, 32, 1, 0, 0, None, None)),
+        # Kp = 48: the persistent kernel's own "K-steps in pairs" rule (Kp % 32 in fp32) can never be what declines a shape
+        ('padded', 'clamd_conv3x3', (None, 48, None, None, None, 32, None, None, None, 0, 1, 16, 16, 48, 32, 1, 0, 0, None, None)),
+        ('border-class bias table', 'clamd_conv3x3', (None, 64, None, None, None, 64, None, None, None, 0, 1, 16, 16, 64, 64, 3, 0, 0, None, None)),
+        ('padded', 'clamd_wgrad', (0, None, 40, None, 32, None, 0, None, 1, 16, 16, 40, 32, 40, 32, 40, 40, 32, 32, 0, None, None)),
+        ('padded', 'clamd_wgrad', (0, None, 32, None, 36, None, 0, None, 1, 16, 16, 32, 32, 32, 32, 32, 32, 32, 32, 0, None, None)),
+        ('workspace too small', 'clamd_wgrad', (0, None, 32, None, 32, None, 0, None, 1, 16, 16, 32, 32, 32, 32, 32, 32, 32, 32, 0, None, None)),
+        ('workspace too small', 'clamd_wgrad', (2, None, 32, None, 32, None, 4 * 4 * 32 * 32 - 1, None, 1, 2, 16, 32, 32, 32, 32, 32, 32, 32, 32, 1,
+                                                tref(wgrad_blocks=1), None)),
     ]
     for needle, name, args in cases:
         with pytest.raises(RuntimeError) as e:
             call(name, *args)
         assert needle in str(e.value), (name, str(e.value))
         assert needle in lib.clamd_last_error().decode()
+    # clamd_conv3x3_border_bias_ok / clamd_conv3x3_bn_sums / clamd_stat_rows(CLAMD_OP_CONV3X3) over the branches of plan_conv3x3 and pws_rows:
+    # the persistent kernel takes igemm_pws 2, or 1 up to 256 input channels; K-steps in pairs (Kp % 64 in bf16); bn_y only in bf16
+    ok = lambda H, W, Kp, dt, **kw: lib.clamd_conv3x3_border_bias_ok(2, H, W, Kp, 64, dt, tref(**kw) if kw else None)
+    assert [ok(16, 16, 64, dt) for dt in (0, 1, 2)] == [1, 1, 1]
+    assert [ok(16, 16, Kp, 1) for Kp in (32, 64, 96, 128, 256, 512)] == [0, 1, 0, 1, 1, 0]
+    assert [ok(16, 16, Kp, 0) for Kp in (32, 96, 256, 288)] == [1, 1, 1, 0] and ok(16, 16, 512, 0, igemm_pws=2) == 1
+    assert ok(16, 16, 64, 0, igemm_pws=0) == 0 and ok(16, 16, 64, 0, igemm_pws=0, igemm_ws=1) == 0
+    assert ok(1, 16, 64, 0) == 0 and ok(16, 1, 64, 0) == 0 and ok(2, 2, 64, 0) == 1
+    assert lib.clamd_conv3x3_border_bias_ok(0, 16, 16, 64, 64, 0, None) == 0
+    bad = C._lib.Tuning()
+    bad.igemm_pws = 3
+    assert lib.clamd_conv3x3_border_bias_ok(2, 16, 16, 64, 64, 0, bad.ref()) == 0 and lib.clamd_conv3x3_bn_sums(2, 16, 16, 64, 64, 1, bad.ref()) == 0
+    sums = lambda Kp, dt, **kw: lib.clamd_conv3x3_bn_sums(2, 16, 16, Kp, 64, dt, tref(**kw) if kw else None)
+    assert [sums(64, dt) for dt in (0, 1, 2)] == [5, 2, 5]
+    assert [sums(Kp, 1) for Kp in (32, 64, 96, 256, 512)] == [5, 2, 5, 2, 5] and sums(512, 1, igemm_pws=2) == 2 and sums(64, 1, igemm_pws=0) == 5
+    assert lib.clamd_conv3x3_bn_sums(0, 16, 16, 64, 64, 1, None) == 0 and lib.clamd_conv3x3_bn_sums(2, 16, 0, 64, 64, 1, None) == 0
+    rows = lambda shape, Kp, Np, dt, bn, **kw: lib.clamd_stat_rows(C._lib.OP_CONV3X3, *shape, Kp, Np, dt, bn, tref(**kw))
+    assert rows((2, 40, 128), 64, 256, 0, 0, igemm_pws=2, cu_reserve=128) == 32           # (256 - 128) CUs / 4 slabs
+    assert rows((2, 40, 128), 64, 256, 0, 0, igemm_pws=2, cu_reserve=0) == 40            # clamped to the 40 tiles
+    assert rows((2, 40, 128), 64, 256, 0, 1, igemm_pws=2, igemm_ws=0, cu_reserve=128) == 40      # fp32 declines bn_y: the baseline's tiles
+    assert rows((2, 40, 128), 64, 256, 1, 1, igemm_pws=2, igemm_ws=0, cu_reserve=128) == 32
+    assert rows((2, 40, 128), 32, 256, 1, 0, igemm_pws=2, igemm_ws=3, cu_reserve=128) == 2 * 3 * 4    # bf16 declines Kp 32: 512-pixel tiles
+    assert [rows((2, 17, 18), 64, 64, 0, 0, igemm_pws=0, igemm_ws=w) for w in (0, 1, 3, 4)] == [8, 8, 8, 12]      # W < 32: 512-pixel tiles clamp to 256
+    assert [rows((1, 9, 36), 64, 64, 0, 0, igemm_pws=0, igemm_ws=w) for w in (0, 1, 3, 4)] == [4, 4, 2, 6]
+
+
+@pytest.fixture
+def conv3_grid(monkeypatch):
+    """tests/test_conv3_grid_gpu.py with its tensors on the host: its case lists, its copies of the launchers' rules and its float64
+    references need no device, only its launches and comparisons do."""
+    import grid_util
+    import test_conv3_grid_gpu as grid
+    for mod in (grid_util, grid):
+        monkeypatch.setattr(mod, 'DEV', torch.device('cpu'))
+    return grid
+
+
+def test_conv3_grid_cases_reach_every_instantiation(conv3_grid):
+    """The rows of test_conv3_grid_gpu.py start every kernel instantiation its path table names: all 8 (fp32, bf16x3) and 16 (bf16) of
+    launch_pws_t, every baseline and producer/consumer one, every reduce kernel and split class of clamd_wgrad."""
+    conv3_grid.check_conv3x3_plans()
+    conv3_grid.check_wgrad_plans()
+
+
+def test_conv3_grid_exact_cases_stay_below_2_24(conv3_grid):
+    """Every exact-integer case of test_conv3_grid_gpu.py keeps every sum of absolute terms below 2^24, from its references alone."""
+    conv3_grid.check_exact_conditions()
 
 
 def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):

@@ -311,7 +311,8 @@ def test_conv3x3_dgrad_and_wgrad(C, name, dcode, shape):
     got = bsums.sum(0).cpu().numpy()[:, [p for p, l in enumerate(pm_) if l >= 0]]
     nsums = lib.load().clamd_conv3x3_bn_sums(B, H, W, cout_p, cin_p, dcode, None)
     assert nsums in (2, 5) and (nsums == 5 or dcode == 1)
-    assert lib.load().clamd_conv3x3_bn_sums(B, H, W, cout_p, cin_p, dcode, lib.Tuning(igemm_pws=0).ref()) == 5      # the other structures: all five
+    no_pws = lib.Tuning(igemm_pws=0)      # kept in a name: ref() is a bare address, the structure must outlive the call
+    assert lib.load().clamd_conv3x3_bn_sums(B, H, W, cout_p, cin_p, dcode, no_pws.ref()) == 5      # the other structures: all five
     if nsums == 2:      # the persistent bf16 kernel: sum g and sum g y only, rows 2-4 written as NaN (clamd_bn_bwd_apply_sums gives d conv-bias;
         #                 a finalize that still asks for dbias from these rows gets NaN, not a silent zero)
         bs = bsums.cpu().numpy()
