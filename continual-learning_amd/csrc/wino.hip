@@ -415,31 +415,55 @@ int wino_band(long long tiles, long long slabs, double x_elems, double f_elems, 
     return best;
 }
 
+int wino_forward_plan(WinoParams& p, WinoTile t, long long slabs, double x_elems, double f_elems, long long grid_cap, int stat_rows,
+                      long long want_rows, const clamd_tuning& tn, const char* who, const char* op, WinoGrid* g) {
+    const long long tiles = wino_tiles(t, p.B, p.H, p.W);
+    if (tiles * slabs > 0x7fffffff) return wino_fail(who, "grid out of range");
+    if (p.stats && stat_rows != want_rows) {
+        char what[128];
+        snprintf(what, sizeof(what), "stat_rows does not match clamd_stat_rows(%s, ...)", op);
+        return wino_fail(who, what);
+    }
+    p.band = wino_band(tiles, slabs, x_elems, f_elems, tn.wino_band);
+    p.nblk = (int)(tiles * slabs);
+    g->grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, grid_cap) : (unsigned)p.nblk;
+    g->ragged = (p.H % t.ph) != 0 || (p.W % t.pw) != 0;
+    return 0;
+}
+
+// one workgroup per CU the grid may occupy by default (wgrad_blocks = 512 counts two per CU, as for the direct kernels);
+// a larger target trades split-K slab traffic for smaller work items (robust when RCCL channels hold CUs)
+int wino_wgrad_nsplit(int ntiles, int blocks, const clamd_tuning& tn, int* per) {
+    int nsplit = (int)((long long)(tn.wgrad_blocks / 2) * clamd_usable_cus(tn) / clamd_num_cus()) / blocks;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > ntiles) nsplit = ntiles;
+    *per = (ntiles + nsplit - 1) / nsplit;
+    return (ntiles + *per - 1) / *per;
+}
+
+int wino_launch_pack(WinoPackKernel kernel, const char* who, const void* jobs_dev, int njobs, int total_blocks, const FoldBias* fold, hipStream_t stream) {
+    if (njobs <= 0 || total_blocks <= 0) return wino_fail(who, "empty job table");
+    const FoldBias f = fold ? *fold : FoldBias{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 9};
+    hipLaunchKernelGGL(kernel, dim3(total_blocks + (fold ? fold->Cout_p : 0)), dim3(256), 0, stream, (const WinoPackJob*)jobs_dev, njobs, total_blocks, f);
+    return clamd_check_launch(who);
+}
+
 }  // namespace clamd
 
 using namespace clamd;
 
 // 16x16-pixel tiles unless that grid would leave a quarter of the CUs without a workgroup
 static bool wino_mt2(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
-    const long long ntn = (Cout_p + 63) / 64, nblk2 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ntn;
-    const long long nblk1 = (long long)B * ((H + 7) / 8) * ((W + 15) / 16) * ntn;
+    const long long ntn = (Cout_p + 63) / 64, nblk2 = wino_tiles({16, 16}, B, H, W) * ntn, nblk1 = wino_tiles({8, 16}, B, H, W) * ntn;
     return tn.wino_mt ? tn.wino_mt == 2 : (nblk2 >= 192 || nblk1 == nblk2);
 }
-static long long wino_tiles(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
-    return (long long)B * ((H + (wino_mt2(B, H, W, Cout_p, tn) ? 15 : 7)) / (wino_mt2(B, H, W, Cout_p, tn) ? 16 : 8)) * ((W + 15) / 16);
-}
-// rows of a launch: one per pixel tile (one workgroup per tile), or one per workgroup of the persistent grid
+static WinoTile wino22_tile(int B, int H, int W, int Cout_p, const clamd_tuning& tn) { return {wino_mt2(B, H, W, Cout_p, tn) ? 16 : 8, 16}; }
 long long clamd_winograd_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
-    const long long tiles = wino_tiles(B, H, W, Cout_p, tn), nblk = tiles * ((Cout_p + 63) / 64);
-    return (tn.wino_persist && nblk > clamd_usable_cus(tn)) ? clamd_usable_cus(tn) : tiles;
+    return wino_stat_rows(wino_tiles(wino22_tile(B, H, W, Cout_p, tn), B, H, W), Cout_p, 64, 1, tn);
 }
 
 int clamd_launch_wino_pack(const void* jobs_dev, int njobs, int total_blocks, const clamd::FoldBias* fold, hipStream_t stream) {
-    if (njobs <= 0 || total_blocks <= 0) return clamd_fail("wino_pack: empty job table");
-    const clamd::FoldBias f = fold ? *fold : clamd::FoldBias{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 9};
-    hipLaunchKernelGGL(clamd::wino_pack_kernel, dim3(total_blocks + (fold ? fold->Cout_p : 0)), dim3(256), 0, stream, (const clamd::WinoPackJob*)jobs_dev, njobs,
-                       total_blocks, f);
-    return clamd_check_launch("wino_pack");
+    return wino_launch_pack(wino_pack_kernel, "wino_pack", jobs_dev, njobs, total_blocks, fold, stream);
 }
 
 extern "C" {
@@ -462,20 +486,17 @@ int clamd_conv3x3_winograd(const float* x, int x_ldc, const float* w_wino, const
     const clamd_tuning& tn = clamd_tune(tune);
     if (relu & ~1) return clamd_fail("conv3x3_winograd: relu must be 0 or 1 (no border-class bias here)");
     WinoParams p{x, x_ldc, w_wino, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu, 1, 0};
-    const long long ntn = (Cout_p + 63) / 64, nblk2 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ntn;
-    const long long nblk1 = (long long)B * ((H + 7) / 8) * ((W + 15) / 16) * ntn;
-    if (nblk1 > 0x7fffffff) return clamd_fail("conv3x3_winograd: grid out of range");
-    const bool mt2 = wino_mt2(B, H, W, Cout_p, tn);
-    p.band = wino_band((mt2 ? nblk2 : nblk1) / ntn, ntn, (double)B * H * W * Cin_p, 16.0 * Cin_p * Cout_p, tn.wino_band);
-    p.nblk = (int)(mt2 ? nblk2 : nblk1);
-    if (stats && stat_rows != clamd_winograd_stat_rows(B, H, W, Cout_p, tn))
-        return clamd_fail("conv3x3_winograd: stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD, ...)");
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    const bool ragged = (H % (mt2 ? 16 : 8)) != 0 || (W % 16) != 0 || (Cout_p % 64) != 0;
-#define WN_LAUNCH(MT_, RG_) hipLaunchKernelGGL((wino_kernel<MT_, RG_>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p)
-    if (mt2) { if (ragged) WN_LAUNCH(2, true); else WN_LAUNCH(2, false); }
-    else { if (ragged) WN_LAUNCH(1, true); else WN_LAUNCH(1, false); }
-#undef WN_LAUNCH
+    const long long ntn = (Cout_p + 63) / 64;
+    // the range is that of the 8-row tiles, whichever tile runs
+    if (wino_tiles({8, 16}, B, H, W) * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd: grid out of range");
+    const WinoTile t = wino22_tile(B, H, W, Cout_p, tn);
+    WinoGrid g;
+    if (int e = wino_forward_plan(p, t, ntn, (double)B * H * W * Cin_p, 16.0 * Cin_p * Cout_p, clamd_usable_cus(tn), stat_rows,
+                                  clamd_winograd_stat_rows(B, H, W, Cout_p, tn), tn, "conv3x3_winograd", "CLAMD_OP_CONV3X3_WINOGRAD", &g))
+        return e;
+    wino_dispatch(t.ph == 16, g.ragged || (Cout_p % 64) != 0, false, [&](auto mt2, auto ragged, auto) {
+        hipLaunchKernelGGL((wino_kernel<mt2() ? 2 : 1, ragged()>), dim3(g.grid), dim3(256), 0, (hipStream_t)stream, p);
+    });
     return clamd_check_launch("conv3x3_winograd");
 }
 
@@ -735,11 +756,6 @@ __global__ void __launch_bounds__(256, 1) wino_wgrad_kernel(const WinoWgradParam
 }
 
 // out[rl][cl][3][3] = G^T (sum_s dU_s) G.  256 threads = 16 (r,c) pairs x 4 planes x 4 split-phases.
-struct WinoReduceParams {
-    const float* partial; float* out;
-    int nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p;
-};
-
 __global__ void __launch_bounds__(256) wino_wgrad_reduce_kernel(const WinoReduceParams p) {
     SIDE_PRIO();
     __shared__ float4 red[4][4][16];                                   // [phase][plane][pair]
@@ -800,17 +816,11 @@ __global__ void __launch_bounds__(256) wino_wgrad_reduce_kernel(const WinoReduce
 extern "C" {
 
 #ifdef CLAMD_DIAG
-int clamd_debug_ww_diag(unsigned long long* out4, int reset) {
-    if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(clamd::g_ww_diag), 32) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[4] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(clamd::g_ww_diag), z, 32) != hipSuccess) return -1; }
-    return 0;
-}
+CLAMD_DIAG_READER(clamd_debug_ww_diag, clamd::g_ww_diag, 4)
 #endif
 
 size_t clamd_wgrad_winograd_workspace_bytes(int Rp, int Cp) {
-    int nsplit = 512 / (((Rp + 63) / 64) * ((Cp + 63) / 64));      // upper bound over every value of wgrad_blocks (<= 1024)
-    if (nsplit < 1) nsplit = 1;
-    return (size_t)nsplit * 16 * Rp * Cp * sizeof(float);
+    return (size_t)wino_wgrad_max_split(((Rp + 63) / 64) * ((Cp + 63) / 64)) * 16 * Rp * Cp * sizeof(float);
 }
 
 int clamd_wgrad_winograd(const float* gz, int gz_ldc, const float* x, int x_ldc, float* workspace, size_t ws_bytes, float* out,
@@ -822,21 +832,15 @@ int clamd_wgrad_winograd(const float* gz, int gz_ldc, const float* x, int x_ldc,
     if ((H | W) & 1) return clamd_fail("wgrad_winograd: H and W must be even");
     if (Rp % 32 || Cp % 32 || gz_ldc % 8 || x_ldc % 8) return clamd_fail("wgrad_winograd: channel counts/pitches must be padded");
     if ((long long)H * W * gz_ldc * 4 >= (1ll << 30) || (long long)H * W * x_ldc * 4 >= (1ll << 30)) return clamd_fail("wgrad_winograd: one image exceeds 2^30 bytes");
-    const int rt = (Rp + 63) / 64, ct = (Cp + 63) / 64;
+    const int blocks = ((Rp + 63) / 64) * ((Cp + 63) / 64);
     const int ntiles = ((W + 2 * WW_TX - 1) / (2 * WW_TX)) * ((H + 2 * WW_TY - 1) / (2 * WW_TY)) * B;
-    // one workgroup per CU the grid may occupy by default (wgrad_blocks = 512 counts two per CU, as for the direct kernels);
-    // a larger target trades split-K slab traffic for smaller work items (robust when RCCL channels hold CUs)
-    const clamd_tuning& tn = clamd_tune(tune);
-    int nsplit = (int)((long long)(tn.wgrad_blocks / 2) * clamd_usable_cus(tn) / clamd_num_cus()) / (rt * ct);
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > ntiles) nsplit = ntiles;
-    const int per = (ntiles + nsplit - 1) / nsplit;
-    nsplit = (ntiles + per - 1) / per;
+    int per = 0;
+    const int nsplit = wino_wgrad_nsplit(ntiles, blocks, clamd_tune(tune), &per);
     if ((size_t)nsplit * 16 * Rp * Cp * sizeof(float) > ws_bytes) return clamd_fail("wgrad_winograd: workspace too small");
     WinoWgradParams p{gz, gz_ldc, x, x_ldc, workspace, B, H, W, Rp, Cp, nsplit, per};
     hipStream_t s = (hipStream_t)stream;
-    if (H % (2 * WW_TY) || W % (2 * WW_TX)) hipLaunchKernelGGL(wino_wgrad_kernel<true>, dim3(rt * ct * nsplit), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(wino_wgrad_kernel<false>, dim3(rt * ct * nsplit), dim3(256), 0, s, p);
+    if (H % (2 * WW_TY) || W % (2 * WW_TX)) hipLaunchKernelGGL(wino_wgrad_kernel<true>, dim3(blocks * nsplit), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino_wgrad_kernel<false>, dim3(blocks * nsplit), dim3(256), 0, s, p);
     if (int e = clamd_check_launch("wgrad_winograd")) return e;
     WinoReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
     long long g = ((long long)Rp * Cp + 15) / 16;

@@ -465,11 +465,7 @@ __global__ void __launch_bounds__(256) wino24_pack_kernel(const WinoPackJob* __r
 using namespace clamd;
 
 int clamd_launch_wino24_pack(const void* jobs_dev, int njobs, int total_blocks, const clamd::FoldBias* fold, hipStream_t stream) {
-    if (njobs <= 0 || total_blocks <= 0) return clamd_fail("wino24_pack: empty job table");
-    const clamd::FoldBias f = fold ? *fold : clamd::FoldBias{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 9};
-    hipLaunchKernelGGL(clamd::wino24_pack_kernel, dim3(total_blocks + (fold ? fold->Cout_p : 0)), dim3(256), 0, stream, (const clamd::WinoPackJob*)jobs_dev, njobs,
-                       total_blocks, f);
-    return clamd_check_launch("wino24_pack");
+    return wino_launch_pack(wino24_pack_kernel, "wino24_pack", jobs_dev, njobs, total_blocks, fold, stream);
 }
 
 extern "C" {
@@ -479,11 +475,7 @@ int clamd_wino24_pack(const void* jobs_dev, int njobs, int total_blocks, void* s
 }
 
 #ifdef CLAMD_DIAG
-int clamd_debug_w24_diag(unsigned long long* out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(clamd::g_w24_diag), 64) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(clamd::g_w24_diag), z, 64) != hipSuccess) return -1; }
-    return 0;
-}
+CLAMD_DIAG_READER(clamd_debug_w24_diag, clamd::g_w24_diag, 8)
 #endif
 
 int clamd_conv3x3_winograd24(const float* x, int x_ldc, const float* w_wino, const float* bias, float* y, int y_ldc,
@@ -505,42 +497,21 @@ int clamd_conv3x3_winograd24(const float* x, int x_ldc, const float* w_wino, con
 
 namespace clamd {
 
-// workgroup tile: 8 x 32 pixels, or 16 x 16 for images narrower than 32
-static inline void w24_tile(int W, int& ph, int& pw) { if (W >= 32) { ph = 8; pw = 32; } else { ph = 16; pw = 16; } }
-
-static long long w24_tiles(int B, int H, int W) {
-    int ph, pw;
-    w24_tile(W, ph, pw);
-    return (long long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
-}
-
-// rows of a launch: one per pixel tile (one workgroup per tile), or one per workgroup of the persistent grid
 long long clamd_winograd24_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
     if (tn.wino_half) return clamd_winograd24_half_stat_rows(B, H, W, Cout_p, tn);
-    const long long tiles = w24_tiles(B, H, W), nblk = tiles * ((Cout_p + 63) / 64);
-    return (tn.wino_persist && nblk > clamd_usable_cus(tn)) ? clamd_usable_cus(tn) : tiles;
+    return wino_stat_rows(wino_tiles(w24_tile(W), B, H, W), Cout_p, 64, 1, tn);
 }
 
 int launch_wino24(WinoParams p, const clamd_tuning& tn, int stat_rows, hipStream_t stream) {
     if (tn.wino_half) return launch_wino24_half(p, tn, stat_rows, stream);
-    int ph, pw;
-    w24_tile(p.W, ph, pw);
-    const long long ntn = (p.Np + 63) / 64, tiles = w24_tiles(p.B, p.H, p.W);
-    if (tiles * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd24: grid out of range");
-    if (p.stats && stat_rows != clamd_winograd24_stat_rows(p.B, p.H, p.W, p.Np, tn))
-        return clamd_fail("conv3x3_winograd24: stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD24, ...)");
-    p.band = wino_band(tiles, ntn, (double)p.B * p.H * p.W * p.Kp, 24.0 * p.Kp * p.Np, tn.wino_band);
-    p.nblk = (int)(tiles * ntn);
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    const bool ragged = (p.H % ph) != 0 || (p.W % pw) != 0 || (p.Np % 64) != 0;
-#define W24_LAUNCH(TXN_, RG_)                                                                                          \
-    do {                                                                                                               \
-        if (p.bias_classes) hipLaunchKernelGGL((wino24_kernel<TXN_, RG_, true>), dim3(grid), dim3(256), 0, stream, p);  \
-        else hipLaunchKernelGGL((wino24_kernel<TXN_, RG_, false>), dim3(grid), dim3(256), 0, stream, p);               \
-    } while (0)
-    if (pw == 32) { if (ragged) W24_LAUNCH(8, true); else W24_LAUNCH(8, false); }
-    else { if (ragged) W24_LAUNCH(4, true); else W24_LAUNCH(4, false); }
-#undef W24_LAUNCH
+    const WinoTile t = w24_tile(p.W);
+    WinoGrid g;
+    if (int e = wino_forward_plan(p, t, (p.Np + 63) / 64, (double)p.B * p.H * p.W * p.Kp, 24.0 * p.Kp * p.Np, clamd_usable_cus(tn), stat_rows,
+                                  clamd_winograd24_stat_rows(p.B, p.H, p.W, p.Np, tn), tn, "conv3x3_winograd24", "CLAMD_OP_CONV3X3_WINOGRAD24", &g))
+        return e;
+    wino_dispatch(t.pw == 32, g.ragged || (p.Np % 64) != 0, p.bias_classes != 0, [&](auto wide, auto ragged, auto cls) {
+        hipLaunchKernelGGL((wino24_kernel<wide() ? 8 : 4, ragged(), cls()>), dim3(g.grid), dim3(256), 0, stream, p);
+    });
     return clamd_check_launch("conv3x3_winograd(F(2x4))");
 }
 

@@ -238,12 +238,7 @@ __global__ void __launch_bounds__(256, 1) wino24_wgrad_kernel(const Wino24WgradP
 }
 
 // out[rl][cl][3][3] = G4^T (sum_s dU_s) G6.  256 threads = 16 (r,c) pairs x 4 planes x 4 split-phases (fixed order: deterministic).
-struct Wino24ReduceParams {
-    const float* partial; float* out;
-    int nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p;
-};
-
-__global__ void __launch_bounds__(256) wino24_wgrad_reduce_kernel(const Wino24ReduceParams p) {
+__global__ void __launch_bounds__(256) wino24_wgrad_reduce_kernel(const WinoReduceParams p) {
     SIDE_PRIO();
     __shared__ float red[4][4][16][6];                                 // [phase][plane][pair][j]
     const int pr = threadIdx.x & 15, pl = (threadIdx.x >> 4) & 3, ph = threadIdx.x >> 6;
@@ -301,23 +296,10 @@ __global__ void __launch_bounds__(256) wino24_wgrad_reduce_kernel(const Wino24Re
 
 using namespace clamd;
 
-static int w24wg_nsplit(int B, int H, int W, int Rp, int Cp, const clamd_tuning& tn, int* per_out) {
-    const int rt = (Rp + 63) / 64, ct = (Cp + 31) / 32;
-    const int ntiles = ((W + V4_PW - 1) / V4_PW) * ((H + V4_PH - 1) / V4_PH) * B;
-    int nsplit = (int)((long long)(tn.wgrad_blocks / 2) * clamd_usable_cus(tn) / clamd_num_cus()) / (rt * ct);
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > ntiles) nsplit = ntiles;
-    const int per = (ntiles + nsplit - 1) / nsplit;
-    if (per_out) *per_out = per;
-    return (ntiles + per - 1) / per;
-}
-
 extern "C" {
 
 size_t clamd_wgrad_winograd24_workspace_bytes(int Rp, int Cp) {
-    int nsplit = 512 / (((Rp + 63) / 64) * ((Cp + 31) / 32));      // upper bound over every value of wgrad_blocks (<= 1024)
-    if (nsplit < 1) nsplit = 1;
-    return (size_t)nsplit * 4 * 8 * Rp * Cp * sizeof(float);
+    return (size_t)wino_wgrad_max_split(((Rp + 63) / 64) * ((Cp + 31) / 32)) * 4 * 8 * Rp * Cp * sizeof(float);
 }
 
 int clamd_wgrad_winograd24(const float* gz, int gz_ldc, const float* x, int x_ldc, float* workspace, size_t ws_bytes, float* out,
@@ -328,17 +310,17 @@ int clamd_wgrad_winograd24(const float* gz, int gz_ldc, const float* x, int x_ld
     if ((H & 1) || (W & 3)) return clamd_fail("wgrad_winograd24: H must be even and W a multiple of 4");
     if (Rp % 32 || Cp % 32 || gz_ldc % 8 || x_ldc % 8) return clamd_fail("wgrad_winograd24: channel counts/pitches must be padded");
     if ((long long)H * W * gz_ldc * 4 >= (1ll << 30) || (long long)H * W * x_ldc * 4 >= (1ll << 30)) return clamd_fail("wgrad_winograd24: one image exceeds 2^30 bytes");
-    const clamd_tuning& tn = clamd_tune(tune);
     const int rt = (Rp + 63) / 64, ct = (Cp + 31) / 32;
+    const int ntiles = ((W + V4_PW - 1) / V4_PW) * ((H + V4_PH - 1) / V4_PH) * B;
     int per = 0;
-    const int nsplit = w24wg_nsplit(B, H, W, Rp, Cp, tn, &per);
+    const int nsplit = wino_wgrad_nsplit(ntiles, rt * ct, clamd_tune(tune), &per);
     if ((size_t)nsplit * 4 * 8 * Rp * Cp * sizeof(float) > ws_bytes) return clamd_fail("wgrad_winograd24: workspace too small");
     Wino24WgradParams p{gz, gz_ldc, x, x_ldc, workspace, B, H, W, Rp, Cp, nsplit, per};
     hipStream_t s = (hipStream_t)stream;
     if (H % V4_PH || W % V4_PW) hipLaunchKernelGGL(wino24_wgrad_kernel<true>, dim3(rt * ct * nsplit), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(wino24_wgrad_kernel<false>, dim3(rt * ct * nsplit), dim3(256), 0, s, p);
     if (int e = clamd_check_launch("wgrad_winograd24")) return e;
-    Wino24ReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
+    WinoReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
     long long g = ((long long)Rp * Cp + 15) / 16;
     if (g > 16384) g = 16384;
     hipLaunchKernelGGL(wino24_wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, rp);

@@ -827,13 +827,8 @@ __global__ void __launch_bounds__(256, 1) wino24g_wgrad_kernel(const W24WgGemmPa
 // out[rl][cl][3][3] = G4^T (sum_s dU_s) G6.  A thread owns four consecutive (r, c) pairs (16-byte loads of all 24 planes); the
 // splits are dealt to PHS lane groups of a wave and combined with two fixed shuffle steps: the summation order is fixed
 // (deterministic).  Plane row i = 2 carries the forward image's sign convention (row 2 of B4^T negated) and is flipped here.
-struct W24GReduceParams {
-    const float* partial; float* out;
-    int nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p;
-};
-
 template <int PHS>
-__global__ void __launch_bounds__(256) wino24g_wgrad_reduce_kernel(const W24GReduceParams p) {
+__global__ void __launch_bounds__(256) wino24g_wgrad_reduce_kernel(const WinoReduceParams p) {
     SIDE_PRIO();
     constexpr int QW = 64 / PHS;                                       // quads per wave
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1176,14 +1171,6 @@ __global__ void __launch_bounds__(256) wino_sk_reduce_kernel(const W24SkReducePa
     }
 }
 
-// workgroup tile of the forward kernels: 8 x 32 pixels, or 16 x 16 for images narrower than 32 (as wino24.hip)
-static inline void w24g_tile(int W, int& ph, int& pw) { if (W >= 32) { ph = 8; pw = 32; } else { ph = 16; pw = 16; } }
-static long long w24g_tiles(int B, int H, int W) {
-    int ph, pw;
-    w24g_tile(W, ph, pw);
-    return (long long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
-}
-
 }  // namespace clamd
 
 using namespace clamd;
@@ -1202,7 +1189,7 @@ int w24g_wg_plan_planes(long long Tp, int Rp, int Cp, int planes, const clamd_tu
     const int quant = 2 * W24G_D;
     const int nb = planes * (Rp / 256) * (Cp / 256);
     const int cus = clamd_usable_cus(tn);
-    const long long max_split = std::max<long long>(1, std::min<long long>((3LL * clamd_num_cus()) / nb, Tp / quant));
+    const long long max_split = w24g_wg_max_split(Tp, Rp, Cp, planes);
     double best = 0;
     long long best_ns = 1, best_per = Tp;
     for (long long ns = 1; ns <= max_split; ++ns) {
@@ -1292,61 +1279,182 @@ int launch_w24g_wgrad_skw(const float* yt, const float* v, float* workspace, siz
     else hipLaunchKernelGGL(wino_sk_reduce_kernel<36>, dim3(g), dim3(256), 0, s, rp);
     return clamd_check_launch("wgrad_winograd_pre (G^T . G)");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// entry points of the pre-transformed forms (F(2x4) below, F(4x4) in wino44g.hip), one body each over a WinoPreForm
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+struct PreName { char s[64]; operator const char*() const { return s; } };       // "<prefix><winograd24 | winograd44><suffix>"
+PreName pre_name(const char* prefix, const WinoPreForm& f, const char* suffix) {
+    PreName n;
+    snprintf(n.s, sizeof(n.s), "%s%s%s", prefix, f.name, suffix);
+    return n;
+}
+bool pre_bad_hw(const WinoPreForm& f, int H, int W) { return (H & f.hmask) || (W & 3); }
+int pre_fail_hw(const WinoPreForm& f, const char* who, bool note) {
+    char what[128];
+    snprintf(what, sizeof(what), "%s%s", f.hw_rule, note ? f.tile_note : "");
+    return wino_fail(who, what);
+}
+long long pre_tiles(const WinoPreForm& f, int B, int H, int W) { return wino_tiles(f.tile(W), B, H, W); }
+// Yt of gz: one thread per (tile, 4-channel group)
+int pre_launch_yt(const WinoPreForm& f, const char* what, const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, long long Tp, hipStream_t s) {
+    const long long na = (Tp * (Rp / 4) + 255) / 256;
+    f.launch_yt(W >= 32, (unsigned)std::min<long long>(na, 1 << 20), s, gz, gz_ldc, yt, B, H, W, Rp, (int)Tp);
+    return clamd_check_launch(what);
+}
+}  // namespace
+
+size_t wino_pre_input_elems(const WinoPreForm& f, int B, int H, int W, int Cp) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cp <= 0) return 0;
+    return (size_t)pre_tiles(f, B, H, W) * (size_t)(Cp / 8) * f.planes * 256;
+}
+
+int wino_pre_transform_input(const WinoPreForm& f, const float* x, int x_ldc, const float* scale, const float* shift, float* v, int B, int H, int W,
+                             int Cp, void* stream) {
+    const PreName who = pre_name("", f, "_transform_input");
+    if ((scale == nullptr) != (shift == nullptr)) return wino_fail(who, "scale and shift go together");
+    if (B <= 0 || H <= 0 || W <= 0) return wino_fail(who, "empty problem");
+    if (pre_bad_hw(f, H, W)) return pre_fail_hw(f, who, true);
+    if (Cp % 8 || x_ldc % 4 || x_ldc < Cp) return wino_fail(who, "channel count / pitch must be padded");
+    if ((long long)H * W * x_ldc * 4 >= (1ll << 31)) return wino_fail(who, "image exceeds 2^31 bytes");
+    const long long nwg = f.xform_wgs * pre_tiles(f, B, H, W), nkg = (Cp / 8 + 3) / 4;
+    if (nwg * nkg > 0x7fffffff) return wino_fail(who, "grid out of range");
+    f.launch_xform(f.tile(W).pw == 32, (unsigned)(nwg * nkg), (hipStream_t)stream, x, x_ldc, scale, shift, v, B, H, W, Cp);
+    return clamd_check_launch(who);
+}
+
+int wino_pre_conv3x3(const WinoPreForm& f, const float* v, const float* w_wino, const float* bias, float* y, int y_ldc, float* stats, int stat_rows,
+                     int B, int H, int W, int Cin_p, int Cout_p, int relu, const clamd_tuning* tune, void* stream) {
+    const PreName who = pre_name("conv3x3_", f, "_pre");
+    if (B <= 0 || H <= 0 || W <= 0) return wino_fail(who, "empty problem");
+    if (pre_bad_hw(f, H, W)) return pre_fail_hw(f, who, true);
+    if (Cin_p % f.cin_mult || Cin_p < f.cin_min || Cout_p % 64 || y_ldc % f.y_mult) {
+        char what[96];
+        snprintf(what, sizeof(what), "needs Cin_p %% %d == 0, Cin_p >= %d, Cout_p %% 64 == 0", f.cin_mult, f.cin_min);
+        return wino_fail(who, what);
+    }
+    if (int e = clamd_check_tuning(tune)) return e;
+    const clamd_tuning& tn = clamd_tune(tune);
+    const WinoTile t = f.tile(W);
+    const long long tiles = wino_tiles(t, B, H, W), ntn = Cout_p / 64;
+    if (tiles * ntn > 0x7fffffff) return wino_fail(who, "grid out of range");       // before the operand bound below; the shared tail repeats it
+    if ((unsigned long long)tiles * (Cin_p / 8) * f.planes * 1024 >= (1ull << 32) || (long long)f.planes * Cout_p * Cin_p * 4 >= (1ll << 31))
+        return wino_fail(who, "transformed input exceeds 2^32 bytes or filter 2^31 bytes");
+    WinoParams p{v, 0, w_wino, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu, 1, 0};
+    WinoGrid g;
+    if (int e = wino_forward_plan(p, t, ntn, f.band_x * B * H * W * Cin_p, (double)f.planes * Cin_p * Cout_p, clamd_usable_cus(tn), stat_rows,
+                                  f.stat_rows(B, H, W, Cout_p, tn), tn, who, f.op, &g))
+        return e;
+    if (relu & ~1) return wino_fail(who, "relu must be 0 or 1 (no border-class bias here)");
+    if (f.y_bound && (long long)H * W * y_ldc * 4 >= (1ll << 31)) return wino_fail(who, "one output image exceeds 2^31 bytes");
+    f.launch_conv(t.pw == 32, g.ragged, g.grid, (hipStream_t)stream, p);
+    return clamd_check_launch(who);
+}
+
+size_t wino_pre_operand_elems(const WinoPreForm& f, int B, int H, int W, int Rp) {
+    if (B <= 0 || H <= 0 || W <= 0 || Rp <= 0) return 0;
+    return (size_t)(f.planes * pre_tiles(f, B, H, W) * 32) * (size_t)Rp;
+}
+
+size_t wino_pre_workspace_bytes(const WinoPreForm& f, int B, int H, int W, int Rp, int Cp) {
+    if (B <= 0 || H <= 0 || W <= 0 || Rp < 128 || Cp < 128) return 0;
+    const long long Tp = pre_tiles(f, B, H, W) * 32;
+    if ((Rp % 256) || (Cp % 256)) return w24g_skw_workspace_bytes(Tp, Rp, Cp, f.planes);      // multiples of 128: the wave-level plan
+    return std::max((size_t)w24g_wg_max_split(Tp, Rp, Cp, f.planes) * f.planes * Rp * Cp * sizeof(float), w24g_sk_workspace_bytes(Tp, Rp, Cp, f.planes));
+}
+
+int wino_pre_wgrad(const WinoPreForm& f, const float* gz, int gz_ldc, const float* v, float* yt, float* workspace, size_t ws_bytes, float* out,
+                   int B, int H, int W, int Rp, int Cp, int R, int C, int r_seg0, int r_seg0p, int c_seg0, int c_seg0p, const clamd_tuning* tune,
+                   void* stream) {
+    const PreName who = pre_name("wgrad_", f, "_pre");
+    if (int e = clamd_check_tuning(tune)) return e;
+    if (B <= 0 || H <= 0 || W <= 0) return wino_fail(who, "empty problem");
+    if (pre_bad_hw(f, H, W)) return pre_fail_hw(f, who, false);
+    if (Rp % 128 || Cp % 128 || Rp <= 0 || Cp <= 0 || gz_ldc % 4) return wino_fail(who, "needs Rp and Cp multiples of 128");
+    const bool wave_level = (Rp % 256) || (Cp % 256);          // a wave owns a 128 x 128 block; 256 x 256 workgroup blocks where both counts allow
+    if (gz && (long long)H * W * gz_ldc * 4 >= (1ll << 31)) return wino_fail(who, "one image exceeds 2^31 bytes");
+    const clamd_tuning& tn = clamd_tune(tune);
+    const long long ntm = pre_tiles(f, B, H, W), Tp = ntm * 32;
+    if (Tp * Rp * 4 >= (1ll << 32) || (unsigned long long)ntm * (Cp / 8) * f.planes * 1024 >= (1ull << 32))
+        return wino_fail(who, "an operand exceeds 2^32 bytes");
+    int per = 0;
+    const int nsplit = wave_level ? 1 : w24g_wg_plan_planes(Tp, Rp, Cp, f.planes, tn, &per);
+    // stream-K where the items alone nearly fill the chip (an item then gets 2-3 slots); with fewer, larger items the split-K plan's
+    // whole rounds are as even and its slabs are fewer (tools/wino44g_ab.py: 1.10-1.21x faster from 96 items on, 0.78-0.95x below)
+    const bool streamk = wave_level || tn.wgrad_streamk == 2 ||
+                         (tn.wgrad_streamk == 1 && (long long)f.planes * (Rp / 256) * (Cp / 256) * 8 >= 3LL * clamd_usable_cus(tn));
+    if (!streamk && (size_t)nsplit * f.planes * Rp * Cp * sizeof(float) > ws_bytes) return wino_fail(who, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    if (gz)                                    // gz == NULL: yt already holds the transformed gradient (wino_pre_wgrad_transform)
+        if (int e = pre_launch_yt(f, pre_name("wgrad_", f, "_pre transform"), gz, gz_ldc, yt, B, H, W, Rp, Tp, s)) return e;
+    if (wave_level)
+        return launch_w24g_wgrad_skw(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, f.planes, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
+    if (streamk)
+        return launch_w24g_wgrad_sk(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, f.planes, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
+    if (int e = launch_w24g_wgrad_gemm(yt, v, workspace, Rp, Cp, Tp, nsplit, per, f.planes, s)) return e;
+    WinoReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
+    // a thread owns four (r, c) pairs; the splits are dealt to 4, 2 or 1 lane groups of a wave where that still fills the chip
+    const long long nquad = (long long)Rp * Cp / 4;
+    const int phs = (nsplit >= 4 && nquad <= 65536) ? 4 : (nsplit >= 2 && nquad <= 131072) ? 2 : 1;
+    f.launch_reduce(phs, (unsigned)std::min<long long>((nquad + 4 * (64 / phs) - 1) / (4 * (64 / phs)), 8192), s, rp);
+    return clamd_check_launch(pre_name("wgrad_", f, "_pre_reduce"));
+}
+
+// The gradient-side transform alone (Yt of gz, tiles in the order of the forward image): a caller with several streams can run it
+// beside another launch's GEMM and then call the weight gradient with gz == NULL.
+int wino_pre_wgrad_transform(const WinoPreForm& f, const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, void* stream) {
+    const PreName who = pre_name("wgrad_", f, "_pre_transform");
+    if (B <= 0 || H <= 0 || W <= 0 || !gz || !yt) return wino_fail(who, "bad arguments");
+    if (pre_bad_hw(f, H, W)) return pre_fail_hw(f, who, false);
+    if (Rp % 4 || Rp <= 0 || gz_ldc % 4) return wino_fail(who, "channel count / pitch must be padded");
+    const long long Tp = pre_tiles(f, B, H, W) * 32;
+    if ((long long)H * W * gz_ldc * 4 >= (1ll << 31) || Tp * Rp * 4 >= (1ll << 32)) return wino_fail(who, "operand too large");
+    return pre_launch_yt(f, f.yt_launch, gz, gz_ldc, yt, B, H, W, Rp, Tp, (hipStream_t)stream);
+}
+
+// ---- F(2x4): the form's description -----------------------------------------------------------------------------------
+static void w24_launch_xform(bool wide, unsigned grid, hipStream_t s, const float* x, int x_ldc, const float* scale, const float* shift, float* v,
+                             int B, int H, int W, int Cp) {
+    W24XformParams p{x, x_ldc, scale, shift, v, B, H, W, Cp};
+    if (wide) hipLaunchKernelGGL(wino24_xform_kernel<8>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino24_xform_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+}
+static void w24_launch_conv(bool wide, bool ragged, unsigned grid, hipStream_t s, const WinoParams& p) {
+    wino_dispatch(wide, ragged, false, [&](auto w, auto rg, auto) {
+        hipLaunchKernelGGL((wino24g_kernel<w() ? 8 : 4, rg(), 2>), dim3(grid), dim3(256), 0, s, p);
+    });
+}
+static void w24_launch_yt(bool wide, unsigned grid, hipStream_t s, const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, int Tp) {
+    W24WgXformParams p{gz, gz_ldc, yt, B, H, W, Rp, Tp};
+    if (wide) hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<8>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+}
+static void w24_launch_reduce(int phs, unsigned grid, hipStream_t s, const WinoReduceParams& p) {
+    if (phs == 4) hipLaunchKernelGGL(wino24g_wgrad_reduce_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+    else if (phs == 2) hipLaunchKernelGGL(wino24g_wgrad_reduce_kernel<2>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino24g_wgrad_reduce_kernel<1>, dim3(grid), dim3(256), 0, s, p);
+}
+static const WinoPreForm W24_FORM = {
+    "winograd24", "CLAMD_OP_CONV3X3_WINOGRAD24", "H must be even and W a multiple of 4", " (2x4 output tiles)",
+    /*planes*/ 24, /*hmask*/ 1, w24_tile, /*xform_wgs*/ 1, /*band_x*/ 3.0, /*cin_mult*/ 32, /*cin_min*/ 64, /*y_mult*/ 8, /*y_bound*/ false,
+    "wgrad_winograd24_pre_transform", clamd_winograd24_stat_rows, w24_launch_xform, w24_launch_conv, w24_launch_yt, w24_launch_reduce};
+
 }  // namespace clamd
-static int w24g_wg_plan(long long Tp, int Rp, int Cp, const clamd_tuning& tn, int* per_out) { return clamd::w24g_wg_plan_planes(Tp, Rp, Cp, 24, tn, per_out); }
 
 extern "C" {
 
-size_t clamd_winograd24_input_elems(int B, int H, int W, int Cp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Cp <= 0) return 0;
-    return (size_t)w24g_tiles(B, H, W) * (size_t)(Cp / 8) * 24 * 256;
-}
+size_t clamd_winograd24_input_elems(int B, int H, int W, int Cp) { return wino_pre_input_elems(W24_FORM, B, H, W, Cp); }
 
 int clamd_winograd24_transform_input(const float* x, int x_ldc, const float* scale, const float* shift, float* v, int B, int H, int W,
                                      int Cp, void* stream) {
-    if ((scale == nullptr) != (shift == nullptr)) return clamd_fail("winograd24_transform_input: scale and shift go together");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("winograd24_transform_input: empty problem");
-    if ((H & 1) || (W & 3)) return clamd_fail("winograd24_transform_input: H must be even and W a multiple of 4 (2x4 output tiles)");
-    if (Cp % 8 || x_ldc % 4 || x_ldc < Cp) return clamd_fail("winograd24_transform_input: channel count / pitch must be padded");
-    if ((long long)H * W * x_ldc * 4 >= (1ll << 31)) return clamd_fail("winograd24_transform_input: image exceeds 2^31 bytes");
-    int ph, pw;
-    w24g_tile(W, ph, pw);
-    const long long ntm = w24g_tiles(B, H, W), nkg = (Cp / 8 + 3) / 4;
-    if (ntm * nkg > 0x7fffffff) return clamd_fail("winograd24_transform_input: grid out of range");
-    W24XformParams p{x, x_ldc, scale, shift, v, B, H, W, Cp};
-    if (pw == 32) hipLaunchKernelGGL(wino24_xform_kernel<8>, dim3((unsigned)(ntm * nkg)), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wino24_xform_kernel<4>, dim3((unsigned)(ntm * nkg)), dim3(256), 0, (hipStream_t)stream, p);
-    return clamd_check_launch("winograd24_transform_input");
+    return wino_pre_transform_input(W24_FORM, x, x_ldc, scale, shift, v, B, H, W, Cp, stream);
 }
 
 int clamd_conv3x3_winograd24_pre(const float* v, const float* w_wino, const float* bias, float* y, int y_ldc,
                                  float* stats, int stat_rows, int B, int H, int W, int Cin_p,
                                  int Cout_p, int relu, const clamd_tuning* tune, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("conv3x3_winograd24_pre: empty problem");
-    if ((H & 1) || (W & 3)) return clamd_fail("conv3x3_winograd24_pre: H must be even and W a multiple of 4 (2x4 output tiles)");
-    if (Cin_p % 32 || Cin_p < 64 || Cout_p % 64 || y_ldc % 8) return clamd_fail("conv3x3_winograd24_pre: needs Cin_p % 32 == 0, Cin_p >= 64, Cout_p % 64 == 0");
-    if (int e = clamd_check_tuning(tune)) return e;
-    const clamd_tuning& tn = clamd_tune(tune);
-    const long long tiles = w24g_tiles(B, H, W), ntn = Cout_p / 64;
-    if (tiles * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd24_pre: grid out of range");
-    if ((unsigned long long)tiles * (Cin_p / 8) * 24 * 1024 >= (1ull << 32) || (long long)24 * Cout_p * Cin_p * 4 >= (1ll << 31))
-        return clamd_fail("conv3x3_winograd24_pre: transformed input exceeds 2^32 bytes or filter 2^31 bytes");
-    if (stats && stat_rows != clamd_winograd24_stat_rows(B, H, W, Cout_p, tn))
-        return clamd_fail("conv3x3_winograd24_pre: stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD24, ...)");
-    if (relu & ~1) return clamd_fail("conv3x3_winograd24_pre: relu must be 0 or 1 (no border-class bias here)");
-    WinoParams p{v, 0, w_wino, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu, 1, 0};
-    p.band = wino_band(tiles, ntn, 3.0 * B * H * W * Cin_p, 24.0 * Cin_p * Cout_p, tn.wino_band);
-    p.nblk = (int)(tiles * ntn);
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    int ph, pw;
-    w24g_tile(W, ph, pw);
-    const bool ragged = (H % ph) != 0 || (W % pw) != 0;
-    hipStream_t s = (hipStream_t)stream;
-#define W24G_LAUNCH(TXN_, RG_) hipLaunchKernelGGL((wino24g_kernel<TXN_, RG_, 2>), dim3(grid), dim3(256), 0, s, p)
-    if (pw == 32) { if (ragged) W24G_LAUNCH(8, true); else W24G_LAUNCH(8, false); }
-    else { if (ragged) W24G_LAUNCH(4, true); else W24G_LAUNCH(4, false); }
-#undef W24G_LAUNCH
-    return clamd_check_launch("conv3x3_winograd24_pre");
+    return wino_pre_conv3x3(W24_FORM, v, w_wino, bias, y, y_ldc, stats, stat_rows, B, H, W, Cin_p, Cout_p, relu, tune, stream);
 }
 
 int clamd_conv3x3_winograd24_direct_filters(const float* x, int x_ldc, const float* w_wino, const float* bias, float* y, int y_ldc,
@@ -1359,108 +1467,34 @@ int clamd_conv3x3_winograd24_direct_filters(const float* x, int x_ldc, const flo
         return clamd_fail("conv3x3_winograd24_direct_filters: image or filter exceeds 2^31 bytes");
     if (int e = clamd_check_tuning(tune)) return e;
     const clamd_tuning& tn = clamd_tune(tune);
-    const long long tiles = w24g_tiles(B, H, W), ntn = Cout_p / 64;
-    if (tiles * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd24_direct_filters: grid out of range");
-    if (stats && stat_rows != clamd_winograd24_stat_rows(B, H, W, Cout_p, tn))
-        return clamd_fail("conv3x3_winograd24_direct_filters: stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD24, ...)");
-    if ((relu & ~3) || ((relu & CLAMD_BIAS_BORDER_CLASSES) && !bias))
-        return clamd_fail("conv3x3_winograd24_direct_filters: bad relu flags (bit 1 needs the [9][Cout_p] bias table)");
     WinoParams p{x, x_ldc, w_wino, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu & 1, 1, 0};
     p.bias_classes = (relu & CLAMD_BIAS_BORDER_CLASSES) ? 1 : 0;
-    p.band = wino_band(tiles, ntn, (double)B * H * W * Cin_p, 24.0 * Cin_p * Cout_p, tn.wino_band);
-    p.nblk = (int)(tiles * ntn);
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    int ph, pw;
-    w24g_tile(W, ph, pw);
-    const bool ragged = (H % ph) != 0 || (W % pw) != 0;
-    hipStream_t s = (hipStream_t)stream;
-#define W24H_LAUNCH(TXN_, RG_)                                                                                         \
-    do {                                                                                                               \
-        if (p.bias_classes) hipLaunchKernelGGL((wino24h_kernel<TXN_, RG_, true>), dim3(grid), dim3(256), 0, s, p);     \
-        else hipLaunchKernelGGL((wino24h_kernel<TXN_, RG_, false>), dim3(grid), dim3(256), 0, s, p);                   \
-    } while (0)
-    if (pw == 32) { if (ragged) W24H_LAUNCH(8, true); else W24H_LAUNCH(8, false); }
-    else { if (ragged) W24H_LAUNCH(4, true); else W24H_LAUNCH(4, false); }
-#undef W24H_LAUNCH
+    const WinoTile t = w24_tile(W);
+    WinoGrid g;
+    if (int e = wino_forward_plan(p, t, Cout_p / 64, (double)B * H * W * Cin_p, 24.0 * Cin_p * Cout_p, clamd_usable_cus(tn), stat_rows,
+                                  clamd_winograd24_stat_rows(B, H, W, Cout_p, tn), tn, "conv3x3_winograd24_direct_filters",
+                                  "CLAMD_OP_CONV3X3_WINOGRAD24", &g))
+        return e;
+    if ((relu & ~3) || ((relu & CLAMD_BIAS_BORDER_CLASSES) && !bias))
+        return clamd_fail("conv3x3_winograd24_direct_filters: bad relu flags (bit 1 needs the [9][Cout_p] bias table)");
+    wino_dispatch(t.pw == 32, g.ragged, p.bias_classes != 0, [&](auto wide, auto ragged, auto cls) {
+        hipLaunchKernelGGL((wino24h_kernel<wide() ? 8 : 4, ragged(), cls()>), dim3(g.grid), dim3(256), 0, (hipStream_t)stream, p);
+    });
     return clamd_check_launch("conv3x3_winograd24_direct_filters");
 }
 
-size_t clamd_wgrad_winograd24_pre_operand_elems(int B, int H, int W, int Rp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Rp <= 0) return 0;
-    return (size_t)(24 * w24g_tiles(B, H, W) * 32) * (size_t)Rp;
-}
+size_t clamd_wgrad_winograd24_pre_operand_elems(int B, int H, int W, int Rp) { return wino_pre_operand_elems(W24_FORM, B, H, W, Rp); }
 
-size_t clamd_wgrad_winograd24_pre_workspace_bytes(int B, int H, int W, int Rp, int Cp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Rp < 128 || Cp < 128) return 0;
-    const long long Tp = w24g_tiles(B, H, W) * 32;
-    if ((Rp % 256) || (Cp % 256)) return clamd::w24g_skw_workspace_bytes(Tp, Rp, Cp, 24);      // multiples of 128: the wave-level plan
-    const long long nb = 24LL * (Rp / 256) * (Cp / 256);
-    const long long max_split = std::max<long long>(1, std::min<long long>((3LL * clamd_num_cus()) / nb, Tp / (2 * W24G_D)));
-    return std::max((size_t)max_split * 24 * Rp * Cp * sizeof(float), clamd::w24g_sk_workspace_bytes(Tp, Rp, Cp, 24));
-}
+size_t clamd_wgrad_winograd24_pre_workspace_bytes(int B, int H, int W, int Rp, int Cp) { return wino_pre_workspace_bytes(W24_FORM, B, H, W, Rp, Cp); }
 
 int clamd_wgrad_winograd24_pre(const float* gz, int gz_ldc, const float* v, float* yt, float* workspace, size_t ws_bytes, float* out,
                                int B, int H, int W, int Rp, int Cp, int R, int C, int r_seg0, int r_seg0p, int c_seg0, int c_seg0p,
                                const clamd_tuning* tune, void* stream) {
-    if (int e = clamd_check_tuning(tune)) return e;
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("wgrad_winograd24_pre: empty problem");
-    if ((H & 1) || (W & 3)) return clamd_fail("wgrad_winograd24_pre: H must be even and W a multiple of 4");
-    if (Rp % 128 || Cp % 128 || Rp <= 0 || Cp <= 0 || gz_ldc % 4) return clamd_fail("wgrad_winograd24_pre: needs Rp and Cp multiples of 128");
-    const bool wave_level = (Rp % 256) || (Cp % 256);          // a wave owns a 128 x 128 block; 256 x 256 workgroup blocks where both counts allow
-    if (gz && (long long)H * W * gz_ldc * 4 >= (1ll << 31)) return clamd_fail("wgrad_winograd24_pre: one image exceeds 2^31 bytes");
-    const clamd_tuning& tn = clamd_tune(tune);
-    const long long ntm = w24g_tiles(B, H, W), Tp = ntm * 32;
-    if (Tp * Rp * 4 >= (1ll << 32) || (unsigned long long)ntm * (Cp / 8) * 24 * 1024 >= (1ull << 32))
-        return clamd_fail("wgrad_winograd24_pre: an operand exceeds 2^32 bytes");
-    int per = 0;
-    const int nsplit = wave_level ? 1 : w24g_wg_plan(Tp, Rp, Cp, tn, &per);
-    // stream-K where the items alone nearly fill the chip (an item then gets 2-3 slots); with fewer, larger items the split-K plan's
-    // whole rounds are as even and its slabs are fewer (tools/wino44g_ab.py: 1.10-1.21x faster from 96 items on, 0.78-0.95x below)
-    const bool streamk = wave_level || tn.wgrad_streamk == 2 || (tn.wgrad_streamk == 1 && (long long)24 * (Rp / 256) * (Cp / 256) * 8 >= 3LL * clamd_usable_cus(tn));
-    if (!streamk && (size_t)nsplit * 24 * Rp * Cp * sizeof(float) > ws_bytes) return clamd_fail("wgrad_winograd24_pre: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    if (gz) {                                  // gz == NULL: yt already holds the transformed gradient (clamd_wgrad_winograd24_pre_transform)
-        W24WgXformParams pa{gz, gz_ldc, yt, B, H, W, Rp, (int)Tp};
-        const long long na = (Tp * (Rp / 4) + 255) / 256;
-        const unsigned g = (unsigned)std::min<long long>(na, 1 << 20);
-        if (W >= 32) hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<8>, dim3(g), dim3(256), 0, s, pa);
-        else hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<4>, dim3(g), dim3(256), 0, s, pa);
-        if (int e = clamd_check_launch("wgrad_winograd24_pre transform")) return e;
-    }
-    if (wave_level)
-        return launch_w24g_wgrad_skw(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, 24, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
-    if (streamk)
-        return launch_w24g_wgrad_sk(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, 24, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
-    if (int e = launch_w24g_wgrad_gemm(yt, v, workspace, Rp, Cp, Tp, nsplit, per, 24, s)) return e;
-    W24GReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
-    const long long nquad = (long long)Rp * Cp / 4;
-#define W24G_REDUCE(PHS_)                                                                                              \
-    do {                                                                                                               \
-        long long g = (nquad + 4 * (64 / PHS_) - 1) / (4 * (64 / PHS_));                                               \
-        if (g > 8192) g = 8192;                                                                                        \
-        hipLaunchKernelGGL(wino24g_wgrad_reduce_kernel<PHS_>, dim3((unsigned)g), dim3(256), 0, s, rp);                 \
-    } while (0)
-    if (nsplit >= 4 && nquad <= 65536) W24G_REDUCE(4);
-    else if (nsplit >= 2 && nquad <= 131072) W24G_REDUCE(2);
-    else W24G_REDUCE(1);
-#undef W24G_REDUCE
-    return clamd_check_launch("wgrad_winograd24_pre_reduce");
+    return wino_pre_wgrad(W24_FORM, gz, gz_ldc, v, yt, workspace, ws_bytes, out, B, H, W, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tune, stream);
 }
 
-// The gradient-side transform alone (A4 dY A6^T of gz into yt, tiles in the order of the forward image): a caller with several
-// streams can run it beside another launch's GEMM and then call clamd_wgrad_winograd24_pre with gz == NULL.
 int clamd_wgrad_winograd24_pre_transform(const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0 || !gz || !yt) return clamd_fail("wgrad_winograd24_pre_transform: bad arguments");
-    if ((H & 1) || (W & 3)) return clamd_fail("wgrad_winograd24_pre_transform: H must be even and W a multiple of 4");
-    if (Rp % 4 || Rp <= 0 || gz_ldc % 4) return clamd_fail("wgrad_winograd24_pre_transform: channel count / pitch must be padded");
-    const long long Tp = w24g_tiles(B, H, W) * 32;
-    if ((long long)H * W * gz_ldc * 4 >= (1ll << 31) || Tp * Rp * 4 >= (1ll << 32)) return clamd_fail("wgrad_winograd24_pre_transform: operand too large");
-    W24WgXformParams pa{gz, gz_ldc, yt, B, H, W, Rp, (int)Tp};
-    const long long na = (Tp * (Rp / 4) + 255) / 256;
-    const unsigned g = (unsigned)std::min<long long>(na, 1 << 20);
-    if (W >= 32) hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<8>, dim3(g), dim3(256), 0, (hipStream_t)stream, pa);
-    else hipLaunchKernelGGL(wino24g_wgrad_xform_kernel<4>, dim3(g), dim3(256), 0, (hipStream_t)stream, pa);
-    return clamd_check_launch("wgrad_winograd24_pre_transform");
+    return wino_pre_wgrad_transform(W24_FORM, gz, gz_ldc, yt, B, H, W, Rp, stream);
 }
 
 }  // extern "C"

@@ -266,42 +266,25 @@ __global__ void __launch_bounds__(256, 2) wino24n_kernel(const WinoParams p) {
     if (cur_tn >= 0) fold_stats();
 }
 
-static inline void w24n_tile(int W, int& ph, int& pw) { if (W >= 32) { ph = 8; pw = 32; } else { ph = 16; pw = 16; } }
-static long long w24n_tiles(int B, int H, int W) {
-    int ph, pw;
-    w24n_tile(W, ph, pw);
-    return (long long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
-}
-
-// rows of a half-width launch: one per pixel tile (one workgroup per tile), or one per workgroup of the persistent grid (two per CU)
+// rows of a half-width launch: 32-channel slabs, two workgroups per CU
 long long clamd_winograd24_half_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
-    const long long tiles = w24n_tiles(B, H, W), nblk = tiles * ((Cout_p + 31) / 32);
-    const long long cap = 2LL * clamd_usable_cus(tn);
-    return (tn.wino_persist && nblk > cap) ? cap : tiles;
+    return wino_stat_rows(wino_tiles(w24_tile(W), B, H, W), Cout_p, 32, 2, tn);
 }
 
 int launch_wino24_half(WinoParams p, const clamd_tuning& tn, int stat_rows, hipStream_t stream) {
-    int ph, pw;
-    w24n_tile(p.W, ph, pw);
-    const long long ntn = (p.Np + 31) / 32, tiles = w24n_tiles(p.B, p.H, p.W);
-    if (tiles * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd24 (half-width): grid out of range");
-    if (p.stats && stat_rows != clamd_winograd24_half_stat_rows(p.B, p.H, p.W, p.Np, tn))
-        return clamd_fail("conv3x3_winograd24 (half-width): stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD24, ...)");
+    const WinoTile t = w24_tile(p.W);
+    WinoGrid g;
+    if (int e = wino_forward_plan(p, t, (p.Np + 31) / 32, (double)p.B * p.H * p.W * p.Kp, 24.0 * p.Kp * p.Np, 2LL * clamd_usable_cus(tn), stat_rows,
+                                  clamd_winograd24_half_stat_rows(p.B, p.H, p.W, p.Np, tn), tn, "conv3x3_winograd24 (half-width)",
+                                  "CLAMD_OP_CONV3X3_WINOGRAD24", &g))
+        return e;
     // block order: the band of the full-width launch (output-channel slabs of 64 whose workgroups share one XCD's L2), in half slabs
     p.band = 1;
     if (p.Np % 64 == 0)
-        p.band = 2 * wino_band(tiles, p.Np / 64, (double)p.B * p.H * p.W * p.Kp, 24.0 * p.Kp * p.Np, tn.wino_band);
-    p.nblk = (int)(tiles * ntn);
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, 2LL * clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    const bool ragged = (p.H % ph) != 0 || (p.W % pw) != 0 || (p.Np % 32) != 0;
-#define W24N_LAUNCH(TXN_, RG_)                                                                                          \
-    do {                                                                                                               \
-        if (p.bias_classes) hipLaunchKernelGGL((wino24n_kernel<TXN_, RG_, true>), dim3(grid), dim3(256), 0, stream, p);  \
-        else hipLaunchKernelGGL((wino24n_kernel<TXN_, RG_, false>), dim3(grid), dim3(256), 0, stream, p);               \
-    } while (0)
-    if (pw == 32) { if (ragged) W24N_LAUNCH(8, true); else W24N_LAUNCH(8, false); }
-    else { if (ragged) W24N_LAUNCH(4, true); else W24N_LAUNCH(4, false); }
-#undef W24N_LAUNCH
+        p.band = 2 * wino_band(wino_tiles(t, p.B, p.H, p.W), p.Np / 64, (double)p.B * p.H * p.W * p.Kp, 24.0 * p.Kp * p.Np, tn.wino_band);
+    wino_dispatch(t.pw == 32, g.ragged || (p.Np % 32) != 0, p.bias_classes != 0, [&](auto wide, auto ragged, auto cls) {
+        hipLaunchKernelGGL((wino24n_kernel<wide() ? 8 : 4, ragged(), cls()>), dim3(g.grid), dim3(256), 0, stream, p);
+    });
     return clamd_check_launch("conv3x3_winograd(F(2x4), half-width)");
 }
 

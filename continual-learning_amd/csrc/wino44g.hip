@@ -62,13 +62,7 @@ __device__ inline void w44_gt6(const float (&t)[6], float (&o)[3]) {
     o[2] = -(1.f / 6.f) * s12 + (1.f / 6.f) * s34 + t[5];
 }
 
-// tile-block geometry: TXN tiles across x 32 / TXN down, 4 x 4 output pixels each
-static inline void w44_block(int W, int& ph, int& pw) { if (W >= 32) { ph = 16; pw = 32; } else { ph = 32; pw = 16; } }
-static long long w44_blocks(int B, int H, int W) {
-    int ph, pw;
-    w44_block(W, ph, pw);
-    return (long long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw);
-}
+// tile-block geometry: TXN tiles across x 32 / TXN down, 4 x 4 output pixels each (w44_block, wino_common.hip.h)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // input transform (forward / data gradient)
@@ -570,13 +564,8 @@ __global__ void __launch_bounds__(256) wino44g_wgrad_xform_kernel(const W44WgXfo
 
 // out[rl][cl][3][3] = G6^T (sum_s dU_s) G6.  A thread owns four consecutive (r, c) pairs (16-byte loads of all 36 planes); the splits
 // are dealt to PHS lane groups of a wave and combined with fixed shuffle steps: the summation order is fixed (deterministic).
-struct W44GReduceParams {
-    const float* partial; float* out;
-    int nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p;
-};
-
 template <int PHS>
-__global__ void __launch_bounds__(256) wino44g_wgrad_reduce_kernel(const W44GReduceParams p) {
+__global__ void __launch_bounds__(256) wino44g_wgrad_reduce_kernel(const WinoReduceParams p) {
     SIDE_PRIO();
     constexpr int QW = 64 / PHS;                                       // quads per wave
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -645,26 +634,46 @@ __global__ void __launch_bounds__(256) wino44g_wgrad_reduce_kernel(const W44GRed
 using namespace clamd;
 
 namespace clamd {
-// wino24g.hip: the batched plane GEMM dU[p] = Yt[p]^T V[p] (planes = 24 or 36) with its split-K plan
-int w24g_wg_plan_planes(long long Tp, int Rp, int Cp, int planes, const clamd_tuning& tn, int* per_out);
-long long w24g_wg_max_split(long long Tp, int Rp, int Cp, int planes);
-int launch_w24g_wgrad_gemm(const float* yt, const float* v, float* partial, int Rp, int Cp, long long Tp, int nsplit, int per, int planes, hipStream_t s);
-size_t w24g_sk_workspace_bytes(long long Tp, int Rp, int Cp, int planes);
-size_t w24g_skw_workspace_bytes(long long Tp, int Rp, int Cp, int planes);
-int launch_w24g_wgrad_skw(const float* yt, const float* v, float* workspace, size_t ws_bytes, float* out, long long Tp, int Rp, int Cp, int planes,
-                          int R, int C, int r_seg0, int r_seg0p, int c_seg0, int c_seg0p, const clamd_tuning& tn, hipStream_t s);
-int launch_w24g_wgrad_sk(const float* yt, const float* v, float* workspace, size_t ws_bytes, float* out, long long Tp, int Rp, int Cp, int planes,
-                         int R, int C, int r_seg0, int r_seg0p, int c_seg0, int c_seg0p, const clamd_tuning& tn, hipStream_t s);
+
+// rows of a launch: one per tile block (one workgroup per tile block and slab), or one per workgroup of the persistent grid
+long long clamd_winograd44_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
+    return wino_stat_rows(wino_tiles(w44_block(W), B, H, W), Cout_p, 64, 1, tn);
+}
+
+// ---- the form's description: its entry points are the bodies of wino24g.hip (wino_pre_*) -----------------------------------
+static void w44_launch_xform(bool wide, unsigned grid, hipStream_t s, const float* x, int x_ldc, const float* scale, const float* shift, float* v,
+                             int B, int H, int W, int Cp) {
+    W44XformParams p{x, x_ldc, scale, shift, v, B, H, W, Cp};
+    if (wide) hipLaunchKernelGGL(wino44_xform_kernel<8>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino44_xform_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+}
+static void w44_launch_conv(bool wide, bool ragged, unsigned grid, hipStream_t s, const WinoParams& p) {
+    wino_dispatch(wide, ragged, false, [&](auto w, auto rg, auto) {
+        hipLaunchKernelGGL((wino44g_kernel<w() ? 8 : 4, rg()>), dim3(grid), dim3(768), 0, s, p);
+    });
+}
+static void w44_launch_yt(bool wide, unsigned grid, hipStream_t s, const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, int Tp) {
+    W44WgXformParams p{gz, gz_ldc, yt, B, H, W, Rp, Tp};
+    if (wide) hipLaunchKernelGGL(wino44g_wgrad_xform_kernel<8>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino44g_wgrad_xform_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+}
+static void w44_launch_reduce(int phs, unsigned grid, hipStream_t s, const WinoReduceParams& p) {
+    if (phs == 4) hipLaunchKernelGGL(wino44g_wgrad_reduce_kernel<4>, dim3(grid), dim3(256), 0, s, p);
+    else if (phs == 2) hipLaunchKernelGGL(wino44g_wgrad_reduce_kernel<2>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wino44g_wgrad_reduce_kernel<1>, dim3(grid), dim3(256), 0, s, p);
+}
+// two half-block workgroups per tile block in the input transform; Cin_p from 16 in steps of 8; one output image below 2^31 bytes
+static const WinoPreForm W44_FORM = {
+    "winograd44", "CLAMD_OP_CONV3X3_WINOGRAD44", "H and W must be multiples of 4", " (4x4 output tiles)",
+    /*planes*/ 36, /*hmask*/ 3, w44_block, /*xform_wgs*/ 2, /*band_x*/ 2.25, /*cin_mult*/ 8, /*cin_min*/ 16, /*y_mult*/ 4, /*y_bound*/ true,
+    "wgrad_winograd44_pre transform", clamd_winograd44_stat_rows, w44_launch_xform, w44_launch_conv, w44_launch_yt, w44_launch_reduce};
+
 }  // namespace clamd
 
 extern "C" {
 
 #ifdef CLAMD_DIAG
-int clamd_debug_w44_diag(unsigned long long* out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(clamd::g_w44_diag), 64) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(clamd::g_w44_diag), z, 64) != hipSuccess) return -1; }
-    return 0;
-}
+CLAMD_DIAG_READER(clamd_debug_w44_diag, clamd::g_w44_diag, 8)
 #endif
 
 int clamd_wino44_pack(const void* jobs_dev, int njobs, int total_blocks, void* stream) {
@@ -673,141 +682,31 @@ int clamd_wino44_pack(const void* jobs_dev, int njobs, int total_blocks, void* s
     return clamd_check_launch("wino44_pack");
 }
 
-size_t clamd_winograd44_input_elems(int B, int H, int W, int Cp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Cp <= 0) return 0;
-    return (size_t)w44_blocks(B, H, W) * (size_t)(Cp / 8) * 36 * 256;
-}
+size_t clamd_winograd44_input_elems(int B, int H, int W, int Cp) { return wino_pre_input_elems(W44_FORM, B, H, W, Cp); }
 
 int clamd_winograd44_transform_input(const float* x, int x_ldc, const float* scale, const float* shift, float* v, int B, int H, int W,
                                      int Cp, void* stream) {
-    if ((scale == nullptr) != (shift == nullptr)) return clamd_fail("winograd44_transform_input: scale and shift go together");
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("winograd44_transform_input: empty problem");
-    if ((H & 3) || (W & 3)) return clamd_fail("winograd44_transform_input: H and W must be multiples of 4 (4x4 output tiles)");
-    if (Cp % 8 || x_ldc % 4 || x_ldc < Cp) return clamd_fail("winograd44_transform_input: channel count / pitch must be padded");
-    if ((long long)H * W * x_ldc * 4 >= (1ll << 31)) return clamd_fail("winograd44_transform_input: image exceeds 2^31 bytes");
-    int ph, pw;
-    w44_block(W, ph, pw);
-    const long long nth = 2 * w44_blocks(B, H, W), nkg = (Cp / 8 + 3) / 4;
-    if (nth * nkg > 0x7fffffff) return clamd_fail("winograd44_transform_input: grid out of range");
-    W44XformParams p{x, x_ldc, scale, shift, v, B, H, W, Cp};
-    if (pw == 32) hipLaunchKernelGGL(wino44_xform_kernel<8>, dim3((unsigned)(nth * nkg)), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wino44_xform_kernel<4>, dim3((unsigned)(nth * nkg)), dim3(256), 0, (hipStream_t)stream, p);
-    return clamd_check_launch("winograd44_transform_input");
+    return wino_pre_transform_input(W44_FORM, x, x_ldc, scale, shift, v, B, H, W, Cp, stream);
 }
-
-}  // extern "C"
-
-namespace clamd {
-// rows of a launch: one per tile block (one workgroup per tile block and slab), or one per workgroup of the persistent grid
-long long clamd_winograd44_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn) {
-    const long long tiles = w44_blocks(B, H, W), nblk = tiles * ((Cout_p + 63) / 64);
-    return (tn.wino_persist && nblk > clamd_usable_cus(tn)) ? clamd_usable_cus(tn) : tiles;
-}
-}  // namespace clamd
-
-extern "C" {
 
 int clamd_conv3x3_winograd44_pre(const float* v, const float* w_wino, const float* bias, float* y, int y_ldc,
                                  float* stats, int stat_rows, int B, int H, int W, int Cin_p,
                                  int Cout_p, int relu, const clamd_tuning* tune, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("conv3x3_winograd44_pre: empty problem");
-    if ((H & 3) || (W & 3)) return clamd_fail("conv3x3_winograd44_pre: H and W must be multiples of 4 (4x4 output tiles)");
-    if (Cin_p % 8 || Cin_p < 16 || Cout_p % 64 || y_ldc % 4) return clamd_fail("conv3x3_winograd44_pre: needs Cin_p % 8 == 0, Cin_p >= 16, Cout_p % 64 == 0");
-    if (int e = clamd_check_tuning(tune)) return e;
-    const clamd_tuning& tn = clamd_tune(tune);
-    const long long tiles = w44_blocks(B, H, W), ntn = Cout_p / 64;
-    if (tiles * ntn > 0x7fffffff) return clamd_fail("conv3x3_winograd44_pre: grid out of range");
-    if ((unsigned long long)tiles * (Cin_p / 8) * 36 * 1024 >= (1ull << 32) || (long long)36 * Cout_p * Cin_p * 4 >= (1ll << 31))
-        return clamd_fail("conv3x3_winograd44_pre: transformed input exceeds 2^32 bytes or filter 2^31 bytes");
-    if (stats && stat_rows != clamd_winograd44_stat_rows(B, H, W, Cout_p, tn))
-        return clamd_fail("conv3x3_winograd44_pre: stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD44, ...)");
-    if (relu & ~1) return clamd_fail("conv3x3_winograd44_pre: relu must be 0 or 1 (no border-class bias here)");
-    if ((long long)H * W * y_ldc * 4 >= (1ll << 31)) return clamd_fail("conv3x3_winograd44_pre: one output image exceeds 2^31 bytes");
-    WinoParams p{v, 0, w_wino, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu, 1, 0};
-    p.band = wino_band(tiles, ntn, 2.25 * B * H * W * Cin_p, 36.0 * Cin_p * Cout_p, tn.wino_band);
-    p.nblk = (int)(tiles * ntn);
-    const unsigned grid = tn.wino_persist ? (unsigned)std::min<long long>(p.nblk, clamd_usable_cus(tn)) : (unsigned)p.nblk;
-    int ph, pw;
-    w44_block(W, ph, pw);
-    const bool ragged = (H % ph) != 0 || (W % pw) != 0;
-    hipStream_t s = (hipStream_t)stream;
-#define W44G_LAUNCH(TXN_, RG_) hipLaunchKernelGGL((wino44g_kernel<TXN_, RG_>), dim3(grid), dim3(768), 0, s, p)
-    if (pw == 32) { if (ragged) W44G_LAUNCH(8, true); else W44G_LAUNCH(8, false); }
-    else { if (ragged) W44G_LAUNCH(4, true); else W44G_LAUNCH(4, false); }
-#undef W44G_LAUNCH
-    return clamd_check_launch("conv3x3_winograd44_pre");
+    return wino_pre_conv3x3(W44_FORM, v, w_wino, bias, y, y_ldc, stats, stat_rows, B, H, W, Cin_p, Cout_p, relu, tune, stream);
 }
 
-size_t clamd_wgrad_winograd44_pre_operand_elems(int B, int H, int W, int Rp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Rp <= 0) return 0;
-    return (size_t)(36 * w44_blocks(B, H, W) * 32) * (size_t)Rp;
-}
+size_t clamd_wgrad_winograd44_pre_operand_elems(int B, int H, int W, int Rp) { return wino_pre_operand_elems(W44_FORM, B, H, W, Rp); }
 
-size_t clamd_wgrad_winograd44_pre_workspace_bytes(int B, int H, int W, int Rp, int Cp) {
-    if (B <= 0 || H <= 0 || W <= 0 || Rp < 128 || Cp < 128) return 0;
-    const long long Tp = w44_blocks(B, H, W) * 32;
-    if ((Rp % 256) || (Cp % 256)) return w24g_skw_workspace_bytes(Tp, Rp, Cp, 36);      // multiples of 128: the wave-level plan
-    return std::max((size_t)w24g_wg_max_split(Tp, Rp, Cp, 36) * 36 * Rp * Cp * sizeof(float), w24g_sk_workspace_bytes(Tp, Rp, Cp, 36));
-}
-
-static int w44_launch_yt(const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, long long Tp, hipStream_t s) {
-    W44WgXformParams pa{gz, gz_ldc, yt, B, H, W, Rp, (int)Tp};
-    const long long na = (Tp * (Rp / 4) + 255) / 256;
-    const unsigned g = (unsigned)std::min<long long>(na, 1 << 20);
-    if (W >= 32) hipLaunchKernelGGL(wino44g_wgrad_xform_kernel<8>, dim3(g), dim3(256), 0, s, pa);
-    else hipLaunchKernelGGL(wino44g_wgrad_xform_kernel<4>, dim3(g), dim3(256), 0, s, pa);
-    return clamd_check_launch("wgrad_winograd44_pre transform");
-}
+size_t clamd_wgrad_winograd44_pre_workspace_bytes(int B, int H, int W, int Rp, int Cp) { return wino_pre_workspace_bytes(W44_FORM, B, H, W, Rp, Cp); }
 
 int clamd_wgrad_winograd44_pre(const float* gz, int gz_ldc, const float* v, float* yt, float* workspace, size_t ws_bytes, float* out,
                                int B, int H, int W, int Rp, int Cp, int R, int C, int r_seg0, int r_seg0p, int c_seg0, int c_seg0p,
                                const clamd_tuning* tune, void* stream) {
-    if (int e = clamd_check_tuning(tune)) return e;
-    if (B <= 0 || H <= 0 || W <= 0) return clamd_fail("wgrad_winograd44_pre: empty problem");
-    if ((H & 3) || (W & 3)) return clamd_fail("wgrad_winograd44_pre: H and W must be multiples of 4");
-    if (Rp % 128 || Cp % 128 || Rp <= 0 || Cp <= 0 || gz_ldc % 4) return clamd_fail("wgrad_winograd44_pre: needs Rp and Cp multiples of 128");
-    const bool wave_level = (Rp % 256) || (Cp % 256);          // a wave owns a 128 x 128 block; 256 x 256 workgroup blocks where both counts allow
-    if (gz && (long long)H * W * gz_ldc * 4 >= (1ll << 31)) return clamd_fail("wgrad_winograd44_pre: one image exceeds 2^31 bytes");
-    const clamd_tuning& tn = clamd_tune(tune);
-    const long long ntm = w44_blocks(B, H, W), Tp = ntm * 32;
-    if (Tp * Rp * 4 >= (1ll << 32) || (unsigned long long)ntm * (Cp / 8) * 36 * 1024 >= (1ull << 32))
-        return clamd_fail("wgrad_winograd44_pre: an operand exceeds 2^32 bytes");
-    int per = 0;
-    const int nsplit = wave_level ? 1 : w24g_wg_plan_planes(Tp, Rp, Cp, 36, tn, &per);
-    // stream-K where the items alone nearly fill the chip (an item then gets 2-3 slots); with fewer, larger items the split-K plan's
-    // whole rounds are as even and its slabs are fewer (tools/wino44g_ab.py: 1.10-1.21x faster from 96 items on, 0.78-0.95x below)
-    const bool streamk = wave_level || tn.wgrad_streamk == 2 || (tn.wgrad_streamk == 1 && (long long)36 * (Rp / 256) * (Cp / 256) * 8 >= 3LL * clamd_usable_cus(tn));
-    if (!streamk && (size_t)nsplit * 36 * Rp * Cp * sizeof(float) > ws_bytes) return clamd_fail("wgrad_winograd44_pre: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    if (gz)                                    // gz == NULL: yt already holds the transformed gradient (clamd_wgrad_winograd44_pre_transform)
-        if (int e = w44_launch_yt(gz, gz_ldc, yt, B, H, W, Rp, Tp, s)) return e;
-    if (wave_level)
-        return launch_w24g_wgrad_skw(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, 36, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
-    if (streamk)
-        return launch_w24g_wgrad_sk(yt, v, workspace, ws_bytes, out, Tp, Rp, Cp, 36, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tn, s);
-    if (int e = launch_w24g_wgrad_gemm(yt, v, workspace, Rp, Cp, Tp, nsplit, per, 36, s)) return e;
-    W44GReduceParams rp{workspace, out, nsplit, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p};
-    const long long nquad = (long long)Rp * Cp / 4;
-#define W44G_REDUCE(PHS_)                                                                                              \
-    do {                                                                                                               \
-        long long g = (nquad + 4 * (64 / PHS_) - 1) / (4 * (64 / PHS_));                                               \
-        if (g > 8192) g = 8192;                                                                                        \
-        hipLaunchKernelGGL(wino44g_wgrad_reduce_kernel<PHS_>, dim3((unsigned)g), dim3(256), 0, s, rp);                 \
-    } while (0)
-    if (nsplit >= 4 && nquad <= 65536) W44G_REDUCE(4);
-    else if (nsplit >= 2 && nquad <= 131072) W44G_REDUCE(2);
-    else W44G_REDUCE(1);
-#undef W44G_REDUCE
-    return clamd_check_launch("wgrad_winograd44_pre_reduce");
+    return wino_pre_wgrad(W44_FORM, gz, gz_ldc, v, yt, workspace, ws_bytes, out, B, H, W, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, tune, stream);
 }
 
 int clamd_wgrad_winograd44_pre_transform(const float* gz, int gz_ldc, float* yt, int B, int H, int W, int Rp, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0 || !gz || !yt) return clamd_fail("wgrad_winograd44_pre_transform: bad arguments");
-    if ((H & 3) || (W & 3)) return clamd_fail("wgrad_winograd44_pre_transform: H and W must be multiples of 4");
-    if (Rp % 4 || Rp <= 0 || gz_ldc % 4) return clamd_fail("wgrad_winograd44_pre_transform: channel count / pitch must be padded");
-    const long long Tp = w44_blocks(B, H, W) * 32;
-    if ((long long)H * W * gz_ldc * 4 >= (1ll << 31) || Tp * Rp * 4 >= (1ll << 32)) return clamd_fail("wgrad_winograd44_pre_transform: operand too large");
-    return w44_launch_yt(gz, gz_ldc, yt, B, H, W, Rp, Tp, (hipStream_t)stream);
+    return wino_pre_wgrad_transform(W44_FORM, gz, gz_ldc, yt, B, H, W, Rp, stream);
 }
 
 }  // extern "C"

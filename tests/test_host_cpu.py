@@ -93,6 +93,14 @@ def test_stat_rows_and_tuning_are_per_call(C):
     assert L.stat_rows(L.OP_CONV3X3_WINOGRAD24, 16, 256, 256, 64, 64, L.F32, tuning=L.Tuning(wino_persist=0)) == 16 * 32 * 8
     assert L.stat_rows(L.OP_CONV3X3_WINOGRAD24, 1, 16, 16, 64, 64, L.F32) == 1                       # fewer tiles than CUs
     assert L.stat_rows(L.OP_CONV1X1, 2, 64, 64, 32, 64, L.F32) == 2 * 8 * 2
+    # F(4x4): 32 tile blocks of 16 x 32 pixels here, 4 slabs; the half-width F(2x4) launch: 32-channel slabs, two workgroups per CU
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD44, 16, 64, 64, 256, 256, L.F32) == 256
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD44, 16, 64, 64, 256, 256, L.F32, tuning=L.Tuning(wino_persist=0)) == 16 * 4 * 2
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD44, 16, 64, 64, 256, 256, L.F32, tuning=L.Tuning(cu_reserve=8)) == 248
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD44, 1, 16, 32, 64, 64, L.F32) == 1
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD24, 16, 256, 256, 64, 64, L.F32, tuning=L.Tuning(wino_half=1)) == 512
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD24, 16, 256, 256, 64, 64, L.F32, tuning=L.Tuning(wino_half=1, cu_reserve=8)) == 496
+    assert L.stat_rows(L.OP_CONV3X3_WINOGRAD24, 16, 256, 256, 64, 64, L.F32, tuning=L.Tuning(wino_half=1, wino_persist=0)) == 16 * 32 * 8
     assert L.stat_rows(L.OP_BN_BWD_REDUCE, 16, 256, 256, 0, 64, L.BF16) == 1024
     assert L.stat_rows(L.OP_BN_BWD_REDUCE, 16, 16, 16, 0, 1024, L.BF16) == 256
     assert lib.clamd_stat_rows(99, 1, 8, 8, 32, 32, 0, 0, None) < 0 and 'unknown op' in lib.clamd_last_error().decode()
@@ -103,6 +111,51 @@ def test_stat_rows_and_tuning_are_per_call(C):
     m = C.UNet(2, 3, 4)
     m.tuning.wino_persist = 0
     assert C.UNet(2, 3, 4).tuning.wino_persist == 1          # per model, not per process
+
+
+def test_winograd_size_queries_are_pinned(C):
+    """The buffer-size queries of the Winograd entry points (pure host functions; values of the 256-CU plan, recorded before the launch
+    layer was shared).  Shapes: W >= 32 and W < 32, exact and ragged tiles; channel counts 128 / 384 (the wave-level plan) and 256 / 512
+    (workgroup blocks: the split-K bound answers except at 16 x 16, where the stream-K slots are larger); zero for empty or too-narrow
+    arguments."""
+    lib = C._lib.load()
+    shapes = [(2, 64, 64), (16, 32, 32), (1, 16, 16), (3, 20, 36), (2, 24, 20), (16, 64, 64)]
+    chans = ((128, 128), (256, 256), (384, 256), (512, 512), (256, 512), (512, 384))
+    want = {
+        '24': ([196608, 393216, 1572864, 393216, 786432, 3145728, 6144, 12288, 49152, 110592, 221184, 884736, 49152, 98304, 393216, 1572864,
+                3145728, 12582912],
+               [98304, 3145728, 196608, 6291456, 3072, 98304, 55296, 1769472, 24576, 786432, 786432, 25165824],
+               [53477376, 201326592, 94371840, 201326592, 201326592, 113246208, 70778880, 201326592, 94371840, 201326592, 201326592, 113246208,
+                6291456, 18874368, 37748736, 75497472, 37748736, 75497472, 59768832, 201326592, 75497472, 201326592, 201326592, 113246208,
+                28311552, 100663296, 75497472, 201326592, 201326592, 113246208, 70778880, 201326592, 94371840, 201326592, 201326592, 113246208]),
+        '44': ([147456, 294912, 1179648, 294912, 589824, 2359296, 9216, 18432, 73728, 110592, 221184, 884736, 36864, 73728, 294912, 1179648,
+                2359296, 9437184],
+               [73728, 2359296, 147456, 4718592, 4608, 147456, 55296, 1769472, 18432, 589824, 589824, 18874368],
+               [42467328, 198180864, 99090432, 188743680, 188743680, 141557760, 56623104, 198180864, 99090432, 188743680, 188743680, 141557760,
+                9437184, 28311552, 56623104, 75497472, 56623104, 113246208, 61341696, 198180864, 84934656, 188743680, 188743680, 141557760,
+                23592960, 75497472, 84934656, 188743680, 150994944, 113246208, 73138176, 198180864, 99090432, 188743680, 188743680, 141557760]),
+    }
+    for form, (inp, opd, ws) in want.items():
+        elems = getattr(lib, f'clamd_winograd{form}_input_elems')
+        operand = getattr(lib, f'clamd_wgrad_winograd{form}_pre_operand_elems')
+        wsb = getattr(lib, f'clamd_wgrad_winograd{form}_pre_workspace_bytes')
+        assert [elems(*s, c) for s in shapes for c in (8, 20, 64)] == inp, form
+        assert [operand(*s, c) for s in shapes for c in (4, 128)] == opd, form
+        assert [wsb(*s, rp, cp) for s in shapes for rp, cp in chans] == ws, form
+        assert [elems(*a) for a in ((0, 8, 8, 8), (1, 0, 8, 8), (1, 8, -1, 8), (1, 8, 8, 0))] == [0] * 4
+        assert [operand(*a) for a in ((0, 8, 8, 8), (1, 8, 8, 0))] == [0] * 2
+        assert [wsb(*a) for a in ((0, 32, 32, 256, 256), (1, 32, 32, 64, 256), (1, 32, 32, 256, 127), (1, 32, 0, 256, 256))] == [0] * 4
+    # the in-kernel-transform weight gradients: slabs of 16 (F(2x2)) or 4 x 8 (F(2x4)) floats per channel pair, at most 512 workgroups of
+    # 64 x 64 or 64 x 32 channels
+    rc = [(r, c) for r in (32, 64, 96, 128, 256, 384, 512, 1024) for c in (32, 128, 384, 2048)]
+    assert [lib.clamd_wgrad_winograd_workspace_bytes(r, c) for r, c in rc] == [
+        33554432, 67108864, 66846720, 67108864, 67108864, 134217728, 133693440, 134217728, 50331648, 100663296, 99090432, 100663296,
+        67108864, 134217728, 132120576, 134217728, 67108864, 134217728, 132120576, 134217728, 66846720, 132120576, 132120576, 100663296,
+        67108864, 134217728, 125829120, 134217728, 67108864, 134217728, 125829120, 134217728]
+    assert [lib.clamd_wgrad_winograd24_workspace_bytes(r, c) for r, c in rc] == [
+        67108864, 67108864, 66060288, 67108864, 134217728, 134217728, 132120576, 134217728, 100663296, 100663296, 99090432, 100663296,
+        134217728, 134217728, 132120576, 134217728, 134217728, 134217728, 125829120, 134217728, 133693440, 132120576, 132120576, 100663296,
+        134217728, 134217728, 125829120, 134217728, 134217728, 134217728, 100663296, 268435456]
 
 
 def test_module_surface_matches_reference_state_dict(C, golden):
@@ -237,6 +290,196 @@ def test_crop_origin_matches_pad_center_crop(C):
         assert np.array_equal(got, ref), (hs, ws, h, w)
 
 
+_CONV = 'x x_ldc w bias y y_ldc stats stat_rows B H W Cin_p Cout_p relu tune stream'.split()
+_CONV_PRE = 'v w bias y y_ldc stats stat_rows B H W Cin_p Cout_p relu tune stream'.split()
+_XFORM = 'x x_ldc scale shift v B H W Cp stream'.split()
+_WGRAD = 'gz gz_ldc x x_ldc ws ws_bytes out B H W Rp Cp R C r_seg0 r_seg0p c_seg0 c_seg0p tune stream'.split()
+_WGRAD_PRE = 'gz gz_ldc v yt ws ws_bytes out B H W Rp Cp R C r_seg0 r_seg0p c_seg0 c_seg0p tune stream'.split()
+_YT = 'gz gz_ldc yt B H W Rp stream'.split()
+
+
+def _check_winograd_refusals(lib, tref, bad_tune):
+    """Every refusal branch of the launching Winograd entry points, with the WHOLE message (the entry point's prefix included) and
+    status -1 (a host check; -2 would be a launch that was tried).  Consecutive branches are also violated together: the earlier check
+    answers.  Nothing here passes validation, so no pointer is dereferenced."""
+    p = 0x1000
+    big = 1 << 30                                           # batch: 2^31 or more workgroups of any of the kernels at 32 x 32
+
+    def refused(name, order, base, want, **kw):
+        a = dict(base)
+        a.update(kw)
+        rc = getattr(lib, name)(*[a[k] for k in order])
+        msg = lib.clamd_last_error().decode()
+        assert rc == -1 and msg == want, (name, kw, rc, msg, want)
+
+    def chain(name, order, base, steps):
+        """steps: (message, overrides) in the order of the checks; each alone, and each together with its successor"""
+        for i, (want, kw) in enumerate(steps):
+            refused(name, order, base, want, **kw)
+            if i + 1 < len(steps):
+                refused(name, order, base, want, **{**steps[i + 1][1], **kw})
+
+    tuning = ('tuning: wino_mt 0..2', dict(tune=bad_tune))
+    rows = 'stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD%s, ...)'
+
+    conv = dict(x=None, x_ldc=64, w=None, bias=None, y=None, y_ldc=64, stats=None, stat_rows=0, B=1, H=32, W=32, Cin_p=64, Cout_p=64, relu=0,
+                tune=None, stream=None)
+    n = 'conv3x3_winograd: '
+    chain('clamd_conv3x3_winograd', _CONV, conv, [
+        (n + 'empty problem', dict(B=0)),
+        (n + 'H and W must be even (2x2 output tiles)', dict(H=15)),
+        (n + 'channel counts/pitches must be padded', dict(Cin_p=40)),
+        (n + 'image or filter exceeds 2^31 bytes', dict(H=4096, W=4096)),
+        tuning,
+        (n + 'relu must be 0 or 1 (no border-class bias here)', dict(relu=2)),
+        (n + 'grid out of range', dict(B=big)),
+        (n + rows % '', dict(stats=p, stat_rows=7))])
+    refused('clamd_conv3x3_winograd', _CONV, conv, n + 'H and W must be even (2x2 output tiles)', W=31)
+    for kw in (dict(Cout_p=48), dict(x_ldc=68), dict(y_ldc=4)):
+        refused('clamd_conv3x3_winograd', _CONV, conv, n + 'channel counts/pitches must be padded', **kw)
+    refused('clamd_conv3x3_winograd', _CONV, conv, n + 'image or filter exceeds 2^31 bytes', Cin_p=8192, Cout_p=8192, x_ldc=8192, y_ldc=8192)
+
+    for half, n in ((0, 'conv3x3_winograd24: '), (1, 'conv3x3_winograd24 (half-width): ')):
+        t = tref(wino_half=half)
+        chain('clamd_conv3x3_winograd24', _CONV, dict(conv, tune=t), [
+            ('conv3x3_winograd24: empty problem', dict(H=0)),
+            ('conv3x3_winograd24: H must be even and W a multiple of 4 (2x4 output tiles)', dict(W=30)),
+            ('conv3x3_winograd24: channel counts/pitches must be padded', dict(y_ldc=68)),
+            ('conv3x3_winograd24: image or filter exceeds 2^31 bytes', dict(H=4096, W=4096)),
+            tuning,
+            ('conv3x3_winograd24: bad relu flags (bit 1 needs the [9][Cout_p] bias table)', dict(relu=4)),
+            (n + 'grid out of range', dict(B=big)),
+            (n + rows % '24', dict(stats=p, stat_rows=3))])
+        refused('clamd_conv3x3_winograd24', _CONV, dict(conv, tune=t), 'conv3x3_winograd24: bad relu flags (bit 1 needs the [9][Cout_p] bias table)', relu=2)
+        refused('clamd_conv3x3_winograd24', _CONV, dict(conv, tune=t), 'conv3x3_winograd24: H must be even and W a multiple of 4 (2x4 output tiles)', H=31)
+    # the rows of a half-width launch differ from the full-width ones (512 against 256 here): each is refused with the other's count
+    wide = dict(conv, B=16, H=256, W=256, stats=p)
+    refused('clamd_conv3x3_winograd24', _CONV, wide, 'conv3x3_winograd24: ' + rows % '24', stat_rows=512)
+    refused('clamd_conv3x3_winograd24', _CONV, wide, 'conv3x3_winograd24 (half-width): ' + rows % '24', stat_rows=256, tune=tref(wino_half=1))
+
+    n = 'conv3x3_winograd24_direct_filters: '
+    chain('clamd_conv3x3_winograd24_direct_filters', _CONV, conv, [
+        (n + 'empty problem', dict(B=-1)),
+        (n + 'H must be even and W a multiple of 4 (2x4 output tiles)', dict(W=34)),
+        (n + 'needs Cin_p % 32 == 0, Cout_p % 64 == 0', dict(Cout_p=96)),
+        (n + 'image or filter exceeds 2^31 bytes', dict(H=4096, W=4096)),
+        tuning,
+        (n + 'grid out of range', dict(B=big)),
+        (n + rows % '24', dict(stats=p, stat_rows=3)),
+        (n + 'bad relu flags (bit 1 needs the [9][Cout_p] bias table)', dict(relu=2))])
+    refused('clamd_conv3x3_winograd24_direct_filters', _CONV, conv, n + 'needs Cin_p % 32 == 0, Cout_p % 64 == 0', Cin_p=48)
+    refused('clamd_conv3x3_winograd24_direct_filters', _CONV, conv, n + 'bad relu flags (bit 1 needs the [9][Cout_p] bias table)', relu=5, bias=p)
+    # its rows follow clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD24), which answers for the half-width launch under wino_half
+    refused('clamd_conv3x3_winograd24_direct_filters', _CONV, wide, n + rows % '24', stat_rows=256, tune=tref(wino_half=1))
+
+    xf = dict(x=None, x_ldc=64, scale=None, shift=None, v=None, B=1, H=32, W=32, Cp=64, stream=None)
+    for form, even, hbad in (('24', 'H must be even and W a multiple of 4 (2x4 output tiles)', 31), ('44', 'H and W must be multiples of 4 (4x4 output tiles)', 30)):
+        n = f'winograd{form}_transform_input: '
+        chain(f'clamd_winograd{form}_transform_input', _XFORM, xf, [
+            (n + 'scale and shift go together', dict(scale=p)),
+            (n + 'empty problem', dict(B=0)),
+            (n + even, dict(H=hbad)),
+            (n + 'channel count / pitch must be padded', dict(Cp=12)),
+            (n + 'image exceeds 2^31 bytes', dict(H=4096, W=4096, x_ldc=32, Cp=32)),
+            (n + 'grid out of range', dict(B=2 * big - 1, H=64))])
+        refused(f'clamd_winograd{form}_transform_input', _XFORM, xf, n + 'scale and shift go together', shift=p)
+        refused(f'clamd_winograd{form}_transform_input', _XFORM, xf, n + even, W=34)
+        for kw in (dict(x_ldc=66), dict(x_ldc=32)):
+            refused(f'clamd_winograd{form}_transform_input', _XFORM, xf, n + 'channel count / pitch must be padded', **kw)
+    # the F(4x4) transform runs two workgroups per tile block: 2^30 blocks are out of its range
+    refused('clamd_winograd44_transform_input', _XFORM, xf, 'winograd44_transform_input: grid out of range', B=big, H=16, Cp=8, x_ldc=8)
+
+    pre = dict(v=None, w=None, bias=None, y=None, y_ldc=64, stats=None, stat_rows=0, B=1, H=32, W=32, Cin_p=64, Cout_p=64, relu=0, tune=None, stream=None)
+    for form, even, hbad, needs, chan in (
+            ('24', 'H must be even and W a multiple of 4 (2x4 output tiles)', 31, 'needs Cin_p % 32 == 0, Cin_p >= 64, Cout_p % 64 == 0',
+             (dict(Cin_p=32), dict(Cin_p=72), dict(Cout_p=96), dict(y_ldc=68))),
+            ('44', 'H and W must be multiples of 4 (4x4 output tiles)', 30, 'needs Cin_p % 8 == 0, Cin_p >= 16, Cout_p % 64 == 0',
+             (dict(Cin_p=8), dict(Cin_p=20), dict(Cout_p=96), dict(y_ldc=66)))):
+        name, n = f'clamd_conv3x3_winograd{form}_pre', f'conv3x3_winograd{form}_pre: '
+        chain(name, _CONV_PRE, pre, [
+            (n + 'empty problem', dict(W=0)),
+            (n + even, dict(H=hbad)),
+            (n + needs, chan[0]),
+            tuning,
+            (n + 'grid out of range', dict(B=big)),
+            (n + 'transformed input exceeds 2^32 bytes or filter 2^31 bytes', dict(B=128, H=256, W=256, Cin_p=128)),
+            (n + rows % form, dict(stats=p, stat_rows=5)),
+            (n + 'relu must be 0 or 1 (no border-class bias here)', dict(relu=2))])
+        for kw in chan[1:]:
+            refused(name, _CONV_PRE, pre, n + needs, **kw)
+        refused(name, _CONV_PRE, pre, n + even, W=34)
+        refused(name, _CONV_PRE, pre, n + 'transformed input exceeds 2^32 bytes or filter 2^31 bytes', Cin_p=8192, Cout_p=8192)
+    refused('clamd_conv3x3_winograd24_pre', _CONV_PRE, dict(pre, B=16, H=256, W=256, stats=p), 'conv3x3_winograd24_pre: ' + rows % '24', stat_rows=256,
+            tune=tref(wino_half=1))
+    # F(4x4) alone bounds the output image, after every other check
+    n = 'conv3x3_winograd44_pre: '
+    refused('clamd_conv3x3_winograd44_pre', _CONV_PRE, pre, n + 'one output image exceeds 2^31 bytes', H=4096, W=4096, Cin_p=16)
+    refused('clamd_conv3x3_winograd44_pre', _CONV_PRE, pre, n + 'relu must be 0 or 1 (no border-class bias here)', H=4096, W=4096, Cin_p=16, relu=3)
+
+    wg = dict(gz=None, gz_ldc=64, x=None, x_ldc=64, ws=None, ws_bytes=0, out=None, B=1, H=32, W=32, Rp=64, Cp=64, R=64, C=64, r_seg0=64, r_seg0p=64,
+              c_seg0=64, c_seg0p=64, tune=None, stream=None)
+    for form, even, wbad in (('', 'H and W must be even', 31), ('24', 'H must be even and W a multiple of 4', 30)):
+        name, n = f'clamd_wgrad_winograd{form}', f'wgrad_winograd{form}: '
+        chain(name, _WGRAD, wg, [
+            tuning,
+            (n + 'empty problem', dict(B=0)),
+            (n + even, dict(W=wbad)),
+            (n + 'channel counts/pitches must be padded', dict(Rp=48)),
+            (n + 'one image exceeds 2^30 bytes', dict(H=2048, W=2048)),
+            (n + 'workspace too small', dict(ws_bytes=16 * 64 * 64 * 4 - 1))])
+        refused(name, _WGRAD, wg, n + even, H=31)
+        for kw in (dict(Cp=40), dict(gz_ldc=68), dict(x_ldc=68)):
+            refused(name, _WGRAD, wg, n + 'channel counts/pitches must be padded', **kw)
+        refused(name, _WGRAD, wg, n + 'one image exceeds 2^30 bytes', H=2048, W=2048, gz_ldc=32)
+
+    wp = dict(gz=None, gz_ldc=256, v=None, yt=None, ws=None, ws_bytes=0, out=None, B=1, H=32, W=32, Rp=256, Cp=256, R=256, C=256, r_seg0=256,
+              r_seg0p=256, c_seg0=256, c_seg0p=256, tune=None, stream=None)
+    for form, planes, even, hbad in (('24', 24, 'H must be even and W a multiple of 4', 31), ('44', 36, 'H and W must be multiples of 4', 30)):
+        name, n = f'clamd_wgrad_winograd{form}_pre', f'wgrad_winograd{form}_pre: '
+        chain(name, _WGRAD_PRE, wp, [
+            tuning,
+            (n + 'empty problem', dict(H=0)),
+            (n + even, dict(H=hbad)),
+            (n + 'needs Rp and Cp multiples of 128', dict(Rp=192)),
+            (n + 'one image exceeds 2^31 bytes', dict(gz=p, H=4096, W=4096)),
+            (n + 'an operand exceeds 2^32 bytes', dict(B=1024, H=256, W=256)),
+            (n + 'workspace too small', dict(ws_bytes=planes * 256 * 256 * 4 - 1))])
+        refused(name, _WGRAD_PRE, wp, n + even, W=34)
+        for kw in (dict(Cp=64), dict(Rp=0), dict(Cp=-128), dict(gz_ldc=258)):
+            refused(name, _WGRAD_PRE, wp, n + 'needs Rp and Cp multiples of 128', **kw)
+        refused(name, _WGRAD_PRE, wp, n + 'an operand exceeds 2^32 bytes', B=256, H=256, W=256, Cp=2048)
+        refused(name, _WGRAD_PRE, wp, n + 'workspace too small', tune=tref(wgrad_streamk=0), Rp=512, Cp=512)
+        # the stream-K plans (gz == NULL: nothing runs before them) size their own slots; both forms share those launchers and their messages
+        sk = 'wgrad_winograd_pre: workspace too small'
+        refused(name, _WGRAD_PRE, wp, sk, Rp=128)                                            # wave-level plan
+        refused(name, _WGRAD_PRE, wp, sk, Cp=384, tune=tref(wgrad_streamk=0))
+        refused(name, _WGRAD_PRE, wp, sk, tune=tref(wgrad_streamk=2))
+        refused(name, _WGRAD_PRE, wp, sk, Rp=512, Cp=512)                                    # planes x 4 items x 8 >= 3 x 256 CUs: stream-K by default
+    # 24 x 2 x 8 = 384 < 768 <= 36 x 3 x 8: the same channel counts choose split-K in F(2x4) and stream-K in F(4x4)
+    refused('clamd_wgrad_winograd24_pre', _WGRAD_PRE, wp, 'wgrad_winograd24_pre: workspace too small', Rp=512)
+    refused('clamd_wgrad_winograd44_pre', _WGRAD_PRE, wp, 'wgrad_winograd_pre: workspace too small', Rp=768)
+    refused('clamd_wgrad_winograd44_pre', _WGRAD_PRE, wp, 'wgrad_winograd44_pre: workspace too small', Rp=512)
+
+    yt = dict(gz=p, gz_ldc=64, yt=p, B=1, H=32, W=32, Rp=64, stream=None)
+    for form, even, hbad in (('24', 'H must be even and W a multiple of 4', 31), ('44', 'H and W must be multiples of 4', 30)):
+        name, n = f'clamd_wgrad_winograd{form}_pre_transform', f'wgrad_winograd{form}_pre_transform: '
+        chain(name, _YT, yt, [
+            (n + 'bad arguments', dict(gz=None)),
+            (n + even, dict(H=hbad)),
+            (n + 'channel count / pitch must be padded', dict(Rp=6)),
+            (n + 'operand too large', dict(H=4096, W=4096, gz_ldc=32))])
+        for kw in (dict(yt=None), dict(B=0), dict(W=-4)):
+            refused(name, _YT, yt, n + 'bad arguments', **kw)
+        refused(name, _YT, yt, n + even, W=34)
+        for kw in (dict(Rp=0), dict(gz_ldc=66)):
+            refused(name, _YT, yt, n + 'channel count / pitch must be padded', **kw)
+        refused(name, _YT, yt, n + 'operand too large', B=2048, H=256, W=256, Rp=128)
+
+    for form in ('', '24', '44'):
+        for args in ((None, 0, 0, None), (p, 1, 0, None), (p, 0, 4, None)):
+            assert getattr(lib, f'clamd_wino{form}_pack')(*args) == -1 and lib.clamd_last_error().decode() == f'wino{form}_pack: empty job table'
+
+
 def test_abi_rejects_bad_arguments_before_any_launch(C):
     """Error behaviour of the C ABI: argument validation happens on the host before anything is
     enqueued, the entry point returns a negative status, clamd_last_error() names the problem and the Python side raises
@@ -286,6 +529,9 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
             call(name, *args)
         assert needle in str(e.value), (name, str(e.value))
         assert needle in lib.clamd_last_error().decode()
+    keep.append(C._lib.Tuning())
+    keep[-1].wino_mt = 7                 # out of range
+    _check_winograd_refusals(lib, tref, keep[-1].ref())
     # clamd_conv3x3_border_bias_ok / clamd_conv3x3_bn_sums / clamd_stat_rows(CLAMD_OP_CONV3X3) over the branches of plan_conv3x3 and pws_rows:
     # the persistent kernel takes igemm_pws 2, or 1 up to 256 input channels; K-steps in pairs (Kp % 64 in bf16); bn_y only in bf16
     ok = lambda H, W, Kp, dt, **kw: lib.clamd_conv3x3_border_bias_ok(2, H, W, Kp, 64, dt, tref(**kw) if kw else None)
