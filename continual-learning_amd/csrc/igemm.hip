@@ -432,18 +432,10 @@ static_assert(Geo<MODE_CONV3, 16>::SLOTS * 16 >= (4 * 32 * 68 + 4 * 2 * 64) * 4,
 static_assert(Geo<MODE_PW, 32>::SLOTS * 16 >= (4 * 32 * 68 + 4 * 2 * 64) * 4, "LDS too small for epilogue");
 static_assert(Geo<MODE_PW, 16>::SLOTS * 16 >= (4 * 32 * 68 + 4 * 2 * 64) * 4, "LDS too small for epilogue");
 
-// pixel tiles of the baseline kernel (256 pixels each) = its partial statistics rows
-static long long igemm_tiles(const IgemmParams& p) {
-    const int TW = p.W >= 32 ? 32 : 16, TH = 256 / TW;
-    return (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
-}
-
 template <typename T, int MODE, int EPI>
 static int launch_tw(const IgemmParams& p, hipStream_t s, int variant) {
     const bool wide = p.W >= 32;
-    const int TW = wide ? 32 : 16, TH = 256 / TW;
-    const long long tiles = (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
-    const long long nblk = tiles * ((p.Np + 63) / 64);
+    const long long nblk = tile_rule(p.B, p.H, p.W, 256).tiles * ((p.Np + 63) / 64);
     if (nblk <= 0 || nblk > 0x7fffffff) return clamd_fail("igemm: grid out of range");
     const int var = (MODE == MODE_CONV3 && EPI == EPI_NHWC && !__is_same(T, split_t)) ? variant : 0;
 #define IGEMM_LAUNCH(TW_, V_) hipLaunchKernelGGL((igemm_kernel<T, MODE, EPI, TW_, V_>), dim3((unsigned)nblk), dim3(256), 0, s, p)
@@ -465,48 +457,62 @@ static int launch_tw(const IgemmParams& p, hipStream_t s, int variant) {
 
 template <int MODE, int EPI>
 static int launch(const IgemmParams& p, int dtype, hipStream_t s, int variant = 0) {
-    if (dtype == CLAMD_BF16) return launch_tw<bf16_t, MODE, EPI>(p, s, variant);
-    if (dtype == CLAMD_F32) return launch_tw<float, MODE, EPI>(p, s, variant);
-    if (dtype == CLAMD_SPLIT) return launch_tw<split_t, MODE, EPI>(p, s, variant);
-    return clamd_fail("igemm: bad dtype");
+    return dispatch_dtype(dtype, "igemm: bad dtype", [&](auto tag) { return launch_tw<typename decltype(tag)::type, MODE, EPI>(p, s, variant); });
 }
 
 // Which structure runs a 3x3 launch (measured choices, tools/conv_ab.py) and how many partial statistics rows it writes.
 struct Conv3Plan { int kind; int mt; int rows; };      // kind 0 = baseline, 1 = producer/consumer, 2 = persistent
-static Conv3Plan plan_conv3x3(const IgemmParams& p, int dtype, const clamd_tuning& tn) {
-    if (tn.igemm_pws == 2 || (tn.igemm_pws == 1 && p.Kp <= 256)) {    // measured: faster up to 256 input channels
-        const int gm = pws_rows(p, dtype, tn);
+static Conv3Plan plan_conv3x3(const Conv3Ask& a, int dtype, const clamd_tuning& tn) {
+    if (tn.igemm_pws == 2 || (tn.igemm_pws == 1 && a.Kp <= 256)) {    // measured: faster up to 256 input channels
+        const int gm = pws_rows(a, dtype, tn);
         if (gm > 0) return {2, 2, gm};                                  // -1: shape not supported there, fall through
     }
     int mt = 0;
     if (tn.igemm_ws == 1 || tn.igemm_ws == 3 || tn.igemm_ws == 4)      // forced: 256- / 512- / 128-pixel tiles
         mt = tn.igemm_ws == 1 ? 2 : tn.igemm_ws == 3 ? 4 : 1;
-    else if (tn.igemm_ws == 2 && p.Kp >= 256) {                        // (exactly 256 only when the persistent kernel declined)
+    else if (tn.igemm_ws == 2 && a.Kp >= 256) {                        // (exactly 256 only when the persistent kernel declined)
         // one workgroup per CU: take the 512-pixel tile only if it still gives every CU a workgroup
-        const long long ntn = (p.Np + 63) / 64;
-        const long long blocks4 = (long long)p.B * ((p.H + 15) / 16) * ((p.W + 31) / 32) * ntn;
-        const long long blocks2 = (long long)p.B * (p.W >= 32 ? ((p.H + 7) / 8) * ((p.W + 31) / 32) : ((p.H + 15) / 16) * ((p.W + 15) / 16)) * ntn;
+        const long long ntn = (a.Np + 63) / 64;
+        const long long blocks4 = tile_rule(a.B, a.H, a.W, 512).tiles * ntn, blocks2 = tile_rule(a.B, a.H, a.W, 256).tiles * ntn;
         const long long fill = 7LL * clamd_usable_cus(tn) / 8;           // 224 of 256 CUs; fewer when CUs are left to RCCL
-        mt = (p.W >= 32 && blocks4 >= fill) ? 4 : blocks2 >= fill ? 2 : 1;
+        mt = (a.W >= 32 && blocks4 >= fill) ? 4 : blocks2 >= fill ? 2 : 1;
     }
-    if (mt) return {1, mt, ws_rows(p, mt)};
-    const long long t = igemm_tiles(p);
+    if (mt) return {1, mt, ws_rows(a, mt)};
+    const long long t = tile_rule(a.B, a.H, a.W, 256).tiles;          // the baseline kernel: one row per 256-pixel tile
     return {0, 2, t > 0x7fffffff ? -1 : (int)t};
 }
 
-static int check_common(const IgemmParams& p, const char* who, int dtype, bool y_nhwc = true) {
+static int check_rows(const IgemmParams& p, int have, int need, const char* who) {
+    if ((p.stats || p.bn_sums) && have != need) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: stat_rows = %d but this launch writes %d partial rows (size the buffer with clamd_stat_rows)", who, have, need);
+        return clamd_fail(msg);
+    }
+    return 0;
+}
+
+// The checks every entry point of this file shares, in the order of their refusals.  `who` names the entry point in its own messages.
+// img_scale: pixels the two image bounds count per GEMM row -- 4 for the ConvTranspose2d data gradient (its input is the 2H x 2W image),
+// 1 everywhere else (see DESIGN.md for what that leaves unbounded).  tune: checked here by the entry point that takes one.
+static int check_common(const IgemmParams& p, const char* who, int dtype, int img_scale, bool y_nhwc, const clamd_tuning* tune) {
     if (p.B <= 0 || p.H <= 0 || p.W <= 0) return clamd_fail("igemm: empty problem");
     if (int e = clamd_check_split(dtype, p.x, p.x_ldc)) return e;
     if (y_nhwc) if (int e = clamd_check_split(dtype, p.y, p.y_ldc)) return e;
     if (p.bn_y) if (int e = clamd_check_split(dtype, p.bn_y, p.Np)) return e;
     if (p.Kp % 32 || p.Np % 32 || p.x_ldc % 8 || p.y_ldc % 8) return clamd_fail("igemm: channel counts/pitches must be padded (K,N %32, ldc %8)");
-    // 32-bit element offsets inside the kernel
     // buffer descriptors address ONE image with 32-bit byte offsets (OOB marker = 2^31)
-    const long long img_bytes = (long long)p.H * p.W * p.x_ldc * (who[0] == 'u' ? 4 : 1) * 4;
-    if (img_bytes >= (1ll << 31)) return clamd_fail("igemm: one image exceeds 2^31 bytes");
-    if ((long long)p.H * p.W * p.y_ldc * (who[0] == 'u' ? 4 : 1) * 4 >= (1ll << 31)) return clamd_fail("igemm: one output image exceeds 2^31 bytes");
+    if ((long long)p.H * p.W * p.x_ldc * img_scale * 4 >= (1ll << 31)) return clamd_fail("igemm: one image exceeds 2^31 bytes");
+    if ((long long)p.H * p.W * p.y_ldc * img_scale * 4 >= (1ll << 31)) return clamd_fail("igemm: one output image exceeds 2^31 bytes");
     if ((long long)9 * p.Np * p.Kp * 4 >= (1ll << 31)) return clamd_fail("igemm: packed filter exceeds 2^31 bytes");
+    if (int e = clamd_check_tuning(tune)) return e;
+    if ((p.bn_y == nullptr) != (p.bn_sums == nullptr)) return wino_fail(who, "bn_y and bn_sums go together");
     return 0;
+}
+// the pointwise forms: no tuning, and the partial rows are the baseline kernel's 256-pixel tiles (clamd_conv3x3 knows its rows only
+// after its plan and checks them there)
+static int check_pointwise(const IgemmParams& p, const char* who, int dtype, int img_scale = 1, bool y_nhwc = true, int stat_rows = 0) {
+    if (int e = check_common(p, who, dtype, img_scale, y_nhwc, nullptr)) return e;
+    return check_rows(p, stat_rows, (int)tile_rule(p.B, p.H, p.W, 256).tiles, who);
 }
 
 }  // namespace clamd
@@ -522,31 +528,19 @@ int clamd_stat_rows(int op, int B, int H, int W, int Cin_p, int Cout_p, int dtyp
     if (B <= 0 || H <= 0 || W <= 0 || Cout_p <= 0) return clamd_fail("stat_rows: empty problem");
     if (int e = clamd_check_tuning(tune)) return e;
     const clamd_tuning& tn = clamd_tune(tune);
-    IgemmParams p{};
-    p.B = B; p.H = H; p.W = W; p.Kp = Cin_p; p.Np = Cout_p;
-    p.bn_y = fused_bn ? (const void*)&p : nullptr;          // only tested against null by the planners
     long long rows = -1;
     switch (op) {
-    case CLAMD_OP_CONV3X3: rows = plan_conv3x3(p, dtype, tn).rows; break;
+    case CLAMD_OP_CONV3X3: rows = plan_conv3x3({B, H, W, Cin_p, Cout_p, fused_bn != 0, false, false, false, false}, dtype, tn).rows; break;
     case CLAMD_OP_CONV3X3_WINOGRAD: rows = clamd_winograd_stat_rows(B, H, W, Cout_p, tn); break;
     case CLAMD_OP_CONV3X3_WINOGRAD24: rows = clamd_winograd24_stat_rows(B, H, W, Cout_p, tn); break;
     case CLAMD_OP_CONV3X3_WINOGRAD44: rows = clamd_winograd44_stat_rows(B, H, W, Cout_p, tn); break;
     case CLAMD_OP_CONV1X1:
-    case CLAMD_OP_CONVT2X2_DGRAD: rows = igemm_tiles(p); break;
+    case CLAMD_OP_CONVT2X2_DGRAD: rows = tile_rule(B, H, W, 256).tiles; break;
     case CLAMD_OP_BN_BWD_REDUCE: rows = clamd_bn_bwd_reduce_rows(B, H, W, Cout_p, Cin_p != 0, tn); break;
     default: return clamd_fail("stat_rows: unknown op");
     }
     if (rows <= 0 || rows > 0x7fffffff) return clamd_fail("stat_rows: out of range");
     return (int)rows;
-}
-
-static int check_rows(const IgemmParams& p, int have, int need, const char* who) {
-    if ((p.stats || p.bn_sums) && have != need) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: stat_rows = %d but this launch writes %d partial rows (size the buffer with clamd_stat_rows)", who, have, need);
-        return clamd_fail(msg);
-    }
-    return 0;
 }
 
 int clamd_conv3x3(const void* x, int x_ldc, const void* w_packed, const float* bias, void* y, int y_ldc,
@@ -555,11 +549,9 @@ int clamd_conv3x3(const void* x, int x_ldc, const void* w_packed, const float* b
     if (relu & ~3) return clamd_fail("conv3x3: bad relu flags");
     IgemmParams p{x, x_ldc, w_packed, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu & 1, 0, m_fastest, bn_y, bn_sums};
     p.bias_classes = (relu & CLAMD_BIAS_BORDER_CLASSES) ? 1 : 0;
-    if (int e = check_common(p, "conv3x3", dtype)) return e;
-    if (int e = clamd_check_tuning(tune)) return e;
-    if ((bn_y == nullptr) != (bn_sums == nullptr)) return clamd_fail("conv3x3: bn_y and bn_sums go together");
+    if (int e = check_common(p, "conv3x3", dtype, 1, true, tune)) return e;
     const clamd_tuning& tn = clamd_tune(tune);
-    const Conv3Plan pl = plan_conv3x3(p, dtype, tn);
+    const Conv3Plan pl = plan_conv3x3(conv3_ask(p), dtype, tn);
     if (pl.rows <= 0) return clamd_fail("conv3x3: grid out of range");
     if (p.bias_classes && (pl.kind != 2 || !bias || H < 2 || W < 2))
         return clamd_fail("conv3x3: the border-class bias table needs the persistent kernel (ask clamd_conv3x3_border_bias_ok), a table and H, W >= 2");
@@ -571,16 +563,12 @@ int clamd_conv3x3(const void* x, int x_ldc, const void* w_packed, const float* b
 
 int clamd_conv3x3_border_bias_ok(int B, int H, int W, int Cin_p, int Cout_p, int dtype, const clamd_tuning* tune) {
     if (B <= 0 || H < 2 || W < 2 || clamd_check_tuning(tune)) return 0;
-    IgemmParams p{nullptr, Cin_p, nullptr, nullptr, nullptr, Cout_p, nullptr, B, H, W, Cin_p, Cout_p, 1, 0, 0, nullptr, nullptr};
-    return plan_conv3x3(p, dtype, clamd_tune(tune)).kind == 2 ? 1 : 0;
+    return plan_conv3x3({B, H, W, Cin_p, Cout_p, false, false, true, false, false}, dtype, clamd_tune(tune)).kind == 2 ? 1 : 0;
 }
 
 int clamd_conv3x3_bn_sums(int B, int H, int W, int Cin_p, int Cout_p, int dtype, const clamd_tuning* tune) {
     if (B <= 0 || H <= 0 || W <= 0 || clamd_check_tuning(tune)) return 0;
-    IgemmParams p{nullptr, Cin_p, nullptr, nullptr, nullptr, Cout_p, nullptr, B, H, W, Cin_p, Cout_p, 0, 0, 0, nullptr, nullptr};
-    p.bn_y = (const void*)&p;          // only tested against null by the planner
-    const clamd_tuning& tn = clamd_tune(tune);
-    return (dtype == CLAMD_BF16 && plan_conv3x3(p, dtype, tn).kind == 2) ? 2 : 5;
+    return (dtype == CLAMD_BF16 && plan_conv3x3({B, H, W, Cin_p, Cout_p, true, false, false, false, false}, dtype, clamd_tune(tune)).kind == 2) ? 2 : 5;
 }
 
 int clamd_conv1x1(const void* x, int x_ldc, const void* w_packed, const float* bias, void* y, int y_ldc,
@@ -588,16 +576,14 @@ int clamd_conv1x1(const void* x, int x_ldc, const void* w_packed, const float* b
                   int relu, int dtype, void* stream) {
     if (relu & ~1) return clamd_fail("conv1x1: relu must be 0 or 1");
     IgemmParams p{x, x_ldc, w_packed, bias, y, y_ldc, stats, B, H, W, Cin_p, Cout_p, relu, 0, 0, bn_y, bn_sums};
-    if (int e = check_common(p, "conv1x1", dtype)) return e;
-    if ((bn_y == nullptr) != (bn_sums == nullptr)) return clamd_fail("conv1x1: bn_y and bn_sums go together");
-    if (int e = check_rows(p, stat_rows, (int)igemm_tiles(p), "conv1x1")) return e;
+    if (int e = check_pointwise(p, "conv1x1", dtype, 1, true, stat_rows)) return e;
     return launch<MODE_PW, EPI_NHWC>(p, dtype, (hipStream_t)stream);
 }
 
 int clamd_conv1x1_logits(const void* x, int x_ldc, const void* w_packed, const float* bias, float* logits_nchw,
                          int B, int H, int W, int Cin_p, int Cout_p, int num_classes, int dtype, void* stream) {
     IgemmParams p{x, x_ldc, w_packed, bias, logits_nchw, 8, nullptr, B, H, W, Cin_p, Cout_p, 0, num_classes, 0, nullptr, nullptr};
-    if (int e = check_common(p, "conv1x1_logits", dtype, false)) return e;
+    if (int e = check_pointwise(p, "conv1x1_logits", dtype, 1, false)) return e;
     if (num_classes > Cout_p) return clamd_fail("conv1x1_logits: num_classes > padded Cout");
     return launch<MODE_PW, EPI_NCHW>(p, dtype, (hipStream_t)stream);
 }
@@ -605,7 +591,7 @@ int clamd_conv1x1_logits(const void* x, int x_ldc, const void* w_packed, const f
 int clamd_conv1x1_argmax(const void* x, int x_ldc, const void* w_packed, const float* bias, long long* pred, float* logits_nchw,
                          int B, int H, int W, int Cin_p, int Cout_p, int num_classes, int dtype, void* stream) {
     IgemmParams p{x, x_ldc, w_packed, bias, logits_nchw, 8, nullptr, B, H, W, Cin_p, Cout_p, 0, num_classes, 0, nullptr, nullptr, pred};
-    if (int e = check_common(p, "conv1x1_argmax", dtype, false)) return e;
+    if (int e = check_pointwise(p, "conv1x1_argmax", dtype, 1, false)) return e;
     if (!pred) return clamd_fail("conv1x1_argmax: pred is null");
     if (num_classes < 1 || num_classes > Cout_p || num_classes > 64) return clamd_fail("conv1x1_argmax: num_classes must be in [1, min(64, padded Cout)]");
     // one 64-channel slab per pixel tile: a workgroup of a second slab would see -inf in every lane and write pred = 64 over the first slab's result
@@ -616,16 +602,14 @@ int clamd_conv1x1_argmax(const void* x, int x_ldc, const void* w_packed, const f
 int clamd_convT2x2_fwd(const void* x, int x_ldc, const void* w_packed, const float* bias, void* y, int y_ldc, int B,
                        int h, int w, int Cin_p, int Cout_p, int dtype, void* stream) {
     IgemmParams p{x, x_ldc, w_packed, bias, y, y_ldc, nullptr, B, h, w, Cin_p, 4 * Cout_p, 0, Cout_p, 0, nullptr, nullptr};
-    if (int e = check_common(p, "convT_fwd", dtype)) return e;
+    if (int e = check_pointwise(p, "convT2x2_fwd", dtype)) return e;
     return launch<MODE_PW, EPI_UP2>(p, dtype, (hipStream_t)stream);
 }
 
 int clamd_convT2x2_dgrad(const void* gy, int gy_ldc, const void* w_packed, void* gx, int gx_ldc, const void* bn_y,
                          float* bn_sums, int stat_rows, int B, int h, int w, int Cin_p, int Cout_p, int dtype, void* stream) {
     IgemmParams p{gy, gy_ldc, w_packed, nullptr, gx, gx_ldc, nullptr, B, h, w, 4 * Cout_p, Cin_p, 0, Cout_p, 0, bn_y, bn_sums};
-    if (int e = check_common(p, "up2_dgrad", dtype)) return e;
-    if ((bn_y == nullptr) != (bn_sums == nullptr)) return clamd_fail("convT2x2_dgrad: bn_y and bn_sums go together");
-    if (int e = check_rows(p, stat_rows, (int)igemm_tiles(p), "convT2x2_dgrad")) return e;
+    if (int e = check_pointwise(p, "convT2x2_dgrad", dtype, 4, true, stat_rows)) return e;
     return launch<MODE_UP2, EPI_NHWC>(p, dtype, (hipStream_t)stream);
 }
 

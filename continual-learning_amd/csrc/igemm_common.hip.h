@@ -65,13 +65,40 @@ template <int TW, int MT> struct WsGeo {
     static constexpr int WT_SLOTS = NT * 4 * WG;
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+// The tile rule: `pixels`-pixel tiles, 32 wide on images at least 32 wide and 16 wide below (or a width the caller chose)
+struct TileRule { int TW, TH; long long tiles; };
+inline TileRule tile_rule_tw(int B, int H, int W, int TW, int pixels) {
+    const int TH = pixels / TW;
+    return {TW, TH, (long long)((W + TW - 1) / TW) * ((H + TH - 1) / TH) * B};
+}
+inline TileRule tile_rule(int B, int H, int W, int pixels) { return tile_rule_tw(B, H, W, W >= 32 ? 32 : 16, pixels); }
+
+// Dtype code -> f(DTag<T>{}) and its status; an unknown dtype is refused with `bad` ("<launcher>: bad dtype") before any launch.
+template <typename T> struct DTag { using type = T; };
+template <typename F>
+inline int dispatch_dtype(int dtype, const char* bad, F&& f) {
+    if (dtype == CLAMD_BF16) return f(DTag<bf16_t>{});
+    if (dtype == CLAMD_F32) return f(DTag<float>{});
+    if (dtype == CLAMD_SPLIT) return f(DTag<split_t>{});
+    return clamd_fail(bad);
+}
+
+// What the planners of a 3x3 launch test (plan_conv3x3, ws_rows, pws_rows): the shape, and which pieces of the epilogue are asked for
+struct Conv3Ask { int B, H, W, Kp, Np; bool has_bn_sums, has_bias, relu, has_stats, bias_classes; };
+inline Conv3Ask conv3_ask(const IgemmParams& p) {
+    return {p.B, p.H, p.W, p.Kp, p.Np, p.bn_y != nullptr, p.bias != nullptr, p.relu != 0, p.stats != nullptr, p.bias_classes != 0};
+}
+
 // igemm_ws.hip: producer/consumer variant of the CONV3/NHWC kernel (same results)
 int launch_igemm_ws(const IgemmParams& p, int dtype, hipStream_t s, int mt);   // mt: 32-pixel row tiles per consumer wave (1, 2 or 4)
-int ws_rows(const IgemmParams& p, int mt);                                     // pixel tiles = partial statistics rows of that launch
+int ws_rows(const Conv3Ask& a, int mt);                                        // pixel tiles = partial statistics rows of that launch
 
 // igemm_pws.hip: persistent producer/consumer variant for short-K layers (same activations; statistics rows are per
 // workgroup instead of per tile); returns -1 without launching when the shape is not supported
 int launch_igemm_pws(const IgemmParams& p, int dtype, hipStream_t s, const ::clamd_tuning& tn);
-int pws_rows(const IgemmParams& p, int dtype, const ::clamd_tuning& tn);
+int pws_rows(const Conv3Ask& a, int dtype, const ::clamd_tuning& tn);
 
 }  // namespace clamd

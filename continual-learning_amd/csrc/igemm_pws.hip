@@ -743,13 +743,12 @@ namespace clamd {
 
 
 // Workgroups per 64-channel output slab (= partial statistics rows of a launch), or -1 when this kernel declines the shape.
-int pws_rows(const IgemmParams& p, int dtype, const clamd_tuning& tn) {
+int pws_rows(const Conv3Ask& a, int dtype, const clamd_tuning& tn) {
     const int esz = dtype == CLAMD_BF16 ? 2 : 4, kc = dtype == CLAMD_BF16 ? 32 : 16;
-    if (p.bn_y && (esz != 2 || p.bias || p.relu || p.stats || p.bias_classes)) return -1;   // the two-sum epilogue: bf16, plain data-gradient launches
-    if (p.Kp % (2 * kc)) return -1;                          // K-steps are staged in pairs
-    const int TW = p.W >= 32 ? 32 : 16, TH = 256 / TW;
-    const long long ntm = (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
-    const int ntn = (p.Np + 63) / 64;
+    if (a.has_bn_sums && (esz != 2 || a.has_bias || a.relu || a.has_stats || a.bias_classes)) return -1;   // the two-sum epilogue: bf16, plain data-gradient launches
+    if (a.Kp % (2 * kc)) return -1;                          // K-steps are staged in pairs
+    const long long ntm = tile_rule(a.B, a.H, a.W, 256).tiles;
+    const int ntn = (a.Np + 63) / 64;
     long long gm = clamd_usable_cus(tn) / ntn;
     if (gm < 1) gm = 1;
     if (gm > ntm) gm = ntm;
@@ -758,11 +757,10 @@ int pws_rows(const IgemmParams& p, int dtype, const clamd_tuning& tn) {
 
 template <typename T>
 static int launch_pws_t(const IgemmParams& p, hipStream_t s, int dtype, const clamd_tuning& tn) {
-    const long long gm = pws_rows(p, dtype, tn);
+    const long long gm = pws_rows(conv3_ask(p), dtype, tn);
     if (gm < 0) return -1;
     const bool wide = p.W >= 32;
-    const int TW = wide ? 32 : 16, TH = 256 / TW;
-    const long long ntm = (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
+    const auto [TW, TH, ntm] = tile_rule(p.B, p.H, p.W, 256);
     const int ntn = (p.Np + 63) / 64;
     const long long nblk = gm * ntn;
     if (ntm > 0x7fffffff) return clamd_fail("igemm_pws: grid out of range");
@@ -789,10 +787,7 @@ static int launch_pws_t(const IgemmParams& p, hipStream_t s, int dtype, const cl
 }
 
 int launch_igemm_pws(const IgemmParams& p, int dtype, hipStream_t s, const clamd_tuning& tn) {
-    if (dtype == CLAMD_BF16) return launch_pws_t<bf16_t>(p, s, dtype, tn);
-    if (dtype == CLAMD_F32) return launch_pws_t<float>(p, s, dtype, tn);
-    if (dtype == CLAMD_SPLIT) return launch_pws_t<split_t>(p, s, dtype, tn);
-    return clamd_fail("igemm_pws: bad dtype");
+    return dispatch_dtype(dtype, "igemm_pws: bad dtype", [&](auto tag) { return launch_pws_t<typename decltype(tag)::type>(p, s, dtype, tn); });
 }
 
 }  // namespace clamd

@@ -396,21 +396,18 @@ __global__ void __launch_bounds__(512, 2) igemm_ws_kernel(const IgemmParams p) {
     if (wave == 0) DIAG_ADD(7, 1);                         // [7] workgroups
 }
 
-int ws_rows(const IgemmParams& p, int mt) {
-    const bool wide = p.W >= 32;
-    if (!wide && mt > 2) mt = 2;
-    const int TW = wide ? 32 : 16, TH = 128 * mt / TW;
-    const long long tiles = (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
+// 16-wide tiles: 256 pixels (16 x 16) or 128 (16 x 8)
+static TileRule ws_tile_rule(int B, int H, int W, int mt) { return tile_rule(B, H, W, 128 * (W < 32 && mt > 2 ? 2 : mt)); }
+
+int ws_rows(const Conv3Ask& a, int mt) {
+    const long long tiles = ws_tile_rule(a.B, a.H, a.W, mt).tiles;
     return tiles > 0x7fffffff ? -1 : (int)tiles;
 }
 
 template <typename T>
 static int launch_ws_t(const IgemmParams& p, hipStream_t s, int mt) {
     const bool wide = p.W >= 32;
-    if (!wide && mt > 2) mt = 2;             // 16-wide tiles: 256 pixels (16 x 16) or 128 (16 x 8)
-    const int TW = wide ? 32 : 16, TH = 128 * mt / TW;
-    const long long tiles = (long long)((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.B;
-    const long long nblk = tiles * ((p.Np + 63) / 64);
+    const long long nblk = ws_tile_rule(p.B, p.H, p.W, mt).tiles * ((p.Np + 63) / 64);
     if (nblk <= 0 || nblk > 0x7fffffff) return clamd_fail("igemm_ws: grid out of range");
     if (!wide && mt == 1) hipLaunchKernelGGL((igemm_ws_kernel<T, 16, 1>), dim3((unsigned)nblk), dim3(512), 0, s, p);
     else if (!wide) hipLaunchKernelGGL((igemm_ws_kernel<T, 16, 2>), dim3((unsigned)nblk), dim3(512), 0, s, p);
@@ -431,10 +428,7 @@ extern "C" int clamd_debug_ws_diag(unsigned long long* out8, int reset) {
 namespace clamd {
 
 int launch_igemm_ws(const IgemmParams& p, int dtype, hipStream_t s, int mt) {
-    if (dtype == CLAMD_BF16) return launch_ws_t<bf16_t>(p, s, mt);
-    if (dtype == CLAMD_F32) return launch_ws_t<float>(p, s, mt);
-    if (dtype == CLAMD_SPLIT) return launch_ws_t<split_t>(p, s, mt);
-    return clamd_fail("igemm_ws: bad dtype");
+    return dispatch_dtype(dtype, "igemm_ws: bad dtype", [&](auto tag) { return launch_ws_t<typename decltype(tag)::type>(p, s, mt); });
 }
 
 }  // namespace clamd

@@ -507,6 +507,29 @@ static void launch_reduce(const ReduceParams& rp, hipStream_t s) {
     hipLaunchKernelGGL((wgrad_reduce_kernel<KP>), dim3((unsigned)g), dim3(256), 0, s, rp);
 }
 
+// The split-K plan of clamd_wgrad: pixel tiles of TW x TH, rt x ct output tiles of 64 x 64 channels, `nsplit` slabs of `per` pixel
+// tiles each, and the bytes of those slabs.
+inline int wgrad_taps(int mode) { return mode == WG_CONV3 ? 9 : (mode == WG_UP2 ? 4 : 1); }
+inline int wgrad_out_tiles(int Rp, int Cp) { return ((Rp + 63) / 64) * ((Cp + 63) / 64); }
+inline size_t wgrad_slab_bytes(int nsplit, int mode, int Rp, int Cp) { return (size_t)nsplit * wgrad_taps(mode) * Rp * Cp * sizeof(float); }
+struct WgradPlan { int TW, out_tiles; bool ws; int nsplit, per; size_t bytes; };
+static WgradPlan wgrad_plan(int mode, int B, int H, int W, int Rp, int Cp, int dtype, const clamd_tuning& tn) {
+    const int TW = wgrad_tw(W, mode, dtype == CLAMD_SPLIT, tn.wgrad_tw16);
+    // 128 pixels in bf16, 64 otherwise (CLAMD_SPLIT tiles like fp32); the ConvTranspose2d gradient's B tile is 4x
+    const int ntiles = (int)tile_rule_tw(B, H, W, TW, (dtype == CLAMD_BF16 ? 128 : 64) / (mode == WG_UP2 ? 2 : 1)).tiles;
+    const int out_tiles = wgrad_out_tiles(Rp, Cp);
+    // the producer/consumer kernel runs one workgroup per CU: half the slabs of the 2-per-CU kernel
+    const bool ws = tn.wgrad_ws && mode == WG_CONV3;
+    // split-K target: wgrad_blocks workgroups on a whole chip (512 = two per CU), scaled down with the CUs left to RCCL
+    const int target = (int)((long long)tn.wgrad_blocks * clamd_usable_cus(tn) / clamd_num_cus());
+    int nsplit = (ws ? target / 2 : target) / out_tiles;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > ntiles) nsplit = ntiles;
+    const int per = (ntiles + nsplit - 1) / nsplit;
+    nsplit = (ntiles + per - 1) / per;
+    return {TW, out_tiles, ws, nsplit, per, wgrad_slab_bytes(nsplit, mode, Rp, Cp)};
+}
+
 }  // namespace clamd
 
 using namespace clamd;
@@ -525,13 +548,10 @@ static inline int wg_identity(int L, int Lp, int seg0, int seg0p) { return L == 
 extern "C" {
 
 size_t clamd_wgrad_workspace_bytes(int mode, int B, int H, int W, int Rp, int Cp, int dtype) {
-    // upper bound used by callers to size the slab buffer: nsplit is capped at 512 blocks total (see below)
-    const int NT = mode == WG_CONV3 ? 9 : (mode == WG_UP2 ? 4 : 1);
-    const int rt = (Rp + 63) / 64, ct = (Cp + 63) / 64;
-    int nsplit = 1024 / (rt * ct);     // upper bound over every value the tuning knob may take
-    if (nsplit < 1) nsplit = 1;
+    // upper bound used by callers to size the slab buffer, over every value the tuning knobs may take: 1024 workgroups
     (void)B; (void)H; (void)W; (void)dtype;
-    return (size_t)nsplit * NT * Rp * Cp * sizeof(float);
+    const int nsplit = 1024 / wgrad_out_tiles(Rp, Cp);
+    return wgrad_slab_bytes(nsplit < 1 ? 1 : nsplit, mode, Rp, Cp);
 }
 
 int clamd_wgrad(int mode, const void* a, int a_ldc, const void* b, int b_ldc, float* workspace, size_t ws_bytes,
@@ -549,32 +569,15 @@ int clamd_wgrad(int mode, const void* a, int a_ldc, const void* b, int b_ldc, fl
         if ((long long)H * W * a_ldc * 4 >= (1ll << 30) || sc * H * W * b_ldc * 4 >= (1ll << 30))
             return clamd_fail("wgrad: one image exceeds 2^30 bytes");
     }
-    const int NT = mode == WG_CONV3 ? 9 : (mode == WG_UP2 ? 4 : 1);
-    const int TW = wgrad_tw(W, mode, dtype == CLAMD_SPLIT, tn.wgrad_tw16);
-    const int TH = (dtype == CLAMD_BF16 ? 128 : 64) / (mode == WG_UP2 ? 2 : 1) / TW;    // CLAMD_SPLIT tiles like fp32
-    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * B;
-    const int rt = (Rp + 63) / 64, ct = (Cp + 63) / 64;
-    // the producer/consumer kernel runs one workgroup per CU: half the slabs of the 2-per-CU kernel
-    const bool ws = tn.wgrad_ws && mode == WG_CONV3;
-    // split-K target: wgrad_blocks workgroups on a whole chip (512 = two per CU), scaled down with the CUs left to RCCL
-    const int target = (int)((long long)tn.wgrad_blocks * clamd_usable_cus(tn) / clamd_num_cus());
-    int nsplit = (ws ? target / 2 : target) / (rt * ct);
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > ntiles) nsplit = ntiles;
-    int per = (ntiles + nsplit - 1) / nsplit;
-    nsplit = (ntiles + per - 1) / per;
-    const size_t need = (size_t)nsplit * NT * Rp * Cp * sizeof(float);
-    if (need > ws_bytes) return clamd_fail("wgrad: workspace too small");
-    WgradParams p{a, a_ldc, b, b_ldc, workspace, B, H, W, Rp, Cp, nsplit, per, tn.wgrad_xcd};
-    const int grid = rt * ct * nsplit;
+    const WgradPlan pl = wgrad_plan(mode, B, H, W, Rp, Cp, dtype, tn);
+    if (pl.bytes > ws_bytes) return clamd_fail("wgrad: workspace too small");
+    WgradParams p{a, a_ldc, b, b_ldc, workspace, B, H, W, Rp, Cp, pl.nsplit, pl.per, tn.wgrad_xcd};
+    const int grid = pl.out_tiles * pl.nsplit, NT = wgrad_taps(mode), nsplit = pl.nsplit;
     hipStream_t s = (hipStream_t)stream;
     int e;
     // LDS-DMA staging: +3..11 % except on the single-tile 64x64-channel layers (HBM-heavy, 6 % slower there); 2 = always
-    if (dtype == CLAMD_BF16 && ws && (tn.wgrad_dma == 2 || (tn.wgrad_dma == 1 && rt * ct > 1))) e = launch_wgrad_dma(p, s, grid, TW);
-    else if (dtype == CLAMD_BF16) e = launch_wg_mode<bf16_t>(mode, ws, p, s, grid, tn.wgrad_tw16);
-    else if (dtype == CLAMD_F32) e = launch_wg_mode<float>(mode, ws, p, s, grid, tn.wgrad_tw16);
-    else if (dtype == CLAMD_SPLIT) e = launch_wg_mode<split_t>(mode, ws, p, s, grid, tn.wgrad_tw16);
-    else return clamd_fail("wgrad: bad dtype");
+    if (dtype == CLAMD_BF16 && pl.ws && (tn.wgrad_dma == 2 || (tn.wgrad_dma == 1 && pl.out_tiles > 1))) e = launch_wgrad_dma(p, s, grid, pl.TW);
+    else e = dispatch_dtype(dtype, "wgrad: bad dtype", [&](auto tag) { return launch_wg_mode<typename decltype(tag)::type>(mode, pl.ws, p, s, grid, tn.wgrad_tw16); });
     if (e) return e;
     const int ident = wg_identity(R, Rp, r_seg0, r_seg0p) && wg_identity(C, Cp, c_seg0, c_seg0p);
     ReduceParams rp{workspace, out, nsplit, NT, Rp, Cp, R, C, r_seg0, r_seg0p, c_seg0, c_seg0p, ident};

@@ -1,6 +1,7 @@
 // Shared declarations of the weight-gradient kernels (wgrad.hip, wgrad_dma.hip).
 #pragma once
 #include "common.hip.h"
+#include "igemm_common.hip.h"      // tile_rule_tw, dispatch_dtype
 
 namespace clamd {
 

@@ -298,13 +298,7 @@ _WGRAD_PRE = 'gz gz_ldc v yt ws ws_bytes out B H W Rp Cp R C r_seg0 r_seg0p c_se
 _YT = 'gz gz_ldc yt B H W Rp stream'.split()
 
 
-def _check_winograd_refusals(lib, tref, bad_tune):
-    """Every refusal branch of the launching Winograd entry points, with the WHOLE message (the entry point's prefix included) and
-    status -1 (a host check; -2 would be a launch that was tried).  Consecutive branches are also violated together: the earlier check
-    answers.  Nothing here passes validation, so no pointer is dereferenced."""
-    p = 0x1000
-    big = 1 << 30                                           # batch: 2^31 or more workgroups of any of the kernels at 32 x 32
-
+def _refusal_tools(lib):
     def refused(name, order, base, want, **kw):
         a = dict(base)
         a.update(kw)
@@ -318,6 +312,17 @@ def _check_winograd_refusals(lib, tref, bad_tune):
             refused(name, order, base, want, **kw)
             if i + 1 < len(steps):
                 refused(name, order, base, want, **{**steps[i + 1][1], **kw})
+
+    return refused, chain
+
+
+def _check_winograd_refusals(lib, tref, bad_tune):
+    """Every refusal branch of the launching Winograd entry points, with the WHOLE message (the entry point's prefix included) and
+    status -1 (a host check; -2 would be a launch that was tried).  Consecutive branches are also violated together: the earlier check
+    answers.  Nothing here passes validation, so no pointer is dereferenced."""
+    p = 0x1000
+    big = 1 << 30                                           # batch: 2^31 or more workgroups of any of the kernels at 32 x 32
+    refused, chain = _refusal_tools(lib)
 
     tuning = ('tuning: wino_mt 0..2', dict(tune=bad_tune))
     rows = 'stat_rows does not match clamd_stat_rows(CLAMD_OP_CONV3X3_WINOGRAD%s, ...)'
@@ -480,6 +485,174 @@ def _check_winograd_refusals(lib, tref, bad_tune):
             assert getattr(lib, f'clamd_wino{form}_pack')(*args) == -1 and lib.clamd_last_error().decode() == f'wino{form}_pack: empty job table'
 
 
+_C3 = 'x x_ldc w bias y y_ldc stats bn_y bn_sums stat_rows B H W Cin_p Cout_p relu m_fastest dtype tune stream'.split()
+_C1 = 'x x_ldc w bias y y_ldc stats bn_y bn_sums stat_rows B H W Cin_p Cout_p relu dtype stream'.split()
+_LOGITS = 'x x_ldc w bias logits B H W Cin_p Cout_p num_classes dtype stream'.split()
+_ARGMAX = 'x x_ldc w bias pred logits B H W Cin_p Cout_p num_classes dtype stream'.split()
+_CT_FWD = 'x x_ldc w bias y y_ldc B H W Cin_p Cout_p dtype stream'.split()
+_CT_DGRAD = 'gy gy_ldc w gx gx_ldc bn_y bn_sums stat_rows B H W Cin_p Cout_p dtype stream'.split()
+_WG = 'mode a a_ldc b b_ldc ws ws_bytes out B H W Rp Cp R C r_seg0 r_seg0p c_seg0 c_seg0p dtype tune stream'.split()
+_ROWS = 'op B H W Cin_p Cout_p dtype fused_bn tune'.split()
+
+
+def _check_direct_conv_refusals(lib, tref, bad_tune, ops):
+    """Every refusal of the direct-convolution, pointwise / ConvTranspose2d GEMM and weight-gradient entry points (igemm*.hip, wgrad*.hip)
+    and of clamd_stat_rows, with the WHOLE message and status -1; consecutive checks are also violated together and the earlier one
+    answers.  Nothing here passes validation: no pointer is dereferenced and nothing is launched."""
+    p, odd = 0x1000, 0x1010                                 # 64-byte aligned / not
+    big = 1 << 30
+    refused, chain = _refusal_tools(lib)
+    F32, SPLIT, NODT = 0, 2, 9
+    split = 'bf16x3 tensors need a 64-byte aligned base and a pitch that is a multiple of 16 channels'
+    padded = 'igemm: channel counts/pitches must be padded (K,N %32, ldc %8)'
+    image, out_image, filt = 'igemm: one image exceeds 2^31 bytes', 'igemm: one output image exceeds 2^31 bytes', 'igemm: packed filter exceeds 2^31 bytes'
+    tuning = ('tuning: wino_mt 0..2', dict(tune=bad_tune))
+    rows = '%s: stat_rows = %d but this launch writes %d partial rows (size the buffer with clamd_stat_rows)'
+    # the checks every GEMM entry point shares, in their order (x / y stand for the entry point's input / output argument names)
+    common = lambda x, y, cin: [
+        ('igemm: empty problem', dict(B=0)),
+        (split, {'dtype': SPLIT, x: odd}),
+        (padded, {cin: 40}),
+        (image, {'H': 4096, 'W': 4096, x + '_ldc': 64, y + '_ldc': 8}),
+        (out_image, {'H': 4096, 'W': 4096, x + '_ldc': 8, y + '_ldc': 64}),
+        (filt, dict(Cin_p=8192, Cout_p=8192))]
+
+    c3 = dict(x=None, x_ldc=64, w=None, bias=None, y=None, y_ldc=64, stats=None, bn_y=None, bn_sums=None, stat_rows=0, B=1, H=32, W=32, Cin_p=64,
+              Cout_p=64, relu=0, m_fastest=0, dtype=F32, tune=None, stream=None)
+    n = 'conv3x3: '
+    direct, ws1 = tref(igemm_pws=0, igemm_ws=0), tref(igemm_pws=0, igemm_ws=1)
+    chain('clamd_conv3x3', _C3, c3, [
+        (n + 'bad relu flags', dict(relu=4))] + common('x', 'y', 'Cin_p') + [
+        tuning,
+        (n + 'bn_y and bn_sums go together', dict(bn_y=p)),
+        (n + 'grid out of range', dict(B=big, tune=direct)),
+        (n + 'the border-class bias table needs the persistent kernel (ask clamd_conv3x3_border_bias_ok), a table and H, W >= 2', dict(relu=2)),
+        (rows % ('conv3x3', 7, 4), dict(stats=p, stat_rows=7)),
+        ('igemm_pws: bad dtype', dict(dtype=NODT)),
+        ('igemm_pws: grid out of range', dict(B=big))])
+    for kw in (dict(y=odd), dict(bn_y=odd, bn_sums=p), dict(x=p, x_ldc=72), dict(y=p, y_ldc=72), dict(bn_y=p, bn_sums=p, Cout_p=72)):
+        refused('clamd_conv3x3', _C3, c3, split, dtype=SPLIT, **kw)
+    for kw in (dict(Cout_p=48), dict(x_ldc=68), dict(y_ldc=68)):
+        refused('clamd_conv3x3', _C3, c3, padded, **kw)
+    refused('clamd_conv3x3', _C3, c3, n + 'bn_y and bn_sums go together', bn_sums=p, stat_rows=4)
+    refused('clamd_conv3x3', _C3, c3, n + 'grid out of range', B=big, tune=ws1)
+    bias_table = n + 'the border-class bias table needs the persistent kernel (ask clamd_conv3x3_border_bias_ok), a table and H, W >= 2'
+    for kw in (dict(bias=p, tune=direct), dict(bias=p, tune=ws1), dict(bias=p, H=1), dict(bias=p, W=1), dict(bias=p, Cin_p=512)):
+        refused('clamd_conv3x3', _C3, c3, bias_table, relu=3, **kw)
+    # the rows are those of the structure the plan chose: workgroups of the persistent kernel, 256- / 512- / 128-pixel tiles
+    for t, have in ((direct, 4), (ws1, 4), (tref(igemm_pws=0, igemm_ws=3), 2), (tref(igemm_pws=0, igemm_ws=4), 8)):
+        refused('clamd_conv3x3', _C3, c3, rows % ('conv3x3', 7, have), stats=p, stat_rows=7, tune=t)
+    refused('clamd_conv3x3', _C3, c3, rows % ('conv3x3', 3, 4), bn_y=p, bn_sums=p, stat_rows=3)
+    # each structure's launcher answers for the dtype first, then for its own grid (2^32 workgroups: 2^30 tiles x 4 slabs)
+    for t, who in ((direct, 'igemm'), (ws1, 'igemm_ws')):
+        refused('clamd_conv3x3', _C3, c3, who + ': bad dtype', dtype=NODT, tune=t)
+        refused('clamd_conv3x3', _C3, c3, who + ': bad dtype', dtype=NODT, tune=t, B=big >> 2, Cout_p=256)
+        refused('clamd_conv3x3', _C3, c3, who + ': grid out of range', tune=t, B=big >> 2, Cout_p=256)
+
+    c1 = {k: v for k, v in c3.items() if k not in ('m_fastest', 'tune')}
+    n = 'conv1x1: '
+    chain('clamd_conv1x1', _C1, c1, [
+        (n + 'relu must be 0 or 1', dict(relu=2))] + common('x', 'y', 'Cin_p') + [
+        (n + 'bn_y and bn_sums go together', dict(bn_y=p)),
+        (rows % ('conv1x1', 7, 4), dict(stats=p, stat_rows=7)),
+        ('igemm: bad dtype', dict(dtype=NODT)),
+        ('igemm: grid out of range', dict(B=big >> 2, Cout_p=256))])
+    refused('clamd_conv1x1', _C1, c1, n + 'bn_y and bn_sums go together', bn_sums=p, stat_rows=4)
+    refused('clamd_conv1x1', _C1, c1, rows % ('conv1x1', 3, 8), bn_y=p, bn_sums=p, stat_rows=3, B=2, H=17, W=18)
+    refused('clamd_conv1x1', _C1, c1, split, dtype=SPLIT, bn_y=odd, bn_sums=p)
+
+    lg = dict(x=None, x_ldc=64, w=None, bias=None, logits=None, pred=p, B=1, H=32, W=32, Cin_p=64, Cout_p=64, num_classes=21, dtype=F32, stream=None)
+    head = lambda: [                         # the fp32 NCHW output is no NHWC tensor: no bf16x3 check of it, and its pitch stands in as 8
+        ('igemm: empty problem', dict(W=0)),
+        (split, dict(dtype=SPLIT, x=odd)),
+        (padded, dict(Cin_p=40)),
+        (image, dict(H=4096, W=4096)),
+        (filt, dict(Cin_p=8192, Cout_p=8192))]
+    chain('clamd_conv1x1_logits', _LOGITS, lg, head() + [
+        ('conv1x1_logits: num_classes > padded Cout', dict(num_classes=65)),
+        ('igemm: bad dtype', dict(dtype=NODT)),
+        ('igemm: grid out of range', dict(B=big >> 2, Cout_p=256))])
+    refused('clamd_conv1x1_logits', _LOGITS, lg, 'conv1x1_logits: num_classes > padded Cout', dtype=SPLIT, logits=odd, num_classes=65)
+    n = 'conv1x1_argmax: '
+    chain('clamd_conv1x1_argmax', _ARGMAX, lg, head() + [
+        (n + 'pred is null', dict(pred=None)),
+        (n + 'num_classes must be in [1, min(64, padded Cout)]', dict(num_classes=0)),
+        (n + 'padded Cout must be 32 or 64 (the arg-max runs inside one 64-channel slab)', dict(Cout_p=96)),
+        ('igemm: bad dtype', dict(dtype=NODT))])
+    for kw in (dict(num_classes=65, Cout_p=96), dict(num_classes=33, Cout_p=32)):
+        refused('clamd_conv1x1_argmax', _ARGMAX, lg, n + 'num_classes must be in [1, min(64, padded Cout)]', **kw)
+
+    ct = dict(x=None, x_ldc=64, w=None, bias=None, y=None, y_ldc=64, B=1, H=32, W=32, Cin_p=64, Cout_p=64, dtype=F32, stream=None)
+    chain('clamd_convT2x2_fwd', _CT_FWD, ct, common('x', 'y', 'Cin_p')[:5] + [
+        (filt, dict(Cin_p=8192, Cout_p=2048)),               # the GEMM's N is 4 Cout_p
+        ('igemm: bad dtype', dict(dtype=NODT)),
+        ('igemm: grid out of range', dict(B=big >> 2, Cout_p=64))])
+    refused('clamd_convT2x2_fwd', _CT_FWD, ct, padded, Cout_p=12)
+    dg = dict(gy=None, gy_ldc=64, w=None, gx=None, gx_ldc=64, bn_y=None, bn_sums=None, stat_rows=0, B=1, H=32, W=32, Cin_p=64, Cout_p=64, dtype=F32,
+              stream=None)
+    n = 'convT2x2_dgrad: '
+    chain('clamd_convT2x2_dgrad', _CT_DGRAD, dg, [
+        ('igemm: empty problem', dict(H=0)),
+        (split, dict(dtype=SPLIT, gy=odd)),
+        (padded, dict(Cin_p=40)),
+        (image, dict(H=2048, W=2048, gy_ldc=32, gx_ldc=8)),
+        (out_image, dict(H=2048, W=2048, gy_ldc=8, gx_ldc=32)),
+        (filt, dict(Cin_p=8192, Cout_p=2048)),
+        (n + 'bn_y and bn_sums go together', dict(bn_y=p, bn_sums=None)),
+        (rows % ('convT2x2_dgrad', 7, 4), dict(bn_y=p, bn_sums=p, stat_rows=7)),
+        ('igemm: bad dtype', dict(dtype=NODT)),
+        ('igemm: grid out of range', dict(B=big >> 2, Cin_p=256))])
+    refused('clamd_convT2x2_dgrad', _CT_DGRAD, dg, n + 'bn_y and bn_sums go together', bn_sums=p)
+    refused('clamd_convT2x2_dgrad', _CT_DGRAD, dg, split, dtype=SPLIT, bn_y=p, bn_sums=p, Cin_p=40)
+    # The image bounds count 4 H W pixels for the data gradient alone, for both of its images (its INPUT is the 2H x 2W one); the forward
+    # launch, whose OUTPUT is 2H x 2W, is bounded as H x W.  2048 x 2048 x 32 channels: 2^29 bytes as H x W, 2^31 as 2H x 2W.
+    refused('clamd_convT2x2_fwd', _CT_FWD, ct, 'igemm: bad dtype', H=2048, W=2048, x_ldc=32, y_ldc=32, dtype=NODT)
+    refused('clamd_convT2x2_dgrad', _CT_DGRAD, dg, image, H=2048, W=2048, gy_ldc=32, gx_ldc=32, dtype=NODT)
+
+    wg = dict(mode=0, a=None, a_ldc=64, b=None, b_ldc=64, ws=None, ws_bytes=0, out=None, B=1, H=32, W=32, Rp=64, Cp=64, R=64, C=64, r_seg0=64,
+              r_seg0p=64, c_seg0=64, c_seg0p=64, dtype=F32, tune=None, stream=None)
+    n = 'wgrad: '
+    chain('clamd_wgrad', _WG, wg, [
+        (n + 'bad mode', dict(mode=3)),
+        tuning,
+        (n + 'channel counts/pitches must be padded', dict(Rp=48)),
+        (n + 'empty problem', dict(B=0)),
+        (split, dict(dtype=SPLIT, a=odd)),
+        (n + 'one image exceeds 2^30 bytes', dict(H=2048, W=2048)),
+        (n + 'workspace too small', dict(ws_bytes=16 * 9 * 64 * 64 * 4 - 1)),
+        (n + 'bad dtype', dict(dtype=NODT, ws_bytes=1 << 40))])
+    refused('clamd_wgrad', _WG, wg, n + 'bad mode', mode=-1)
+    for kw in (dict(Cp=40), dict(a_ldc=68), dict(b_ldc=68)):
+        refused('clamd_wgrad', _WG, wg, n + 'channel counts/pitches must be padded', **kw)
+    for kw in (dict(b=odd), dict(a=p, a_ldc=72), dict(b=p, b_ldc=72)):
+        refused('clamd_wgrad', _WG, wg, split, dtype=SPLIT, **kw)
+    # the ConvTranspose2d gradient's B operand lives on the 2H x 2W grid
+    refused('clamd_wgrad', _WG, wg, n + 'one image exceeds 2^30 bytes', mode=2, H=1024, W=1024, a_ldc=8)
+    refused('clamd_wgrad', _WG, wg, n + 'one image exceeds 2^30 bytes', H=2048, W=2048, b_ldc=8)
+    # slabs of the split-K plan: fp32 32 x 32 -> 16 tiles of 2 x 32 (the 16 splits above), of 4 x 16 with wgrad_tw16; the 2-per-CU
+    # kernel (wgrad_ws = 0) takes twice the slabs of the producer/consumer one when the tiles allow; 1x1 and 2x2 forms have 1 and 4 taps
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', H=64, W=64, ws_bytes=64 * 9 * 64 * 64 * 4 - 1, tune=tref(wgrad_ws=0))
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', H=64, W=64, Rp=256, Cp=256, ws_bytes=16 * 9 * 256 * 256 * 4 - 1)
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', H=64, W=64, Rp=256, Cp=256, ws_bytes=32 * 9 * 256 * 256 * 4 - 1, tune=tref(wgrad_ws=0))
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', mode=1, ws_bytes=16 * 64 * 64 * 4 - 1)
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', mode=2, ws_bytes=32 * 4 * 64 * 64 * 4 - 1)
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', dtype=1, ws_bytes=8 * 9 * 64 * 64 * 4 - 1)
+    refused('clamd_wgrad', _WG, wg, n + 'workspace too small', ws_bytes=9 * 64 * 64 * 4 - 1, tune=tref(wgrad_blocks=1))
+
+    sr = dict(op=ops['conv1x1'], B=1, H=32, W=32, Cin_p=64, Cout_p=64, dtype=F32, fused_bn=0, tune=None)
+    n = 'stat_rows: '
+    chain('clamd_stat_rows', _ROWS, sr, [
+        (n + 'empty problem', dict(Cout_p=0)),
+        tuning,
+        (n + 'unknown op', dict(op=99)),
+        (n + 'out of range', dict(B=big))])
+    for kw in (dict(B=0), dict(H=-1), dict(W=0)):
+        refused('clamd_stat_rows', _ROWS, sr, n + 'empty problem', **kw)
+    refused('clamd_stat_rows', _ROWS, sr, n + 'out of range', op=ops['convT_dgrad'], B=big)
+    for t in (direct, ws1):
+        refused('clamd_stat_rows', _ROWS, sr, n + 'out of range', op=ops['conv3x3'], B=big, tune=t)
+
+
 def test_abi_rejects_bad_arguments_before_any_launch(C):
     """Error behaviour of the C ABI: argument validation happens on the host before anything is
     enqueued, the entry point returns a negative status, clamd_last_error() names the problem and the Python side raises
@@ -531,7 +704,9 @@ def test_abi_rejects_bad_arguments_before_any_launch(C):
         assert needle in lib.clamd_last_error().decode()
     keep.append(C._lib.Tuning())
     keep[-1].wino_mt = 7                 # out of range
-    _check_winograd_refusals(lib, tref, keep[-1].ref())
+    bad_tune = keep[-1].ref()
+    _check_winograd_refusals(lib, tref, bad_tune)
+    _check_direct_conv_refusals(lib, tref, bad_tune, dict(conv3x3=C._lib.OP_CONV3X3, conv1x1=C._lib.OP_CONV1X1, convT_dgrad=C._lib.OP_CONVT2X2_DGRAD))
     # clamd_conv3x3_border_bias_ok / clamd_conv3x3_bn_sums / clamd_stat_rows(CLAMD_OP_CONV3X3) over the branches of plan_conv3x3 and pws_rows:
     # the persistent kernel takes igemm_pws 2, or 1 up to 256 input channels; K-steps in pairs (Kp % 64 in bf16); bn_y only in bf16
     ok = lambda H, W, Kp, dt, **kw: lib.clamd_conv3x3_border_bias_ok(2, H, W, Kp, 64, dt, tref(**kw) if kw else None)
