@@ -11,9 +11,10 @@ from .consolidate import Consolidation  # noqa: F401
 from .pseudo import PseudoLabeler, thresholds_from_histogram  # noqa: F401
 from .pod import LocalPODLoss  # noqa: F401
 from .replay import ReplayMemory, class_pixel_counts  # noqa: F401
+from .augment import RandomScaleCrop, augment_batch, params_from_draws  # noqa: F401
 from .metrics import argmax_confusion, eval_metrics, metrics_from_confusion  # noqa: F401
 from .trainer import Trainer, default_config  # noqa: F401
-from . import consolidate, data, ddp, pod, pseudo, replay, syncbn  # noqa: F401
+from . import augment, consolidate, data, ddp, pod, pseudo, replay, syncbn  # noqa: F401
 
-__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'FusedAdam', 'Consolidation', 'PseudoLabeler', 'thresholds_from_histogram', 'LocalPODLoss', 'ReplayMemory', 'class_pixel_counts', 'replay', 'Trainer', 'default_config',
+__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'FusedAdam', 'Consolidation', 'PseudoLabeler', 'thresholds_from_histogram', 'LocalPODLoss', 'ReplayMemory', 'class_pixel_counts', 'replay', 'RandomScaleCrop', 'augment_batch', 'params_from_draws', 'augment', 'Trainer', 'default_config',
            'argmax_confusion', 'eval_metrics', 'metrics_from_confusion', 'data', 'ddp', 'synth']

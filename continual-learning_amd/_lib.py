@@ -134,6 +134,7 @@ SIGNATURES = {
     'clamd_class_pixel_counts': (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _P]),
     'clamd_replay_store': (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _LL, _P]),
     'clamd_replay_mix': (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _LL, _P]),
+    'clamd_augment_batch': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _D, _LL, _P, _P]),
     'clamd_adam_step': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     'clamd_adam_step_consolidated': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),

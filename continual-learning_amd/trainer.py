@@ -17,7 +17,9 @@ Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.Sync
 of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
 confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`` adds Local POD distillation of the logits (build-defined,
 pod.py); ``begin_task2(replay=M, replay_batch=R)`` keeps M exemplars of the finished task in an on-device memory and mixes R of them into
-every batch (build-defined, replay.py).
+every batch (build-defined, replay.py).  ``cfg.augment=True`` (with augment_scale, augment_flip, augment_seed) rescales, crops or pads and
+flips every training batch -- the replayed rows included -- in one launch before the forward pass (build-defined, augment.py); off by
+default, and then nothing on the step's path changes.
 """
 import os
 import warnings
@@ -34,6 +36,7 @@ from .consolidate import Consolidation
 from .pseudo import PseudoLabeler
 from .pod import LocalPODLoss
 from .replay import ReplayMemory
+from .augment import RandomScaleCrop
 from . import syncbn
 from .unet import UNet
 
@@ -41,7 +44,8 @@ from .unet import UNet
 def default_config(**kw):
     """Defaults of main.py:64-105 for the flags the hot path reads."""
     cfg = dict(n_iters=10000, train_batch_size=2, lr=1e-4, lr_exp=0.9, beta1=0.5, beta2=0.99, h_image_size=512,
-               w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False)
+               w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False,
+               augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -61,6 +65,8 @@ class Trainer:
         self.replay = None                # replay.ReplayMemory once begin_task2(replay > 0) ran
         self.replay_batch = 0             # exemplars mixed into every batch
         self.replay_boundary = None       # c_old of the last call that added a segment: the next segment's first class
+        self.augment = None               # augment.RandomScaleCrop when cfg.augment is set (build_model)
+        self.step_labels = None           # the labels the last train_step's loss was computed against, rows [0, B), before pseudo-labelling
         self.build_model()
 
     def build_model(self):
@@ -72,6 +78,11 @@ class Trainer:
         self.optim = FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
         self.scheduler = LambdaLR(self.optim, lr_lambda=lambda n: (1 - n / cfg.n_iters) ** cfg.lr_exp)
         self.c_loss = CrossEntropyLoss().to(self.device)
+        self.augment = None
+        if getattr(cfg, 'augment', False):       # each rank draws its own scales, crops and flips
+            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+            self.augment = RandomScaleCrop(scale=getattr(cfg, 'augment_scale', (0.5, 2.0)), flip=getattr(cfg, 'augment_flip', True),
+                                           ignore_index=self.c_loss.ignore_index, seed=int(getattr(cfg, 'augment_seed', 0)) + rank)
 
     def reset_grad(self):
         self.optim.zero_grad()
@@ -292,13 +303,16 @@ class Trainer:
             snap['consolidation_state'] = cons_host
         if replay_host is not None:
             snap['replay_state'] = replay_host
+        if self.augment is not None:                 # a third optional key: the configuration and the generator state (a host tensor)
+            snap['augment_state'] = self.augment.state_dict()
         return snap
 
     def save_network(self, network_label, epoch_label, epoch, save_dir):
         """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/
         scheduler_state (loadable by the reference's load_network and by torch.optim.Adam); with elastic weight consolidation
         active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores; with an exemplar memory
-        replay_state (ReplayMemory.state_dict() on the host, replay_batch and the class boundary), ignored by the reference too."""
+        replay_state (ReplayMemory.state_dict() on the host, replay_batch and the class boundary), ignored by the reference too; with
+        augmentation augment_state (RandomScaleCrop.state_dict(): configuration and generator state), likewise."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -318,7 +332,17 @@ class Trainer:
         self.scheduler.load_state_dict(ck['scheduler_state'])
         self.load_consolidation_state(ck.get('consolidation_state'))
         self.load_replay_state(ck.get('replay_state'))
+        self.load_augment_state(ck.get('augment_state'))
         return True
+
+    def load_augment_state(self, state):
+        """Restores what snapshot() stored under 'augment_state' (None, e.g. a checkpoint without the key: nothing changes): the next step
+        draws what the uninterrupted run would have drawn."""
+        if state is None:
+            return
+        if self.augment is None:
+            self.augment = RandomScaleCrop()
+        self.augment.load_state_dict(state)
 
     def load_replay_state(self, state):
         """Restores what snapshot() stored under 'replay_state' (None, e.g. a checkpoint without the key: nothing changes)."""
@@ -340,9 +364,16 @@ class Trainer:
 
     def train_step(self, inputs, labels):
         """trainer.py:172-176.  With an exemplar memory the batch is first extended by replay_batch exemplars: everything below, and the
-        returned outputs, cover B + replay_batch rows, the caller's batch being rows [0, B)."""
+        returned outputs, cover B + replay_batch rows, the caller's batch being rows [0, B).  With cfg.augment the (mixed) batch is then
+        rescaled, cropped or padded and flipped in one launch, exemplars included: everything below sees the augmented batch.
+        ``self.step_labels`` keeps the labels the loss is computed against, rows [0, B), before pseudo-labelling: the caller's own tensor
+        without augmentation."""
+        self.step_labels = labels
         if self.replay is not None and self.replay_batch > 0:
             inputs, labels = self.replay.mix(inputs, labels, self.replay_batch)
+        if self.augment is not None:
+            inputs, labels = self.augment(inputs, labels)
+            self.step_labels = labels[:self.step_labels.shape[0]]
         outputs = self.model(inputs)
         self.reset_grad()
         distill = getattr(self, 'distill', None) if self.old_model is not None else None
@@ -393,6 +424,7 @@ class Trainer:
             outputs, loss = self.train_step(inputs, labels)
             if i % self.cfg.stats_every == 0:
                 out = outputs.detach()
+                labels = self.step_labels                # the caller's labels, or what the augmentation made of them
                 if out.shape[0] != labels.shape[0]:      # replayed rows behind the caller's batch
                     out = out[:labels.shape[0]]
                 c, _ = argmax_confusion(out, labels, self.cfg.num_classes)

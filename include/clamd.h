@@ -514,6 +514,33 @@ int clamd_replay_store(const float* images, const long long* labels, const int* 
 int clamd_replay_mix(const float* cur_images, const long long* cur_labels, int B, const void* store_images, const unsigned char* store_labels,
                      int store_fp32, int cap, const long long* slots, const int* flips, int R, float* out_images, long long* out_labels,
                      unsigned int* bad, int C, int H, int W, long long ignore_index, void* stream);
+/* ---- training augmentation (augment.hip) ----------------------------------------------------------------------
+ * Build-defined, parity unpinned (the reference stops at Pad + CenterCrop + Normalize): random scale, crop or pad, and horizontal flip of
+ * a batch and its labels in one launch.  images fp32 [B, C, H, W] -> out_images of the same shape, labels int64 [B, H, W] -> out_labels;
+ * either pair may be NULL (both members), not both pairs.  params: DEVICE long long [B][4] = {step, y0, x0, flags}.  step is the source
+ * pitch per output pixel in Q16 (65536 = scale 1), accepted in [2^13, 2^19] (scale 8 ... 1/8); (y0, x0) the Q16 source coordinate of output
+ * pixel (0, 0); flags bit 0 the horizontal flip.  H, W <= 4096.
+ * Definition -- every coordinate in 64-bit integers, hence exact.  Output pixel (i, j'), j = flip ? W - 1 - j' : j':
+ *   sy = y0 + i * step, sx = x0 + j * step;  inside <=> 0 <= sy + 32768 < H * 65536 and 0 <= sx + 32768 < W * 65536.
+ *   label = inside ? labels[b][(sy + 32768) >> 16][(sx + 32768) >> 16] (copied verbatim, no class check) : ignore_index.
+ *   image = fill (converted to fp32) when not inside; inside: fy = sy >> 16 (arithmetic shift), wy = (float)(sy & 65535) * 2^-16, rows
+ *   clamp(fy, 0, H - 1) and clamp(fy + 1, 0, H - 1), the columns alike from sx; with the four taps a b / c d:
+ *   top = a + wx * (b - a), bot = c + wx * (d - c), out = top + wy * (bot - top) in fp32 (the compiler may contract into fma).
+ * That is resize(bilinear, align_corners = False) for the image and nearest-exact for the labels, then crop or pad, then flip; the image's
+ * fill region and the labels' ignore region are the same pixels by construction.  step == 65536 with y0 == x0 == 0 returns the input's bits
+ * (both weights are 0; the formula is evaluated all the same, so a -0.0 may come back as +0.0 and an infinity or NaN reaches the pixels
+ * whose taps include it).
+ * A step outside the range gives an all-fill image and all-ignore_index labels for that row and adds 1 to *bad (unsigned int [1], the caller
+ * zeroes it): a guard like clamd_replay_mix's, not an expected path.
+ * A lane owns four consecutive output pixels of a row (one 16-byte store per channel, two 16-byte label stores; the row's and the four
+ * pixels' coordinates formed once for all channels) when W % 4 == 0 and the OUTPUT bases are aligned -- out_images 16 bytes, out_labels 32
+ * bytes --; a one-pixel instantiation of the same arithmetic inside the same entry point for any other width or alignment (fp32 needs 4,
+ * int64 8 bytes at least).  The taps are 4-byte gathers on either path.  out must not overlap any input.
+ * Enqueue only: no allocation, no host synchronisation, device taken from the stream; no atomics except the guard's integer add:
+ * bit-reproducible.  An empty problem, H or W above 4096, an input without its output or the reverse, a misaligned tensor: an error, nothing
+ * launched. */
+int clamd_augment_batch(const float* images, const long long* labels, const long long* params, int B, int C, int H, int W,
+                        float* out_images, long long* out_labels, double fill, long long ignore_index, unsigned int* bad, void* stream);
 /* torch.optim.Adam.step over all parameters in one launch (trainer.py:108-110,176); hyper/step/derived live on the
  * device so a captured graph can be replayed with a new learning rate.  l2_accum_dev (optional, with the L2-to-old-weights
  * term): 1 + nchunks floats, [0] = sum ||theta - theta_old||^2 of this step, [1..] = per-workgroup partials added in a fixed
