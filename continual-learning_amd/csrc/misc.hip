@@ -250,8 +250,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackJob* __restrict__ j
 // hyper (device, fp32): [0] lr  [1] beta1  [2] beta2  [3] eps  [4] grad_scale  [5] l2_lambda
 // state (device): step counter (int), derived[0] = lr/bc1, derived[1] = sqrt(bc2)
 struct AdamTensor { float* p; const float* g; float* m; float* v; const float* old; long long n; };
-struct AdamChunk { int tensor; int chunk; };
-constexpr int ADAM_CHUNK = 4096;
+// AdamChunk and ADAM_CHUNK: clamd_internal.h (shared with sgd.hip)
 
 __global__ void adam_prepare_kernel(const float* hyper, int* step, float* derived) {
     const int s = *step + 1;
@@ -610,6 +609,10 @@ __global__ void fill_kernel(float* p, long long n, float v) {
 }  // namespace clamd
 
 using namespace clamd;
+
+void clamd_launch_partial_sum(float* accum, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, stream, accum, n);
+}
 
 int clamd_launch_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, const FoldBias* fold, hipStream_t stream) {
     if (njobs <= 0 || total_blocks <= 0) return clamd_fail("pack: empty job table");

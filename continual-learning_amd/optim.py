@@ -12,6 +12,9 @@ Optional L2-to-old-weights regulariser (build-defined): ``se
 Optional elastic weight consolidation (build-defined as well): ``set_consolidation(old_params, importance, lam)`` adds
 lam*omega*(theta - theta_old); such a step runs ``clamd_adam_step_consolidated`` (36 B / parameter), every other step the unchanged
 ``clamd_adam_step``.
+
+``FusedSGD`` (below) is the second optimiser: torch.optim.SGD with momentum, Nesterov and weight decay in one launch of
+``clamd_sgd_step`` (csrc/sgd.hip), with the same surface and the same two anchor terms (shared through ``_AnchorTerms``).
 """
 import numpy as np
 import torch
@@ -22,7 +25,125 @@ from ._lib import call, ptr
 _TENSOR_DT = np.dtype([('p', 'u8'), ('g', 'u8'), ('m', 'u8'), ('v', 'u8'), ('old', 'u8'), ('n', 'i8')])
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _AnchorTerms:
+    """The two build-defined pulls towards an anchor that FusedAdam and FusedSGD share (one anchor pointer per tensor serves both): the
+    L2-to-old-weights term and elastic weight consolidation.  The optimiser provides param_groups, _NAME, _table, _hyper_host and, after a
+    step, _l2acc / _ewcacc."""
+
+    def _init_anchor_terms(self):
+        self._l2_lambda = 0.0
+        self._anchor = None
+        self._l2_on = False           # the anchor serves the L2 term, the consolidation term, or both
+        self._importance = None
+        self._ewc_lambda = 0.0
+        self._ewcacc = None
+
+    @staticmethod
+    def _grown(old, new_shape, fill):
+        """`old` with rows appended along dim 0 up to new_shape; the new rows take `fill`'s (None: zero)."""
+        out = torch.zeros(new_shape, dtype=old.dtype, device=old.device)
+        out[:old.shape[0]].copy_(old)
+        if fill is not None:
+            out[old.shape[0]:].copy_(fill[old.shape[0]:])
+        return out
+
+    def _growth_plan(self, mapping):
+        """Validates a replace_params mapping -> [(index in the group, old parameter, new parameter)]."""
+        params = self.param_groups[0]['params']
+        index = {id(p): i for i, p in enumerate(params)}
+        todo = []
+        for old, new in mapping.items():
+            if id(old) not in index:
+                raise ValueError(f'{self._NAME}.replace_params: a key of the mapping is not a parameter of this optimiser')
+            if old.dim() != new.dim() or old.dim() < 1 or new.shape[0] <= old.shape[0] or new.shape[1:] != old.shape[1:]:
+                raise ValueError(f'{self._NAME}.replace_params: {tuple(old.shape)} -> {tuple(new.shape)} is not growth along dim 0')
+            if new.device != old.device or new.dtype != old.dtype:
+                raise ValueError(f'{self._NAME}.replace_params: the new parameter must keep the device and dtype')
+            todo.append((index[id(old)], old, new))
+        return todo
+
+    def _grow_anchor_terms(self, i, new):
+        """The anchor of the new rows is their current (initial) value and their importance zero."""
+        if self._anchor is not None:
+            self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
+        if self._importance is not None:
+            self._importance[i] = self._grown(self._importance[i], new.shape, None)
+
+    def set_l2_anchor(self, old_params, lam):
+        """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot).  With a consolidation set the
+        anchor is shared (one pointer per tensor in the device table): it has to be the same snapshot."""
+        anchor = [o.detach().contiguous().float() for o in old_params] if old_params is not None else None
+        if anchor is not None and self._importance is not None:
+            self._same_anchor(anchor)
+        elif self._importance is None:
+            self._anchor = anchor
+        self._l2_on = anchor is not None
+        self._l2_lambda = float(lam) if anchor is not None else 0.0
+        self._table = None
+        self._hyper_host = None
+
+    def _same_anchor(self, anchor):
+        """Setup-time check (compares on the device, so it synchronises; never on the step path)."""
+        if len(anchor) != len(self._anchor) or not all(a.shape == b.shape and a.device == b.device and
+                                                       (a.data_ptr() == b.data_ptr() or torch.equal(a, b))
+                                                       for a, b in zip(anchor, self._anchor)):
+            raise ValueError(f'{self._NAME}: the L2 anchor and the consolidation anchor must be the same snapshot (one anchor per tensor)')
+
+    @property
+    def l2_lambda(self):
+        """Weight of the L2-to-old-weights term (0 when it is off)."""
+        return self._l2_lambda if self._l2_on else 0.0
+
+    def l2_penalty(self):
+        """lam * sum ||theta - theta_old||^2 as accumulated by the LAST step (device scalar)."""
+        return self._l2acc[:1] * self._l2_lambda
+
+    def set_consolidation(self, old_params, importance, lam):
+        """Elastic weight consolidation: every step adds lam * importance * (theta - old) to the gradient inside the optimiser's kernel.
+        old_params / importance: lists of tensors aligned with this optimiser's parameters (same shapes, on the parameters' device; the
+        importance fp32 and contiguous -- it is read in place, so a consolidate.Consolidation can update it between steps).
+        importance >= 0 is the caller's contract: it is not checked (that would synchronise).  old_params None clears the term."""
+        if old_params is None:
+            self._importance, self._ewc_lambda = None, 0.0
+            if not self._l2_on:
+                self._anchor = None
+            self._table = None
+            self._hyper_host = None
+            return
+        params = self.param_groups[0]['params']
+        old_params, importance = list(old_params), list(importance)
+        if len(old_params) != len(params) or len(importance) != len(params):
+            raise ValueError(f'{self._NAME}.set_consolidation: {len(params)} parameters, {len(old_params)} anchors, {len(importance)} importance tensors')
+        for i, (p, o, w) in enumerate(zip(params, old_params, importance)):
+            if o.shape != p.shape or w.shape != p.shape:
+                raise ValueError(f'{self._NAME}.set_consolidation: parameter {i} has shape {tuple(p.shape)}, anchor {tuple(o.shape)}, '
+                                 f'importance {tuple(w.shape)}')
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                raise ValueError(f'{self._NAME}.set_consolidation: importance {i} must be contiguous fp32')
+            if o.device != p.device or w.device != p.device:
+                raise ValueError(f'{self._NAME}.set_consolidation: parameter {i} is on {p.device}, anchor on {o.device}, importance on {w.device}')
+        if not float(lam) >= 0.0:
+            raise ValueError(f'{self._NAME}.set_consolidation: lam must be >= 0')
+        anchor = [o.detach().contiguous().float() for o in old_params]
+        if self._l2_on:
+            self._same_anchor(anchor)         # the L2 anchor stays: one pointer per tensor serves both terms
+        else:
+            self._anchor = anchor
+        self._importance = [w.detach() for w in importance]
+        self._ewc_lambda = float(lam)
+        self._table = None
+        self._hyper_host = None
+
+    def consolidation_penalty(self):
+        """(lam / 2) * sum importance * (theta - theta_old)^2 as accumulated by the LAST step (device scalar)."""
+        if self._ewcacc is None:
+            raise RuntimeError(f'{self._NAME}.consolidation_penalty: no step with a consolidation has run')
+        return self._ewcacc[:1] * (0.5 * self._ewc_lambda)
+
+
+class FusedAdam(_AnchorTerms, torch.optim.Optimizer):
+    _NAME = 'FusedAdam'
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
         betas = tuple(betas)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
@@ -31,12 +152,7 @@ class FusedAdam(torch.optim.Optimizer):
         if len(self.param_groups) != 1:
             raise ValueError('FusedAdam supports a single parameter group (as trainer.py:108 builds)')
         self.grad_scale = grad_scale
-        self._l2_lambda = 0.0
-        self._anchor = None
-        self._l2_on = False           # the anchor serves the L2 term, the consolidation term, or both
-        self._importance = None
-        self._ewc_lambda = 0.0
-        self._ewcacc = None
+        self._init_anchor_terms()
         self._table = None
         self._hyper_host = None
         self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
@@ -100,15 +216,6 @@ class FusedAdam(torch.optim.Optimizer):
         if hasattr(self, '_m'):
             del self._m
 
-    @staticmethod
-    def _grown(old, new_shape, fill):
-        """`old` with rows appended along dim 0 up to new_shape; the new rows take `fill`'s (None: zero)."""
-        out = torch.zeros(new_shape, dtype=old.dtype, device=old.device)
-        out[:old.shape[0]].copy_(old)
-        if fill is not None:
-            out[old.shape[0]:].copy_(fill[old.shape[0]:])
-        return out
-
     @torch.no_grad()
     def replace_params(self, mapping):
         """Class-incremental head growth (UNet.expand_classes): swaps parameter objects inside the group and re-homes their state.
@@ -118,26 +225,14 @@ class FusedAdam(torch.optim.Optimizer):
         finished task never had.  The importance list is replaced (grown copies); a Consolidation re-installs its own views after
         Consolidation.grow.  Device tables are rebuilt at the next step."""
         params = self.param_groups[0]['params']
-        index = {id(p): i for i, p in enumerate(params)}
-        todo = []
-        for old, new in mapping.items():
-            if id(old) not in index:
-                raise ValueError('FusedAdam.replace_params: a key of the mapping is not a parameter of this optimiser')
-            if old.dim() != new.dim() or old.dim() < 1 or new.shape[0] <= old.shape[0] or new.shape[1:] != old.shape[1:]:
-                raise ValueError(f'FusedAdam.replace_params: {tuple(old.shape)} -> {tuple(new.shape)} is not growth along dim 0')
-            if new.device != old.device or new.dtype != old.dtype:
-                raise ValueError('FusedAdam.replace_params: the new parameter must keep the device and dtype')
-            todo.append((index[id(old)], old, new))
+        todo = self._growth_plan(mapping)
         states = [self.state.get(p) for p in params]
         for i, old, new in todo:
             st = states[i]
             if st:       # moments of the leading rows; _init_state re-homes them into new flat buffers at the next step
                 states[i] = {'step': st['step'], 'exp_avg': self._grown(st['exp_avg'], new.shape, None),
                              'exp_avg_sq': self._grown(st['exp_avg_sq'], new.shape, None)}
-            if self._anchor is not None:
-                self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
-            if self._importance is not None:
-                self._importance[i] = self._grown(self._importance[i], new.shape, None)
+            self._grow_anchor_terms(i, new)
             self.state.pop(old, None)
             params[i] = new
         step = float(self._step_host) if hasattr(self, '_step_host') else None
@@ -147,77 +242,6 @@ class FusedAdam(torch.optim.Optimizer):
         if hasattr(self, '_m'):
             del self._m              # as after load_state_dict: the flat moment buffers are laid out again
         self._table = None
-
-    def set_l2_anchor(self, old_params, lam):
-        """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot).  With a consolidation set the
-        anchor is shared (one pointer per tensor in the device table): it has to be the same snapshot."""
-        anchor = [o.detach().contiguous().float() for o in old_params] if old_params is not None else None
-        if anchor is not None and self._importance is not None:
-            self._same_anchor(anchor)
-        elif self._importance is None:
-            self._anchor = anchor
-        self._l2_on = anchor is not None
-        self._l2_lambda = float(lam) if anchor is not None else 0.0
-        self._table = None
-        self._hyper_host = None
-
-    def _same_anchor(self, anchor):
-        """Setup-time check (compares on the device, so it synchronises; never on the step path)."""
-        if len(anchor) != len(self._anchor) or not all(a.shape == b.shape and a.device == b.device and
-                                                       (a.data_ptr() == b.data_ptr() or torch.equal(a, b))
-                                                       for a, b in zip(anchor, self._anchor)):
-            raise ValueError('FusedAdam: the L2 anchor and the consolidation anchor must be the same snapshot (one anchor per tensor)')
-
-    @property
-    def l2_lambda(self):
-        """Weight of the L2-to-old-weights term (0 when it is off)."""
-        return self._l2_lambda if self._l2_on else 0.0
-
-    def l2_penalty(self):
-        """lam * sum ||theta - theta_old||^2 as accumulated by the LAST step (device scalar)."""
-        return self._l2acc[:1] * self._l2_lambda
-
-    def set_consolidation(self, old_params, importance, lam):
-        """Elastic weight consolidation: every step adds lam * importance * (theta - old) to the gradient inside the Adam kernel.
-        old_params / importance: lists of tensors aligned with this optimiser's parameters (same shapes, on the parameters' device; the
-        importance fp32 and contiguous -- it is read in place, so a consolidate.Consolidation can update it between steps).
-        importance >= 0 is the caller's contract: it is not checked (that would synchronise).  old_params None clears the term."""
-        if old_params is None:
-            self._importance, self._ewc_lambda = None, 0.0
-            if not self._l2_on:
-                self._anchor = None
-            self._table = None
-            self._hyper_host = None
-            return
-        params = self.param_groups[0]['params']
-        old_params, importance = list(old_params), list(importance)
-        if len(old_params) != len(params) or len(importance) != len(params):
-            raise ValueError(f'FusedAdam.set_consolidation: {len(params)} parameters, {len(old_params)} anchors, {len(importance)} importance tensors')
-        for i, (p, o, w) in enumerate(zip(params, old_params, importance)):
-            if o.shape != p.shape or w.shape != p.shape:
-                raise ValueError(f'FusedAdam.set_consolidation: parameter {i} has shape {tuple(p.shape)}, anchor {tuple(o.shape)}, '
-                                 f'importance {tuple(w.shape)}')
-            if w.dtype != torch.float32 or not w.is_contiguous():
-                raise ValueError(f'FusedAdam.set_consolidation: importance {i} must be contiguous fp32')
-            if o.device != p.device or w.device != p.device:
-                raise ValueError(f'FusedAdam.set_consolidation: parameter {i} is on {p.device}, anchor on {o.device}, importance on {w.device}')
-        if not float(lam) >= 0.0:
-            raise ValueError('FusedAdam.set_consolidation: lam must be >= 0')
-        anchor = [o.detach().contiguous().float() for o in old_params]
-        if self._l2_on:
-            self._same_anchor(anchor)         # the L2 anchor stays: one pointer per tensor serves both terms
-        else:
-            self._anchor = anchor
-        self._importance = [w.detach() for w in importance]
-        self._ewc_lambda = float(lam)
-        self._table = None
-        self._hyper_host = None
-
-    def consolidation_penalty(self):
-        """(lam / 2) * sum importance * (theta - theta_old)^2 as accumulated by the LAST step (device scalar)."""
-        if self._ewcacc is None:
-            raise RuntimeError('FusedAdam.consolidation_penalty: no step with a consolidation has run')
-        return self._ewcacc[:1] * (0.5 * self._ewc_lambda)
 
     def sync_hyper(self):
         """Upload lr / betas / eps / gradient scale / L2 and consolidation weights to device memory if they changed on the host (LambdaLR
@@ -268,4 +292,175 @@ class FusedAdam(torch.optim.Optimizer):
                    ptr(self._step_dev), ptr(self._derived), ptr(self._l2acc) if self._anchor is not None else None,
                    _lib.stream_ptr())
         self._step_host += 1                # host-side mirror of the device counter (shared by all param states)
+        return loss
+
+
+_SGD_TENSOR_DT = np.dtype([('p', 'u8'), ('g', 'u8'), ('buf', 'u8'), ('old', 'u8'), ('n', 'i8'), ('decay_mult', 'f4'), ('pad', 'f4')])
+
+
+class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
+    """Fused multi-tensor SGD with momentum, Nesterov and weight decay: ``torch.optim.SGD`` semantics (dampening 0, maximize off) in one
+    launch of ``clamd_sgd_step`` over all parameters, with the same surface as FusedAdam (grad_scale, pre_step_hooks, sync_hyper,
+    set_l2_anchor, set_consolidation, replace_params), so the trainer, ddp.GradSync and Consolidation work with either.
+
+    One parameter group.  ``state[p] == {'momentum_buffer': view into one flat buffer}`` with momentum > 0, no state without; the
+    ``state_dict()`` layout is torch.optim.SGD's, so optimiser checkpoints are interchangeable in both directions.  ``no_decay``: parameters
+    of this optimiser whose weight decay is switched off (BatchNorm weights and biases) without a second group.  Hyper-parameters live in
+    device memory (a replayed graph sees a new learning rate); per element, in this order:
+        g = grad * grad_scale;  g += weight_decay * decay_mult * p;  d = p - old;  g += 2 * l2_lambda * d;  g += ewc_lambda * omega * d
+        buf = momentum * buf + g;  p -= lr * (nesterov ? g + momentum * buf : buf)
+    """
+    _NAME = 'FusedSGD'
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, no_decay=(), grad_scale=1.0):
+        if not lr >= 0.0:
+            raise ValueError(f'FusedSGD: invalid learning rate {lr}')
+        if not momentum >= 0.0:
+            raise ValueError(f'FusedSGD: invalid momentum {momentum}')
+        if not weight_decay >= 0.0:
+            raise ValueError(f'FusedSGD: invalid weight_decay {weight_decay}')
+        if dampening != 0:
+            raise ValueError('FusedSGD: dampening is not supported (it must be 0)')
+        if nesterov and momentum <= 0:
+            raise ValueError('FusedSGD: Nesterov momentum requires a momentum and zero dampening')
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False,
+                        foreach=None, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError('FusedSGD supports a single parameter group (the anchor and importance lists follow model.parameters())')
+        own = {id(p) for p in self.param_groups[0]['params']}
+        self._no_decay = set()
+        for p in no_decay:
+            if id(p) not in own:
+                raise ValueError('FusedSGD: a tensor of no_decay is not a parameter of this optimiser')
+            self._no_decay.add(id(p))
+        self.grad_scale = grad_scale
+        self._init_anchor_terms()
+        self._table = None
+        self._hyper_host = None
+        self._l2acc = None
+        self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
+
+    # -- device state ------------------------------------------------------------------------------------
+    def _init_state(self, params):
+        """Lays the momentum buffers out in one flat buffer (each tensor's slice starts on 16 bytes, as the parameters themselves do; the
+        kernel does not depend on it) and re-homes what load_state_dict or replace_params left in self.state."""
+        dev = params[0].device
+        assert _lib.load().clamd_sizeof_sgd_tensor() == _SGD_TENSOR_DT.itemsize
+        prev = [self.state.get(p) for p in params]
+        self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+        self._hyper_host = None       # a new device buffer: sync_hyper uploads again
+        self._with_momentum = float(self.param_groups[0]['momentum']) > 0
+        self._flat = None
+        for p in params:
+            self.state.pop(p, None)   # momentum 0: no state (a restored {'momentum_buffer': None} goes too)
+        if not self._with_momentum:
+            return
+        self._flat = torch.zeros(sum((p.numel() + 3) // 4 * 4 for p in params), dtype=torch.float32, device=dev)
+        off = 0
+        for p, st in zip(params, prev):
+            buf = self._flat[off:off + p.numel()].view_as(p)
+            if st and st.get('momentum_buffer') is not None:      # absent or None: torch before its first step, starts at zero
+                buf.copy_(st['momentum_buffer'])
+            self.state[p] = {'momentum_buffer': buf}
+            off += (p.numel() + 3) // 4 * 4
+
+    def _build_table(self, params):
+        chunk = _lib.load().clamd_adam_chunk_elems()
+        t = np.zeros(len(params), dtype=_SGD_TENSOR_DT)
+        chunks = []
+        for i, p in enumerate(params):
+            buf = self.state[p]['momentum_buffer'].data_ptr() if self._with_momentum else 0
+            old = self._anchor[i].data_ptr() if self._anchor is not None else 0
+            t[i] = (p.data_ptr(), p.grad.data_ptr(), buf, old, p.numel(), 0.0 if id(p) in self._no_decay else 1.0, 0.0)
+            chunks += [(i, c) for c in range((p.numel() + chunk - 1) // chunk)]
+        dev = params[0].device
+        self._tensors_dev = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
+        self._chunks_dev = torch.tensor(chunks, dtype=torch.int32, device=dev)
+        self._nchunks = len(chunks)
+        self._numel = int(sum(p.numel() for p in params))
+        self._l2acc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+        self._ewcacc = self._importance_dev = None
+        if self._importance is not None:
+            self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
+            self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+        self._table = [(p.data_ptr(), p.grad.data_ptr()) for p in params]
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._table = None            # restored momentum buffers are re-homed into the flat buffer at the next step
+        self._hyper_host = None
+        if hasattr(self, '_flat'):
+            del self._flat
+
+    @torch.no_grad()
+    def replace_params(self, mapping):
+        """Class-incremental head growth, as FusedAdam.replace_params: swaps parameter objects inside the group and re-homes their state.
+        The momentum buffer's leading rows are kept and the new rows start at zero; anchors and importance grow as in FusedAdam (the new
+        rows' anchor is their current value, their importance zero); a no_decay flag follows the swapped parameter.  Device tables are
+        rebuilt at the next step."""
+        params = self.param_groups[0]['params']
+        todo = self._growth_plan(mapping)
+        states = [self.state.get(p) for p in params]
+        for i, old, new in todo:
+            st = states[i]
+            if st and st.get('momentum_buffer') is not None:
+                states[i] = {'momentum_buffer': self._grown(st['momentum_buffer'], new.shape, None)}
+            self._grow_anchor_terms(i, new)
+            if id(old) in self._no_decay:
+                self._no_decay.discard(id(old))
+                self._no_decay.add(id(new))
+            self.state.pop(old, None)
+            params[i] = new
+        for p, st in zip(params, states):
+            if st:
+                self.state[p] = dict(st)
+        if hasattr(self, '_flat'):
+            del self._flat            # as after load_state_dict: the flat momentum buffer is laid out again
+        self._table = None
+
+    def sync_hyper(self):
+        """Upload lr / momentum / weight decay / Nesterov flag / gradient scale / L2 and consolidation weights to device memory if they
+        changed on the host (LambdaLR writes param_groups[0]['lr']).  step() calls this; a replayed HIP graph of the step calls it before
+        every replay, because the captured kernel reads the values from that device buffer."""
+        group = self.param_groups[0]
+        if group['dampening'] != 0 or group['maximize']:
+            raise ValueError('FusedSGD: dampening and maximize are not supported')
+        hyper = (float(group['lr']), float(group['momentum']), float(group['weight_decay']), 1.0 if group['nesterov'] else 0.0,
+                 float(self.grad_scale), float(self._l2_lambda), float(self._ewc_lambda), 0.0)
+        if hyper != self._hyper_host:
+            self._hyper.copy_(torch.tensor(hyper, dtype=torch.float32))
+            self._hyper_host = hyper
+
+    def note_replayed_step(self, n=1):
+        """FusedAdam mirrors its device step counter here; SGD has none, so there is nothing to do."""
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for h in self.pre_step_hooks:
+            h()
+        group = self.param_groups[0]
+        params = group['params']
+        key = []
+        for p in params:
+            gr = p.grad
+            if gr is None:
+                raise RuntimeError('FusedSGD: every parameter must have a gradient (the UNet backward produces all of them)')
+            key.append((p.data_ptr(), gr.data_ptr()))
+        if self._table != key:       # first step, or parameters / gradients moved: validate and rebuild the device table
+            for p in params:
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise RuntimeError('FusedSGD needs contiguous fp32 GPU parameters and gradients: there is no CPU fallback')
+            if not hasattr(self, '_flat') or self._hyper.device != params[0].device:
+                self._init_state(params)
+            self._build_table(params)
+        self.sync_hyper()
+        from . import unet as U
+        ewc = self._importance is not None
+        # p, g read and p written; buf read and written; the anchor and the importance read
+        per_param = 12 + (8 if self._with_momentum else 0) + (4 if self._anchor is not None else 0) + (4 if ewc else 0)
+        U._hbm('sgd', per_param * self._numel, 'clamd_sgd_step', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None,
+               ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._ewcacc) if ewc else None,
+               ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
         return loss

@@ -3,6 +3,8 @@
 Same construction and ordering as the reference:
   model  = UNet(num_classes, in_dim=3, conv_dim=64)                       trainer.py:107 (num_classes is a knob here, Q8)
   optim  = Adam(model.parameters(), lr, betas=[beta1, beta2])             trainer.py:108-110 -> FusedAdam
+           (cfg.optimizer='sgd', build-defined: FusedSGD with cfg.momentum, nesterov, weight_decay; cfg.lr_schedule='iteration': the
+            polynomial decay stepped after every optimiser step over cfg.max_iters instead of once per epoch)
   sched  = LambdaLR(optim, lambda n: (1 - n/n_iters) ** lr_exp)           trainer.py:111-112
   c_loss = CrossEntropyLoss()                                             trainer.py:113
   per epoch: scheduler.step() FIRST (trainer.py:147), then for each batch
@@ -31,7 +33,7 @@ from torch.optim.lr_scheduler import LambdaLR
 
 from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
-from .optim import FusedAdam
+from .optim import FusedAdam, FusedSGD
 from .consolidate import Consolidation
 from .pseudo import PseudoLabeler
 from .pod import LocalPODLoss
@@ -45,9 +47,49 @@ def default_config(**kw):
     """Defaults of main.py:64-105 for the flags the hot path reads."""
     cfg = dict(n_iters=10000, train_batch_size=2, lr=1e-4, lr_exp=0.9, beta1=0.5, beta2=0.99, h_image_size=512,
                w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False,
-               augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0)
+               augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0,
+               optimizer='adam', momentum=0.9, nesterov=True, weight_decay=1e-4, decay_norm_and_bias=True, lr_schedule='epoch',
+               max_iters=None)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
+
+
+def make_scheduler(optim, cfg, iters_per_epoch=None):
+    """The learning-rate schedule of cfg.lr_schedule on any optimiser.  'epoch' (the default, the reference's trainer.py:111-112):
+    (1 - n/n_iters) ** lr_exp, stepped once at the start of every epoch.  'iteration' (build-defined, what the class-incremental
+    segmentation papers train with): max(0, 1 - n/max_iters) ** lr_exp, stepped after every optimiser step; cfg.max_iters None means
+    n_iters * iters_per_epoch."""
+    kind = getattr(cfg, 'lr_schedule', 'epoch')
+    if kind == 'epoch':
+        return LambdaLR(optim, lr_lambda=lambda n: (1 - n / cfg.n_iters) ** cfg.lr_exp)
+    if kind != 'iteration':
+        raise ValueError(f"lr_schedule must be 'epoch' or 'iteration', not {kind!r}")
+    max_iters = getattr(cfg, 'max_iters', None)
+    if max_iters is None:
+        if iters_per_epoch is None:
+            raise ValueError("lr_schedule='iteration' needs max_iters or a loader with a length")
+        max_iters = cfg.n_iters * iters_per_epoch
+    if not max_iters > 0:
+        raise ValueError('max_iters must be > 0')
+    return LambdaLR(optim, lr_lambda=lambda n: max(0.0, 1 - n / max_iters) ** cfg.lr_exp)
+
+
+def optimizer_kind(state_dict):
+    """'adam' or 'sgd' from the per-parameter state keys of an optimiser state dict; None for an empty state (either loads it)."""
+    for st in state_dict.get('state', {}).values():
+        if 'exp_avg' in st:
+            return 'adam'
+        if 'momentum_buffer' in st:
+            return 'sgd'
+    return None
+
+
+def check_optimizer_state(state_dict, kind):
+    """Raises ValueError when a checkpoint's optimiser state was written by the other optimiser than `kind` ('adam' or 'sgd')."""
+    found = optimizer_kind(state_dict)
+    if found is not None and found != kind:
+        raise ValueError(f"the checkpoint's optimizer_state was written by the {found!r} optimiser, this trainer runs {kind!r} "
+                         f"(cfg.optimizer): an optimiser state loads only into its own kind")
 
 
 class Trainer:
@@ -75,8 +117,25 @@ class Trainer:
                           compute_dtype=cfg.compute_dtype).to(self.device)
         if getattr(cfg, 'sync_bn', False) and syncbn.initialized():
             self.model = nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
-        self.optim = FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
-        self.scheduler = LambdaLR(self.optim, lr_lambda=lambda n: (1 - n / cfg.n_iters) ** cfg.lr_exp)
+        kind = getattr(cfg, 'optimizer', 'adam')
+        if kind == 'adam':
+            self.optim = FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
+        elif kind == 'sgd':
+            no_decay = []
+            if not getattr(cfg, 'decay_norm_and_bias', True):      # every BatchNorm parameter and every bias
+                for mod in self.model.modules():
+                    if isinstance(mod, nn.modules.batchnorm._BatchNorm):
+                        no_decay += list(mod.parameters(recurse=False))
+                    elif getattr(mod, 'bias', None) is not None and isinstance(mod.bias, nn.Parameter):
+                        no_decay.append(mod.bias)
+            self.optim = FusedSGD(self.model.parameters(), lr=cfg.lr, momentum=getattr(cfg, 'momentum', 0.9),
+                                  nesterov=getattr(cfg, 'nesterov', True), weight_decay=getattr(cfg, 'weight_decay', 1e-4),
+                                  no_decay=no_decay)
+        else:
+            raise ValueError(f"optimizer must be 'adam' or 'sgd', not {kind!r}")
+        self.per_iteration = getattr(cfg, 'lr_schedule', 'epoch') == 'iteration'
+        loader = self.train_data_loader
+        self.scheduler = make_scheduler(self.optim, cfg, len(loader) if self.per_iteration and hasattr(loader, '__len__') else None)
         self.c_loss = CrossEntropyLoss().to(self.device)
         self.augment = None
         if getattr(cfg, 'augment', False):       # each rank draws its own scales, crops and flips
@@ -328,6 +387,7 @@ class Trainer:
         ck = torch.load(path, map_location='cpu', weights_only=False)
         self.model.load_state_dict(ck['model_state'])
         self.start_epoch = ck['epoch']
+        check_optimizer_state(ck['optimizer_state'], getattr(self.cfg, 'optimizer', 'adam'))
         self.optim.load_state_dict(ck['optimizer_state'])
         self.scheduler.load_state_dict(ck['scheduler_state'])
         self.load_consolidation_state(ck.get('consolidation_state'))
@@ -392,6 +452,8 @@ class Trainer:
             loss = loss + pod(outputs, old, channels=self.pod_channels, merge_extra=True)
         loss.backward()
         self.optim.step()
+        if self.per_iteration:
+            self.scheduler.step()
         return outputs, loss
 
     @torch.no_grad()
@@ -413,9 +475,10 @@ class Trainer:
         return 100.0 * float(correct) / max(total, 1)
 
     def train_epoch(self, epoch):
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore')          # torch warns that scheduler.step() precedes optim.step(); the
-            self.scheduler.step()                    # reference does exactly that (trainer.py:147)
+        if not self.per_iteration:                   # lr_schedule='iteration': train_step steps it after every optim.step()
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')          # torch warns that scheduler.step() precedes optim.step(); the
+                self.scheduler.step()                    # reference does exactly that (trainer.py:147)
         conf = None
         losses = []
         for i, (images, masks) in enumerate(self.train_data_loader):

@@ -564,6 +564,24 @@ int clamd_adam_step_consolidated(const void* tensors_dev, const void* importance
  * importance; or, kept in the new one, decay 1, scale gamma, src = the previous importance).  decay and scale must be finite and >= 0.  Enqueue only: no allocation, no synchronisation, no atomics; element-wise,
  * so bit-reproducible.  12 B / element; dst and src need 4-byte alignment only (16-byte accesses from dst's first 16-byte boundary). */
 int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double scale, int power, void* stream);
+/* torch.optim.SGD.step (dampening 0, maximize off) over all parameters in one launch, with the two build-defined pulls of the Adam steps
+ * added to the gradient in the same place.  Per element, in this order:
+ *   g = grad * grad_scale;  g += (weight_decay * decay_mult) * p;
+ *   d = p - old;  g += 2 * l2_lambda * d;  g += ewc_lambda * omega * d;      (rows with an anchor; omega only with importance_dev)
+ *   buf = mu * buf + g;                                                       (rows with a momentum buffer)
+ *   u = nesterov ? g + mu * buf : (buf ? buf : g);  p -= lr * u.
+ * tensors_dev: clamd_sizeof_sgd_tensor()-byte rows {float* p; const float* g; float* buf (null: no momentum); const float* old (null: no
+ * anchor); long long n; float decay_mult; float pad}; chunks_dev: the (tensor, chunk) job list of clamd_adam_step, chunks of
+ * clamd_adam_chunk_elems() elements.  importance_dev (optional): device array of one `const float*` per row, omega >= 0 of the row's
+ * shape.  hyper_dev: device fp32[8] = lr, mu, weight_decay, nesterov (0 or 1), grad_scale, l2_lambda, ewc_lambda, 0 (device memory: a
+ * replayed graph sees a changed value).  ewc_accum_dev (required with importance_dev, refused without): 1 + nchunks floats, [0] = sum
+ * omega d^2 of this step; l2_accum_dev (optional): [0] = sum d^2; both reduced as in clamd_adam_step (fixed order, no float atomics,
+ * bit-reproducible).  20 B / parameter with momentum, 12 B without, +4 B with an anchor, +4 B with importance.  Every pointer needs
+ * 4-byte alignment only (16-byte accesses from p's first 16-byte boundary); nothing outside [0, n) of a row is touched.  Enqueue only:
+ * no allocation, no synchronisation, no process state. */
+int clamd_sizeof_sgd_tensor(void);
+int clamd_sgd_step(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks, const float* hyper_dev,
+                   float* ewc_accum_dev, float* l2_accum_dev, void* stream);
 /* argmax over classes + confusion matrix (trainer.py:183-188, metrics.py:32-38). */
 int clamd_argmax_confusion(const float* logits, const long long* labels, long long* pred, unsigned long long* conf,
                            int B, int K, int Kc, int H, int W, void* stream);
