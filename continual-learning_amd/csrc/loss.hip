@@ -558,6 +558,293 @@ __global__ void ce_finalize_kernel(const float* __restrict__ partial, int nblock
     }
 }
 
+// ---- cross-entropy + soft Dice (build-defined; the definitions are restated in include/clamd.h) --------------------------------------
+// Dice is not per-pixel: its gradient at a pixel depends on the per-class sums I = sum p_k [y = k], P = sum p_k, Y = sum [y = k] over the
+// pixel's group (the batch, or its image).  Three passes, every reduction in a fixed order:
+//   dice_sums_kernel   logits + labels once, ce4_kernel's access shape; a workgroup owns a chunk of ONE image and leaves one partial row
+//   dice_coef_kernel   one workgroup per group: the rows added in fp64, then N, D, |S|, the pair {c, a} per class and the group's loss term
+//   dice_grad_kernel   logits + labels again: softmax recomputed, d logits (NCHW and optionally NHWC), one CE partial pair per workgroup
+//   dice_finalize_kernel
+// A partial row, in 32-bit words: I[32], P[32] (fp32), Y[32] (unsigned), {bad, valid, -, -}.
+constexpr int DICE_KP = 32;
+constexpr int DICE_ROW_WORDS = 3 * DICE_KP + 4;
+constexpr int DICE_ROW_BAD = 3 * DICE_KP, DICE_ROW_VALID = 3 * DICE_KP + 1;
+constexpr int DICE_MAX_ROWS = CE_MAX_BLOCKS;                   // workgroups of the two per-pixel passes = partial rows = CE partial pairs
+
+// a[i] summed over the 64 lanes, N = 16, 32 or 64 values per lane: halving exchanges (lane bit 32 decides who keeps which half of the
+// values, then bit 16, ...) -- N - 1 shuffles instead of 6 N -- then a butterfly over the lane bits that are left.  Afterwards a[0] of lane l
+// is the total of value l >> (6 - log2 N).  A fixed tree: the same bits every run.
+template <int N, int H = N / 2, int BIT = 32>
+__device__ inline void dice_wave_reduce(float (&a)[N], int lane) {
+    if constexpr (H >= 1) {
+        const bool up = lane & BIT;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float keep = up ? a[j + H] : a[j], send = up ? a[j] : a[j + H];
+            a[j] = keep + __shfl_xor(send, BIT);
+        }
+        dice_wave_reduce<N, H / 2, BIT / 2>(a, lane);
+    } else if constexpr (BIT >= 1) {
+        a[0] += __shfl_xor(a[0], BIT);
+        dice_wave_reduce<N, 0, BIT / 2>(a, lane);
+    }
+}
+
+// KP2: KMAX rounded up to a power of two (the reduction's width); workgroup blockIdx.x = image * cpi + chunk
+template <int KMAX, int NPX>
+__global__ void __launch_bounds__(256) dice_sums_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                        float* __restrict__ rows, int cpi, int K, long long HW, long long ignore_index) {
+    PASS_PRIO();
+    constexpr int KP2 = KMAX == 24 ? 32 : KMAX, N = 2 * KP2, SHIFT = N == 64 ? 0 : N == 32 ? 1 : 2;
+    __shared__ float red[4][N];
+    __shared__ unsigned int cnt[DICE_KP + 1];                   // Y_k, then the bad labels: integer atomics in LDS (any order, same sum)
+    const int b = blockIdx.x / cpi, chunk = blockIdx.x - b * cpi;
+    if (threadIdx.x <= DICE_KP) cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long nq = HW / NPX;
+    const float* zb = logits + (long long)b * K * HW;
+    const long long* lb = labels + (long long)b * HW;
+    float acc[N];                                               // [0, KP2): I_k   [KP2, 2 KP2): P_k
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.f;
+    for (long long i = (long long)chunk * 256 + threadIdx.x; i < nq; i += (long long)cpi * 256) {
+        const long long p = NPX * i;
+        const float* z = zb + p;
+        float4 v[KMAX];
+        float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                v[k] = ce_ldpx<NPX>(z + k * HW);
+                CE_PX ce_at(mx, c) = fmaxf(ce_at(mx, c), ce_at(v[k], c));
+            }
+        long long lab[4];
+        ce_ld_labels<NPX>(lb, p, lab);
+        float4 se = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                CE_PX ce_at(v[k], c) = expf(ce_at(v[k], c) - ce_at(mx, c));
+                CE_PX ce_at(se, c) += ce_at(v[k], c);
+            }
+        float r[NPX];
+        CE_PX {
+            const bool ok = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K;
+            r[c] = ok ? 1.f / ce_at(se, c) : 0.f;                // an invalid pixel adds zeros
+            if (ok) atomicAdd(&cnt[(int)lab[c]], 1u);
+            else if (lab[c] != ignore_index) atomicAdd(&cnt[DICE_KP], 1u);
+        }
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) CE_PX {
+                const float pk = ce_at(v[k], c) * r[c];
+                acc[KP2 + k] += pk;
+                acc[k] += lab[c] == k ? pk : 0.f;
+            }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    dice_wave_reduce<N>(acc, lane);
+    if ((lane & ((1 << SHIFT) - 1)) == 0) red[wv][lane >> SHIFT] = acc[0];
+    __syncthreads();
+    float* row = rows + (long long)blockIdx.x * DICE_ROW_WORDS;
+    const int t = threadIdx.x;
+    if (t < N) {
+        const int k = t < KP2 ? t : t - KP2;
+        if (k < K) row[(t < KP2 ? 0 : DICE_KP) + k] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    } else if (t >= 64 && t < 64 + DICE_KP) {
+        reinterpret_cast<unsigned int*>(row)[t] = cnt[t - 64];          // word 64 + k: Y_k
+    } else if (t == 128) {
+        unsigned int nv = 0;
+        for (int k = 0; k < DICE_KP; ++k) nv += cnt[k];
+        reinterpret_cast<unsigned int*>(row)[DICE_ROW_BAD] = cnt[DICE_KP];
+        reinterpret_cast<unsigned int*>(row)[DICE_ROW_VALID] = nv;
+    }
+}
+
+// One workgroup of 512 threads per group g: rows [g * rows_per_group, (g + 1) * rows_per_group).  Thread (slice s = t / 32, class k = t % 32)
+// adds rows s, s + 16, ... in fp64, eight rows' loads in flight per trip; the 16 slices are added in order.  coef[g][k] = {c_gk, a_gk} (zero
+// outside S_g), gterm[g] = the group's loss term 1 - mean dice (0 for an empty S_g).  Workgroup 0 also totals {valid, bad} over ALL rows into
+// totals[0 .. 1].  (Slices, loads in flight and the times they gave: DESIGN.md, the kernel table's Dice row.)
+constexpr int DICE_SLICES = 16;
+__global__ void __launch_bounds__(32 * DICE_SLICES) dice_coef_kernel(const float* __restrict__ rows, int nrows, int rows_per_group, int G, int K,
+                                                        double w_dice, double smooth, int first_class, int present_only,
+                                                        float* __restrict__ coef, double* __restrict__ gterm, unsigned int* __restrict__ totals) {
+    SIDE_PRIO();
+    __shared__ double sI[DICE_SLICES][DICE_KP], sP[DICE_SLICES][DICE_KP], sdice[DICE_KP];
+    __shared__ unsigned long long sY[DICE_SLICES][DICE_KP];
+    __shared__ unsigned int wtot[2][DICE_SLICES / 2];
+    const int t = threadIdx.x, k = t & 31, s = t >> 5, g = blockIdx.x;
+    // eight rows per trip, every load of a trip issued before its first add (a row past the end is read from row r and adds zeros)
+    double aI = 0.0, aP = 0.0;
+    unsigned long long aY = 0;
+    const int r1 = (g + 1) * rows_per_group;
+    if (k < K)
+        for (int r = g * rows_per_group + s; r < r1; r += 8 * DICE_SLICES) {
+            float vi[8], vp[8];
+            unsigned int vy[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int rr = r + j * DICE_SLICES;
+                const float* row = rows + (long long)(rr < r1 ? rr : r) * DICE_ROW_WORDS;
+                vi[j] = row[k]; vp[j] = row[DICE_KP + k]; vy[j] = reinterpret_cast<const unsigned int*>(row)[2 * DICE_KP + k];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const bool in = r + j * DICE_SLICES < r1;
+                aI += in ? (double)vi[j] : 0.0; aP += in ? (double)vp[j] : 0.0; aY += in ? vy[j] : 0u;
+            }
+        }
+    if (g == 0) {                                                // the label totals: per wave by shuffles, the waves added below
+        unsigned int nv = 0, nb = 0;
+        for (int r = t; r < nrows; r += 32 * DICE_SLICES) {
+            const unsigned int* row = reinterpret_cast<const unsigned int*>(rows) + (long long)r * DICE_ROW_WORDS;
+            nb += row[DICE_ROW_BAD]; nv += row[DICE_ROW_VALID];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o); nb += __shfl_xor(nb, o); }
+        if ((t & 63) == 0) { wtot[0][t >> 6] = nv; wtot[1][t >> 6] = nb; }
+    }
+    sI[s][k] = aI; sP[s][k] = aP; sY[s][k] = aY;
+    __syncthreads();
+    if (g == 0 && t < 2) {
+        unsigned int n = 0;
+        for (int j = 0; j < DICE_SLICES / 2; ++j) n += wtot[t][j];
+        totals[t] = n;
+    }
+    int nS = 0;
+    if (t < DICE_KP) {                                           // the first half of wave 0: class k = t
+        double I = 0.0, P = 0.0;
+        unsigned long long Y = 0;
+        for (int j = 0; j < DICE_SLICES; ++j) { I += sI[j][k]; P += sP[j][k]; Y += sY[j][k]; }
+        const bool in_set = k >= first_class && k < K && (!present_only || Y > 0);
+        nS = __popcll(__ballot(in_set));
+        const double u = nS ? w_dice / ((double)G * (double)nS) : 0.0;
+        const double Nk = 2.0 * I + smooth, Dk = P + (double)Y + smooth;
+        const bool flat = !in_set || Dk == 0.0;                 // D == 0: dice = 1 and no gradient
+        sdice[k] = in_set ? (Dk == 0.0 ? 1.0 : Nk / Dk) : 0.0;
+        coef[((long long)g * DICE_KP + k) * 2 + 0] = flat ? 0.f : (float)(u * Nk / (Dk * Dk));
+        coef[((long long)g * DICE_KP + k) * 2 + 1] = flat ? 0.f : (float)(-2.0 * u / Dk);
+    }
+    __syncthreads();
+    if (t == 0) {
+        double sum = 0.0;
+        for (int j = 0; j < DICE_KP; ++j) sum += sdice[j];
+        gterm[g] = nS ? 1.0 - sum / (double)nS : 0.0;
+    }
+}
+
+// ce4_kernel's shape and arithmetic for the cross-entropy part (gce = grad_scale * w_ce / max(N, 1)); the Dice part from the group's table:
+// g_k = c_k + [y = k] a_y, dot = sum_k p_k g_k = (sum_k e_k c_k) / se + p_y a_y,
+//   d logits_k = e_k * (gce / se + (grad_scale / se) * (g_k - dot)) - [y = k] gce          on a valid pixel, 0 elsewhere.
+// c_k is workgroup-uniform (a workgroup stays inside one image): scalar registers; a_y is looked up by the label: LDS.
+template <int KMAX, int NPX, typename NT>
+__global__ void __launch_bounds__(256) dice_grad_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                        const float* __restrict__ coef, const unsigned int* __restrict__ totals,
+                                                        float* __restrict__ dlogits, float* __restrict__ partial, int cpi, int per_image,
+                                                        int K, long long HW, long long ignore_index, float grad_scale, float w_ce,
+                                                        NT* dl_nhwc, int dl_ldc) {
+    PASS_PRIO();
+    __shared__ float red[4];
+    __shared__ float ta[DICE_KP];
+    constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;
+    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
+    const int b = blockIdx.x / cpi, chunk = blockIdx.x - b * cpi;
+    const float* cf = coef + (long long)(per_image ? b : 0) * (2 * DICE_KP);
+    if (threadIdx.x < DICE_KP) ta[threadIdx.x] = cf[2 * threadIdx.x + 1];
+    float ck[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) ck[k] = cf[2 * k];
+    __syncthreads();
+    const float gce = grad_scale * w_ce / (float)max(totals[0], 1u);
+    const long long nq = HW / NPX, q0 = (long long)b * nq;       // quads (pixels) of an image; the image's first
+    float ce_sum = 0.f;
+    for (long long lbase = (long long)chunk * 256; lbase < nq; lbase += (long long)cpi * 256) {
+        const long long i = lbase + threadIdx.x;
+        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange has barriers)
+        if (!XCH && !live) continue;
+        const long long p = NPX * (live ? i : nq - 1), pix = (long long)b * HW + p;
+        const float* z = logits + (long long)b * K * HW + p;
+        float4 v[KMAX];
+        float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                v[k] = ce_ldpx<NPX>(z + k * HW);
+                CE_PX ce_at(mx, c) = fmaxf(ce_at(mx, c), ce_at(v[k], c));
+            }
+        long long lab[4];
+        ce_ld_labels<NPX>(labels, pix, lab);
+        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), picked = se, ey = se, dc = se;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                CE_PX ce_at(picked, c) = lab[c] == k ? ce_at(v[k], c) : ce_at(picked, c);
+                CE_PX ce_at(v[k], c) = expf(ce_at(v[k], c) - ce_at(mx, c));
+                CE_PX ce_at(se, c) += ce_at(v[k], c);
+                CE_PX ce_at(ey, c) = lab[c] == k ? ce_at(v[k], c) : ce_at(ey, c);
+                CE_PX ce_at(dc, c) = fmaf(ce_at(v[k], c), ck[k], ce_at(dc, c));
+            }
+        float rce[NPX], rd[NPX], h[NPX], ay[NPX], dot[NPX];
+        CE_PX {
+            const bool ok = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K;
+            if (live && ok) ce_sum += ce_at(mx, c) + logf(ce_at(se, c)) - ce_at(picked, c);
+            const float rinv = 1.f / ce_at(se, c);
+            ay[c] = ta[ok ? (int)lab[c] : 0];
+            ay[c] = ok ? ay[c] : 0.f;
+            dot[c] = fmaf(ce_at(ey, c) * rinv, ay[c], ce_at(dc, c) * rinv);
+            rce[c] = ok ? gce * rinv : 0.f;
+            rd[c] = ok ? grad_scale * rinv : 0.f;
+            h[c] = ok ? gce : 0.f;
+        }
+        float* d = dlogits + (long long)b * K * HW + p;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+                CE_PX {
+                    const bool hit = lab[c] == k;
+                    const float gk = ck[k] + (hit ? ay[c] : 0.f);
+                    ce_at(g, c) = ce_at(v[k], c) * fmaf(rd[c], gk - dot[c], rce[c]) - (hit ? h[c] : 0.f);
+                }
+                if (live) {
+                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
+                    else d[k * HW] = g.x;
+                }
+                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
+            }
+        // the NHWC copy: `base` and the bound are this image's -- the exchange must not reach into the next image from the tail's dead lanes
+        if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, q0 + lbase, q0 + nq, xbuf);
+        else ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
+    }
+    ce_sum = wave_sum(ce_sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ce_sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x + 0] = red[0] + red[1] + red[2] + red[3];
+        partial[2 * blockIdx.x + 1] = 0.f;
+    }
+}
+
+// loss3 = {ce + dice, ce = w_ce * mean CE, dice = w_dice * mean_g gterm}: the CE partials and the group terms added in fp64 in a fixed order
+__global__ void __launch_bounds__(256) dice_finalize_kernel(const float* __restrict__ partial, int nblocks, const unsigned int* __restrict__ totals,
+                                                            const double* __restrict__ gterm, int G, double w_ce, double w_dice, float* out3) {
+    __shared__ double red[2][256];
+    double a = 0, b = 0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) a += partial[2 * i];
+    for (int i = threadIdx.x; i < G; i += 256) b += gterm[i];
+    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float ce = (float)(w_ce * (red[0][0] / (double)max(totals[0], 1u)));
+        const float dice = (float)(w_dice * (red[1][0] / (double)G));
+        out3[0] = ce + dice; out3[1] = ce; out3[2] = dice;
+    }
+}
+
 }  // namespace clamd
 
 using namespace clamd;
@@ -644,7 +931,74 @@ static void ce_count(const long long* labels, long long npix, long long ignore_i
     hipLaunchKernelGGL(count_valid_rows_kernel, dim3(CE_COUNT_BLOCKS), dim3(256), 0, s, labels, npix, ignore_index, K, rows);
 }
 
+// The grid of the two per-pixel Dice passes and the pieces of their workspace behind the CE workspace.  A workgroup owns a chunk of one image:
+// cpi chunks per image, as many as 256-lane trips cover it, capped so that B * cpi <= DICE_MAX_ROWS (a capped workgroup loops).  The
+// offsets are those of the one-pixel form (the larger row count), so the layout does not depend on the alignment of a call's tensors.
+struct DicePlan {
+    int cpi, nrows, G;       // chunks per image, partial rows = workgroups, groups
+    long long rows, coef, gterm, words;      // offsets and size in 32-bit words
+};
+static bool dice_plan(DicePlan* d, int B, int K, int H, int W, int per_image, bool four) {
+    if (B <= 0 || H <= 0 || W <= 0 || K < 1 || K > 32 || B > DICE_MAX_ROWS) return false;
+    const long long HW = (long long)H * W, cap = DICE_MAX_ROWS / B;
+    const long long want1 = (HW + 255) / 256, want = ((four ? HW / 4 : HW) + 255) / 256;
+    d->cpi = (int)(want < cap ? want : cap);
+    d->nrows = B * d->cpi;
+    d->G = per_image ? B : 1;
+    d->rows = CE_WS_WORDS;
+    d->coef = d->rows + (long long)B * (want1 < cap ? want1 : cap) * DICE_ROW_WORDS;
+    d->gterm = d->coef + (long long)d->G * 2 * DICE_KP;
+    d->words = d->gterm + 2LL * d->G;
+    return true;
+}
+
 extern "C" {
+
+size_t clamd_ce_dice_workspace_bytes(int B, int K, int H, int W, int per_image) {
+    DicePlan d;
+    return dice_plan(&d, B, K, H, W, per_image, false) ? (size_t)d.words * 4 : 0;
+}
+
+int clamd_ce_dice_fwd_bwd(const float* logits, const long long* labels, float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype,
+                          float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
+                          double w_ce, double w_dice, double smooth, int first_class, int present_only, int per_image,
+                          double grad_scale, void* stream) {
+    const char* who = "ce_dice";
+    if (first_class != 0 && first_class != 1) return ce_fail(who, "first_class must be 0 or 1");
+    if (!(w_ce >= 0.0) || !(w_dice >= 0.0) || !(smooth >= 0.0) || !isfinite(w_ce) || !isfinite(w_dice) || !isfinite(smooth))
+        return ce_fail(who, "w_ce, w_dice and smooth must be finite and >= 0");
+    if (workspace && ws_bytes < clamd_ce_workspace_bytes()) return ce_fail(who, "workspace too small (clamd_ce_dice_workspace_bytes)");
+    CePlan p;
+    if (int e = ce_plan(&p, who, true, logits, labels, nullptr, dlogits, dl_nhwc, dl_ldc, dl_dtype, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    DicePlan d;
+    if (!dice_plan(&d, B, K, H, W, per_image, p.four)) return ce_fail(who, "more than 2048 images: every image needs a partial row of its own and the coefficient pass adds at most 2048");
+    if (ws_bytes < (size_t)d.words * 4) return ce_fail(who, "workspace too small (clamd_ce_dice_workspace_bytes)");
+    if ((size_t)workspace % 16) return ce_fail(who, "workspace must be 16-byte aligned");
+    float* ws = (float*)workspace;
+    float *rows = ws + d.rows, *coef = ws + d.coef;
+    double* gterm = (double*)(ws + d.gterm);
+    const float gs = (float)grad_scale;
+    auto sums = [&](auto kmax, auto npx) {
+        hipLaunchKernelGGL((dice_sums_kernel<decltype(kmax)::value, decltype(npx)::value>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels, rows,
+                           d.cpi, K, p.HW, ignore_index);
+    };
+    if (p.four) ce_for_kmax(K, [&](auto kmax) { sums(kmax, ce_int<4>{}); });
+    else sums(ce_int<32>{}, ce_int<1>{});
+    hipLaunchKernelGGL(dice_coef_kernel, dim3(d.G), dim3(32 * DICE_SLICES), 0, p.s, rows, d.nrows, per_image ? d.cpi : d.nrows, d.G, K, w_dice, smooth,
+                       first_class, present_only ? 1 : 0, coef, gterm, p.totals);
+    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
+        using NT = typename decltype(nt)::type;
+        auto grad = [&](auto kmax, auto npx) {
+            hipLaunchKernelGGL((dice_grad_kernel<decltype(kmax)::value, decltype(npx)::value, NT>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels,
+                               coef, p.totals, dlogits, p.partial, d.cpi, per_image ? 1 : 0, K, p.HW, ignore_index, gs, (float)w_ce, (NT*)dl_nhwc,
+                               dl_ldc);
+        };
+        if (p.four) ce_for_kmax(K, [&](auto kmax) { grad(kmax, ce_int<4>{}); });
+        else grad(ce_int<32>{}, ce_int<1>{});
+    });
+    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, p.s, p.partial, d.nrows, p.totals, gterm, d.G, w_ce, w_dice, loss3);
+    return clamd_check_launch("ce_dice_fwd_bwd");
+}
 
 size_t clamd_ce_workspace_bytes(void) { return (size_t)CE_WS_WORDS * 4; }
 size_t clamd_ce_bad_label_count_offset(void) { return (size_t)(CE_WS_TOTALS + 1) * 4; }

@@ -13,6 +13,9 @@ cross-entropy and unbiased distillation of Cermelli et al. (CVPR 2020) as includ
 
 ``CrossEntropyLoss()(logits, labels, image_weight)`` is the pseudo-label step's loss (build-defined, pseudo.py): every pixel's term times its
 image's weight, on ``clamd_ce_fwd_bwd_weighted``; without the weight nothing changes.
+
+``DiceCrossEntropyLoss`` is cross-entropy plus soft Dice (build-defined, the compound loss of nnU-Net / MONAI's DiceCELoss), on
+``clamd_ce_dice_fwd_bwd``: a sums pass, a coefficient pass and a gradient pass, every reduction in a fixed order.
 """
 import os
 
@@ -28,10 +31,11 @@ from ._lib import call, ptr
 HANDOVER = os.environ.get('CLAMD_LOSS_HANDOVER', '1') != '0'
 
 
-def _forward(ctx, holder, logits, labels, ignore_index, others, middle):
+def _forward(ctx, holder, logits, labels, ignore_index, others, middle, ws_bytes=None):
     """What every loss forward shares: the checks, the allocation, and the bookkeeping behind the kernels.  `others`: the further tensors
     the caller hands to the library.  ``middle(counted, logits, labels, dl, out3, ws, wsb)`` launches the loss: its own call on these
-    buffers, or ``counted(entry, lead, px_bytes)`` -- the training-step form."""
+    buffers, or ``counted(entry, lead, px_bytes)`` -- the training-step form.  ``ws_bytes(lib, B, K, H, W)``: the size of a workspace
+    larger than the cross-entropy one (which it starts with)."""
     if not all(t.is_cuda for t in (logits, labels) + tuple(others) if t is not None):
         raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
     lib = _lib.load()
@@ -45,23 +49,25 @@ def _forward(ctx, holder, logits, labels, ignore_index, others, middle):
         raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
     dl = torch.empty_like(logits)
     out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
-    wsb = lib.clamd_ce_workspace_bytes()
+    wsb = lib.clamd_ce_workspace_bytes() if ws_bytes is None else ws_bytes(lib, B, K, H, W)
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
     ctx.sink = None
 
-    def counted(entry, lead=(), px_bytes=0):
+    def counted(entry, lead=(), px_bytes=0, count=True, tail=()):
         """clamd_ce_count, then `entry`(logits, labels, *lead, d logits, its NHWC copy, ...): the count of valid pixels as partial rows (no
         memset, no atomics), and, when the logits come from this package's UNet, d logits written a second time in the layout (and dtype) its
         1x1 head's data gradient reads -- the backward pass then starts without a conversion pass (unet._Engine.backward).
-        px_bytes: what the entry reads per pixel beyond the logits and the label."""
+        px_bytes: what the entry reads per pixel beyond the logits and the label.  count=False: the entry counts for itself; tail: its
+        arguments between ignore_index and grad_scale."""
         from . import unet as U
         # (algorithmic bytes, SURVEY 8d: logits read + d logits written + the label; the counting pass reads the labels a second time)
-        U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
+        if count:
+            U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
         eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
         nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
         U._hbm('loss', B * H * W * (2 * K * 4 + px_bytes + 8 + (ldc * eng.esize if eng is not None else 0)),
                entry, ptr(logits), ptr(labels), *lead, ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb, B, K, H, W,
-               int(ignore_index), 1.0, _lib.stream_ptr())
+               int(ignore_index), *tail, 1.0, _lib.stream_ptr())
         if eng is not None:
             ctx.sink = eng
             # a STRONG reference: while the engine waits for this gradient its storage cannot be freed and handed to another
@@ -194,3 +200,54 @@ class UnbiasedDistillationCrossEntropy(nn.Module):
 
     def forward(self, logits, labels, old_logits=None):
         return _UCEFn.apply(logits, labels, None if old_logits is None else old_logits.detach(), self.c_old, self.lam, self.ignore_index, self)
+
+
+class _DiceCEFn(torch.autograd.Function):
+    """clamd_ce_dice_fwd_bwd (it counts the valid pixels itself); the hand-over of d logits to the UNet's backward pass and the backward as
+    _CEFn."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, w_ce, w_dice, smooth, first_class, present_only, per_image, ignore_index, holder):
+        def middle(counted, logits, *_):
+            K = logits.shape[1]
+            # algorithmic bytes: the logits and the label a second time on top of the plain loss's
+            counted('clamd_ce_dice_fwd_bwd', px_bytes=4 * K + 8, count=False,
+                    tail=(float(w_ce), float(w_dice), float(smooth), int(first_class), int(present_only), int(per_image)))
+
+        def ws_bytes(lib, B, K, H, W):
+            n = lib.clamd_ce_dice_workspace_bytes(B, K, H, W, int(per_image))
+            if n == 0:
+                raise ValueError(f'DiceCrossEntropyLoss: logits {(B, K, H, W)}: needs 1 <= K <= 32 classes and at most 2048 images')
+            return n
+        return _forward(ctx, holder, logits, labels, ignore_index, (), middle, ws_bytes)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _CEFn.backward(ctx, g) + (None, None)
+
+
+class DiceCrossEntropyLoss(nn.Module):
+    """ce_weight * CE + dice_weight * soft Dice (build-defined; the definitions are in include/clamd.h): the compound loss of nnU-Net and of
+    MONAI's DiceCELoss on ``clamd_ce_dice_fwd_bwd``.  The Dice term is computed from softmax probabilities over the valid pixels (label not
+    ``ignore_index`` and inside [0, K)), per class over the whole batch or (``per_image``) over each image, averaged over the classes that
+    take part: all of them, without the background (``include_background=False``), only those present in the group's labels
+    (``present_only``).  After a forward: ``parts`` = device {total, ce_weight * ce, dice_weight * dice}, ``bad_labels`` as on
+    CrossEntropyLoss.  Data parallelism: each rank's Dice sums cover its own batch (like non-synchronised BatchNorm); no collective is added."""
+
+    def __init__(self, ce_weight=1.0, dice_weight=1.0, smooth=1e-5, include_background=True, present_only=True, per_image=False,
+                 ignore_index=-100):
+        super().__init__()
+        for name, v in (('ce_weight', ce_weight), ('dice_weight', dice_weight), ('smooth', smooth)):
+            if not (float(v) >= 0.0 and float(v) != float('inf')):
+                raise ValueError(f'DiceCrossEntropyLoss: {name} must be finite and >= 0, got {v!r}')
+        if float(ce_weight) == 0.0 and float(dice_weight) == 0.0:
+            raise ValueError('DiceCrossEntropyLoss: ce_weight and dice_weight are both zero')
+        self.ce_weight, self.dice_weight, self.smooth = float(ce_weight), float(dice_weight), float(smooth)
+        self.include_background, self.present_only, self.per_image = bool(include_background), bool(present_only), bool(per_image)
+        self.ignore_index = ignore_index
+        self.bad_labels = None
+        self.parts = None
+
+    def forward(self, logits, labels):
+        return _DiceCEFn.apply(logits, labels, self.ce_weight, self.dice_weight, self.smooth, 0 if self.include_background else 1,
+                               self.present_only, self.per_image, self.ignore_index, self)

@@ -21,7 +21,11 @@ confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`
 pod.py); ``begin_task2(replay=M, replay_batch=R)`` keeps M exemplars of the finished task in an on-device memory and mixes R of them into
 every batch (build-defined, replay.py).  ``cfg.augment=True`` (with augment_scale, augment_flip, augment_seed) rescales, crops or pads and
 flips every training batch -- the replayed rows included -- in one launch before the forward pass (build-defined, augment.py); off by
-default, and then nothing on the step's path changes.
+default, and then nothing on the step's path changes.  ``cfg.loss='ce_dice'`` (build-defined, loss.DiceCrossEntropyLoss with dice_weight,
+dice_smooth, dice_include_background, dice_present_only, dice_per_image) makes the step's criterion cross-entropy + soft Dice; the default
+'ce' changes nothing.  ``begin_task2(pod_lambda=...)`` adds on top of it; not with distill_lambda > 0, unbiased=True or pseudo_adaptive=True
+(those criteria have no Dice term, this one no per-image weight).  ``estimate_importance`` keeps differentiating the plain log-likelihood.
+Data parallel: each rank's Dice sums cover its own batch, like non-synchronised BatchNorm; no collective is added.
 """
 import os
 import warnings
@@ -31,7 +35,7 @@ import torch
 import torch.nn as nn
 from torch.optim.lr_scheduler import LambdaLR
 
-from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
+from .loss import CrossEntropyLoss, DiceCrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam, FusedSGD
 from .consolidate import Consolidation
@@ -49,7 +53,8 @@ def default_config(**kw):
                w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False,
                augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0,
                optimizer='adam', momentum=0.9, nesterov=True, weight_decay=1e-4, decay_norm_and_bias=True, lr_schedule='epoch',
-               max_iters=None)
+               max_iters=None,
+               loss='ce', dice_weight=1.0, dice_smooth=1e-5, dice_include_background=True, dice_present_only=True, dice_per_image=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -137,6 +142,14 @@ class Trainer:
         loader = self.train_data_loader
         self.scheduler = make_scheduler(self.optim, cfg, len(loader) if self.per_iteration and hasattr(loader, '__len__') else None)
         self.c_loss = CrossEntropyLoss().to(self.device)
+        self.likelihood_loss = self.c_loss       # estimate_importance differentiates the plain log-likelihood whatever the step's criterion
+        kind = getattr(cfg, 'loss', 'ce')
+        if kind == 'ce_dice':
+            self.c_loss = DiceCrossEntropyLoss(1.0, getattr(cfg, 'dice_weight', 1.0), getattr(cfg, 'dice_smooth', 1e-5),
+                                               getattr(cfg, 'dice_include_background', True), getattr(cfg, 'dice_present_only', True),
+                                               getattr(cfg, 'dice_per_image', False)).to(self.device)
+        elif kind != 'ce':
+            raise ValueError(f"loss must be 'ce' or 'ce_dice', not {kind!r}")
         self.augment = None
         if getattr(cfg, 'augment', False):       # each rank draws its own scales, crops and flips
             rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
@@ -164,7 +177,7 @@ class Trainer:
                     break
                 outputs = model(images.to(self.device, non_blocking=True))
                 self.reset_grad()
-                self.c_loss(outputs, masks.to(self.device, non_blocking=True)).backward()
+                self.likelihood_loss(outputs, masks.to(self.device, non_blocking=True)).backward()
                 cons.accumulate(params)
             cons.finish()
         finally:
@@ -230,6 +243,16 @@ class Trainer:
         if pseudo_label and pseudo_adaptive and distill_lambda > 0:
             raise ValueError('pseudo_adaptive=True with distill_lambda > 0: DistillationCrossEntropy has no per-image weight '
                              '(use distill_lambda=0, or pseudo_adaptive=False)')
+        if getattr(getattr(self, 'cfg', None), 'loss', 'ce') == 'ce_dice':
+            if unbiased:
+                raise ValueError("loss='ce_dice' with unbiased=True: the Dice term is not defined inside the unbiased criterion "
+                                 "(labels below c_old mean 'background or any old class' there)")
+            if distill_lambda > 0:
+                raise ValueError("loss='ce_dice' with distill_lambda > 0: DistillationCrossEntropy has no Dice term "
+                                 "(use distill_lambda=0, with pod_lambda > 0 for distillation)")
+            if pseudo_label and pseudo_adaptive:
+                raise ValueError("loss='ce_dice' with pseudo_adaptive=True: DiceCrossEntropyLoss has no per-image weight "
+                                 "(use pseudo_adaptive=False)")
         if replay > 0:
             self._fill_replay(c_old, replay, self.train_data_loader if replay_loader is None else replay_loader, replay_storage, replay_flip,
                               replay_min_pixels, replay_seed)

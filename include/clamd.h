@@ -404,6 +404,40 @@ int clamd_ce_fwd_bwd_counted(const float* logits, const long long* labels, float
 int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, const float* old_logits, int K_old_total, int c_old, double lam,
                               float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes,
                               int B, int K, int H, int W, long long ignore_index, double grad_scale, void* stream);
+/* ---- cross-entropy + soft Dice (loss.hip) ---------------------------------------------------------------------
+ * Build-defined, parity unpinned (the reference trains with plain cross-entropy): the compound loss of nnU-Net and of MONAI's DiceCELoss.
+ * Logits z fp32 NCHW [B,K,H,W], labels y int64 [B,H,W], 1 <= K <= 32.
+ *   valid pixel   y != ignore_index and y in [0, K); invalid pixels contribute to nothing; a label that is neither ignore_index nor a
+ *                 class is counted as a bad label, as by the clamd_ce_* entry points
+ *   p             softmax(z) over the K classes of a pixel, in fp32, relative to the pixel's maximum
+ *   group         per_image = 0: all images are one group (batch Dice, G = 1); per_image = 1: each image is a group (G = B)
+ *   sums          per group g and class k over the valid pixels of g:  I = sum p_k [y = k],  P = sum p_k,  Y = sum [y = k] (an integer)
+ *   class set     S_g = { k in [first_class, K) : not present_only or Y_gk > 0 };  first_class in {0, 1} (1 leaves the background out)
+ *   Dice          N_gk = 2 I_gk + smooth,  D_gk = P_gk + Y_gk + smooth,  dice_gk = N_gk / D_gk  (D_gk == 0: dice_gk = 1, no gradient)
+ *   L_dice        (1 / G) sum_g [ 1 - (1 / |S_g|) sum_{k in S_g} dice_gk ];  a group with empty S_g contributes 0 and no gradient
+ *   CE            clamd_ce_fwd_bwd_counted's: the mean of -log p_y over the N valid pixels of the batch
+ *   total         w_ce * CE + w_dice * L_dice;  loss3 = {total, w_ce * CE, w_dice * L_dice}, total the fp32 sum of the other two
+ *   gradient      on a valid pixel of group g, with u = w_dice / (G |S_g|), for k in S_g:  c_gk = u N_gk / D_gk^2,  a_gk = -2 u / D_gk,
+ *                 g_k = c_gk + [y = k] a_gk  (g_k = 0 outside S_g):
+ *                 d total / d z_j = grad_scale * [ w_ce (p_j - [y = j]) / max(N, 1) + p_j (g_j - sum_k p_k g_k) ];   exactly 0 on invalid pixels
+ * Four launches: a sums pass (logits and labels once; one partial row {I, P, Y, counts} per workgroup, plain stores, a workgroup inside one
+ * image), a coefficient pass (the rows of each group added in a fixed order in fp64; N, D, |S|, {c, a} and the loss term in fp64; the table
+ * [G][32][2] in fp32; the valid / bad totals, so no clamd_ce_count in front), a gradient pass (softmax recomputed; d logits in NCHW and,
+ * with dl_nhwc, a second time as [B,H,W,dl_ldc] of dl_dtype, channels K .. dl_ldc-1 zero: clamd_ce_fwd_bwd_counted's contract byte for
+ * byte) and a finalize.  Four pixels per thread with 16-byte logit and 32-byte label accesses when H * W % 4 == 0 and logits / dlogits are
+ * 16-byte, labels 32-byte aligned; any other size or alignment takes a one-pixel variant of the same arithmetic inside the same entry
+ * point.  Enqueue only: no allocation, no synchronisation, no memset, no float atomics (bit-reproducible), graph-capturable.
+ * Workspace: clamd_ce_dice_workspace_bytes(B, K, H, W, per_image) bytes (0 for an invalid shape), 16-byte aligned; its first
+ * clamd_ce_workspace_bytes() bytes are laid out as the CE workspace (clamd_ce_bad_label_count_offset() finds the bad-label counter, the
+ * valid count sits in the word before it); the contents are otherwise undefined before and after.
+ * Rejected before any launch: K outside [1, 32]; first_class outside {0, 1}; negative or non-finite w_ce, w_dice or smooth; dl_nhwc with
+ * dl_ldc < 32; a workspace that is too small or unaligned; null logits / labels / dlogits / loss3 / workspace; B > 2048 (every image has a
+ * partial row of its own and the coefficient pass adds at most 2048 rows; larger images share the 2048 rows, their workgroups loop). */
+size_t clamd_ce_dice_workspace_bytes(int B, int K, int H, int W, int per_image);
+int clamd_ce_dice_fwd_bwd(const float* logits, const long long* labels, float* dlogits, void* dl_nhwc, int dl_ldc, int dl_dtype,
+                          float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
+                          double w_ce, double w_dice, double smooth, int first_class, int present_only, int per_image,
+                          double grad_scale, void* stream);
 /* ---- pseudo-labelling of the old classes (pseudo.hip; its loss clamd_ce_fwd_bwd_weighted: loss.hip) -----------
  * Build-defined, parity unpinned (the reference has no continual-learning code): the classification half of PLOP (Douillard et al.,
  * CVPR 2021, section 3.2).  In a task-2 batch every pixel of an old class is labelled 0; the frozen old model labels the background
