@@ -1,6 +1,7 @@
-"""Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py, test_conv3_grid_gpu.py): poisoned
-buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit expectations, the two-runs check, the
-storage rounding of the three dtypes and the per-element comparison against a float64 reference."""
+"""Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py, test_conv3_grid_gpu.py,
+test_wino_wgrad_grid_gpu.py): poisoned buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit
+expectations, the two-runs check, the storage rounding of the three dtypes, the per-element comparison against a float64 reference and the
+float64 weight-gradient reference (a sum over pixels per tap)."""
 import math
 
 import numpy as np
@@ -159,6 +160,16 @@ def _expect_rows(what, rows, exp):
     raise AssertionError(f'{what}: {int((d != 0).sum())} elements differ; worst at {idx}: got {float(got[idx])!r}, expected {float(exp[idx])!r}')
 
 
+def _expect_vals(what, got, exp):
+    """`got` equals the float64 `exp` element for element as NUMBERS (a zero's sign is free, NaN never passes); the worst element on failure."""
+    got = got.reshape(exp.shape).double()
+    if torch.equal(got, exp):
+        return
+    d = torch.nan_to_num((got - exp).abs(), nan=float('inf'))
+    idx = np.unravel_index(int(d.argmax()), tuple(d.shape))
+    raise AssertionError(f'{what}: {int((d != 0).sum())} of {d.numel()} elements differ; worst at {idx}: got {float(got[idx])!r}, expected {float(exp[idx])!r}')
+
+
 # ------------------------------------------------------------------------------------------------------------------------------- inputs
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
@@ -197,3 +208,21 @@ def _operand(C, w, dcode):
     """fp32 [..., K] in a documented packed layout -> the device operand of the compute dtype (bf16x3: split on the innermost dimension)."""
     w = w.contiguous()
     return C.ops.split_encode(w) if dcode == 2 else w.to(C.ops.TORCH_DT[dcode])
+
+
+# --------------------------------------------------------------------------------------------------------------------------- references
+def _wgrad_ref(mode, a, b, shape):
+    """a [npix, Rp], b [npix | 4 npix, Cp] (fp32 values) -> float64 [Rp][Cp][taps] = sum over pixels of a[p, r] b[nbr_t(p), c] and the sum of the
+    absolute terms.  CONV3: nbr_t(p) = p + (ky - 1, kx - 1), zero outside the image; PW: p; UP2: (2 y + dy, 2 x + dx), t = 2 dy + dx."""
+    B, H, W = shape
+    Cp, ad = b.shape[1], a.double()
+    if mode == 0:
+        pad = torch.zeros(B, H + 2, W + 2, Cp, dtype=torch.float64, device=a.device)
+        pad[:, 1:H + 1, 1:W + 1] = b.double().view(B, H, W, Cp)
+        taps = [pad[:, ky:ky + H, kx:kx + W].reshape(B * H * W, Cp) for ky in range(3) for kx in range(3)]
+    elif mode == 1:
+        taps = [b.double()]
+    else:
+        bv = b.double().view(B, H, 2, W, 2, Cp)
+        taps = [bv[:, :, dy, :, dx].reshape(B * H * W, Cp) for dy in range(2) for dx in range(2)]
+    return torch.stack([ad.T @ t for t in taps], -1), torch.stack([ad.abs().T @ t.abs() for t in taps], -1)

@@ -102,7 +102,7 @@ import pytest
 import torch
 
 from grid_util import (DEV, EPS, STORE_REL, Act, Rows, _dev, _expect_bits, _expect_rows, _half, _ints, _normal, _operand, _per_element, _raw,
-                       _twice)
+                       _twice, _wgrad_ref)
 
 pytestmark = pytest.mark.gpu
 
@@ -264,23 +264,6 @@ def _border_class(shape):
     _, y, x = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(W), indexing='ij')
     cls = 3 * torch.where(y == 0, 0, torch.where(y == H - 1, 2, 1)) + torch.where(x == 0, 0, torch.where(x == W - 1, 2, 1))
     return cls.reshape(-1).to(DEV)
-
-
-def _wgrad_ref(mode, a, b, shape):
-    """a [npix, Rp], b [npix | 4 npix, Cp] (fp32 values) -> float64 [Rp][Cp][taps] = sum over pixels of a[p, r] b[nbr_t(p), c] and the sum of the
-    absolute terms.  CONV3: nbr_t(p) = p + (ky - 1, kx - 1), zero outside the image; PW: p; UP2: (2 y + dy, 2 x + dx), t = 2 dy + dx."""
-    B, H, W = shape
-    Cp, ad = b.shape[1], a.double()
-    if mode == 0:
-        pad = torch.zeros(B, H + 2, W + 2, Cp, dtype=torch.float64, device=a.device)
-        pad[:, 1:H + 1, 1:W + 1] = b.double().view(B, H, W, Cp)
-        taps = [pad[:, ky:ky + H, kx:kx + W].reshape(B * H * W, Cp) for ky in range(3) for kx in range(3)]
-    elif mode == 1:
-        taps = [b.double()]
-    else:
-        bv = b.double().view(B, H, 2, W, 2, Cp)
-        taps = [bv[:, :, dy, :, dx].reshape(B * H * W, Cp) for dy in range(2) for dx in range(2)]
-    return torch.stack([ad.T @ t for t in taps], -1), torch.stack([ad.abs().T @ t.abs() for t in taps], -1)
 
 
 def _acc_bound(key, dcode, n, mag, prod):

@@ -756,6 +756,33 @@ def test_conv3_grid_exact_cases_stay_below_2_24(conv3_grid):
     conv3_grid.check_exact_conditions()
 
 
+@pytest.fixture
+def wino_grid(monkeypatch):
+    """tests/test_wino_wgrad_grid_gpu.py with its tensors on the host (as conv3_grid)."""
+    import grid_util
+    import test_wino_wgrad_grid_gpu as grid
+    for mod in (grid_util, grid):
+        monkeypatch.setattr(mod, 'DEV', torch.device('cpu'))
+    return grid
+
+
+def test_wino_wgrad_grid_cases_reach_every_plan(wino_grid):
+    """The rows of test_wino_wgrad_grid_gpu.py reach both in-kernel kernels ragged and not, every reduce template and split class, every
+    stream-K slot class, the wave-level plan's four block shapes and the default plan's switch, from its copies of the launchers' rules."""
+    wino_grid.check_wino_wgrad_plans()
+
+
+def test_wino_wgrad_grid_exact_cases_stay_below_2_24(wino_grid):
+    """Every exact-integer case keeps every transform and plane sum of absolute terms below 2^24, and the file's transform matrices
+    reproduce the direct-sum reference in float64, from the references alone."""
+    wino_grid.check_wino_exact_conditions()
+
+
+def test_wino_wgrad_grid_layout_helpers_round_trip(wino_grid):
+    """The V / Yt index helpers and the tile order of test_wino_wgrad_grid_gpu.py round-trip and agree with the vectorised placement."""
+    wino_grid.check_wino_layout_helpers()
+
+
 def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):
     """clamd_bn_finalize / _apply / _bwd_reduce / _bwd_finalize / _bwd_apply / _bwd_apply_sums / _bwd_eval, clamd_maxpool2x2[_bwd] and
     clamd_channel_sum: a null pointer the selected kernel would dereference, a pitch below Cp, a non-positive B / H / W are refused by a host check -- status -1 (clamd_fail) and that check's message, never -2 (a launch
