@@ -205,6 +205,25 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+_ROWS_CHECKED = set()
+
+
+def job_table(row_dtype, rows, numels, device, sizeof_name):
+    """Device tables of one launch of a multi-tensor pass (csrc/optim.hip): `rows`, one tuple of the numpy struct `row_dtype` per tensor, and
+    the job list of (tensor, chunk) pairs that covers numels[i] elements of tensor i in chunks of clamd_adam_chunk_elems().  `sizeof_name`:
+    the library's getter of the row size, checked against row_dtype once.  Returns (rows_dev, chunks_dev, nchunks)."""
+    import numpy as np
+    import torch
+    lib = load()
+    if sizeof_name not in _ROWS_CHECKED:
+        assert getattr(lib, sizeof_name)() == row_dtype.itemsize, sizeof_name
+        _ROWS_CHECKED.add(sizeof_name)
+    chunk = lib.clamd_adam_chunk_elems()
+    chunks = [(i, c) for i, n in enumerate(numels) for c in range((n + chunk - 1) // chunk)]
+    table = np.array(rows, dtype=row_dtype)
+    return (torch.from_numpy(table.view(np.uint8).copy()).to(device), torch.tensor(chunks, dtype=torch.int32, device=device), len(chunks))
+
+
 def stream_ptr():
     import torch
     return torch.cuda.current_stream().cuda_stream

@@ -55,18 +55,11 @@ class Consolidation:
         key = tuple(s.data_ptr() for s in srcs)
         tab = self._tables.get(key)
         if tab is None:
-            lib = _lib.load()
-            assert lib.clamd_sizeof_importance_tensor() == _ROW_DT.itemsize
-            chunk = lib.clamd_adam_chunk_elems()
-            rows = np.zeros(len(srcs), dtype=_ROW_DT)
-            chunks = []
-            for i, (w, s) in enumerate(zip(self.importance, srcs)):
-                rows[i] = (w.data_ptr(), s.data_ptr(), w.numel())
-                chunks += [(i, c) for c in range((w.numel() + chunk - 1) // chunk)]
+            rows = [(w.data_ptr(), s.data_ptr(), w.numel()) for w, s in zip(self.importance, srcs)]
             if len(self._tables) >= 4:          # gradients that move every step: do not pile tables up
                 self._tables.clear()
-            tab = self._tables[key] = (torch.from_numpy(rows.view(np.uint8).copy()).to(self.device),
-                                       torch.tensor(chunks, dtype=torch.int32, device=self.device), len(chunks))
+            tab = self._tables[key] = _lib.job_table(_ROW_DT, rows, [w.numel() for w in self.importance], self.device,
+                                                     'clamd_sizeof_importance_tensor')
         return tab
 
     def _launch(self, srcs, decay, scale, power):

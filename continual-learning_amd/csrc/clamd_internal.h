@@ -52,15 +52,6 @@ inline int clamd_usable_cus(const clamd_tuning& t) {
 long long clamd_winograd_stat_rows(int B, int H, int W, int Cout_p, const clamd_tuning& tn);
 long long clamd_bn_bwd_reduce_rows(int B, int H, int W, int Cp, bool pooled, const clamd_tuning& tn);
 
-// The (tensor, chunk) job list of the multi-tensor passes (Adam and importance in misc.hip, SGD in sgd.hip): one workgroup per job,
-// ADAM_CHUNK elements per chunk (clamd_adam_chunk_elems()).
-namespace clamd {
-struct AdamChunk { int tensor; int chunk; };
-constexpr int ADAM_CHUNK = 4096;
-}
-// accum[0] = the sum of the per-workgroup partials accum[1 .. n] in a fixed order (misc.hip, adam_l2_final_kernel); enqueue only
-void clamd_launch_partial_sum(float* accum, int n, hipStream_t stream);
-
 // the three filter-pack launches with an optional border-class bias table appended (grid = total_blocks + Cout_p; bnfold.hip)
 namespace clamd { struct FoldBias; }
 int clamd_launch_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, const clamd::FoldBias* fold, hipStream_t stream);

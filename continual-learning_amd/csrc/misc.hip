@@ -1,6 +1,6 @@
 // Remaining pieces of the train-step path: error plumbing, weight re-packing (fp32 NCHW-style master parameters ->
-// the K-innermost compute-dtype layouts the implicit-GEMM kernels read), fused multi-tensor Adam (+ L2-to-old-weights, A13),
-// and the GPU-resident arg-max/confusion-matrix instrument.  The per-pixel loss is loss.hip.
+// the K-innermost compute-dtype layouts the implicit-GEMM kernels read) and the GPU-resident arg-max/confusion-matrix instrument
+// (SURVEY.md §8f row 1).  The per-pixel loss is loss.hip, the optimisers are optim.hip.
 #include <string.h>
 #include <stdio.h>
 #include "common.hip.h"
@@ -244,160 +244,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackJob* __restrict__ j
     }
 }
 
-// ------------------------------------------------------------------------------------------------ Adam
-// torch.optim.Adam semantics (trainer.py:108-110,176): weight decay 0, amsgrad off, maximize off.
-//   m = lerp(m, g, 1-b1); v = v*b2 + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-// hyper (device, fp32): [0] lr  [1] beta1  [2] beta2  [3] eps  [4] grad_scale  [5] l2_lambda
-// state (device): step counter (int), derived[0] = lr/bc1, derived[1] = sqrt(bc2)
-struct AdamTensor { float* p; const float* g; float* m; float* v; const float* old; long long n; };
-// AdamChunk and ADAM_CHUNK: clamd_internal.h (shared with sgd.hip)
-
-__global__ void adam_prepare_kernel(const float* hyper, int* step, float* derived) {
-    const int s = *step + 1;
-    *step = s;
-    const double b1 = hyper[1], b2 = hyper[2];
-    derived[0] = (float)((double)hyper[0] / (1.0 - pow(b1, (double)s)));
-    derived[1] = (float)sqrt(1.0 - pow(b2, (double)s));
-}
-
-__global__ void __launch_bounds__(256) adam_kernel(const AdamTensor* __restrict__ tensors,
-                                                   const AdamChunk* __restrict__ chunks,
-                                                   const float* __restrict__ hyper, const float* __restrict__ derived,
-                                                   float* l2_accum) {
-    const AdamChunk c = chunks[blockIdx.x];
-    const AdamTensor t = tensors[c.tensor];
-    const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], gs = hyper[4], l2 = hyper[5];
-    const float step_size = derived[0], bc2s = derived[1];
-    const float w1 = 1.f - b1, w2 = 1.f - b2;
-    const long long base = (long long)c.chunk * ADAM_CHUNK;
-    float l2sum = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
-        const long long i = base + k * 256 + threadIdx.x;
-        if (i < t.n) {
-            float g = t.g[i] * gs;
-            const float p = t.p[i];
-            if (t.old) { const float d = p - t.old[i]; g += 2.f * l2 * d; l2sum += d * d; }
-            float m = t.m[i], v = t.v[i];
-            // torch lerp: weight < 0.5 ? m + w*(g-m) : g - (g-m)*(1-w)
-            m = (w1 < 0.5f) ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);
-            v = v * b2 + (w2 * g) * g;
-            const float denom = sqrtf(v) / bc2s + eps;
-            t.p[i] = p - step_size * (m / denom);
-            t.m[i] = m; t.v[i] = v;
-        }
-    }
-    if (l2_accum) {
-        // no float atomics: one partial per workgroup (shuffle tree, then the four waves in a fixed order); adam_l2_final_kernel
-        // adds the partials in a fixed order, so the reported penalty is bit-reproducible
-        __shared__ float wsum[4];
-        l2sum = wave_sum(l2sum);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = l2sum;
-        __syncthreads();
-        if (threadIdx.x == 0) l2_accum[1 + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-    }
-}
-
-// l2[0] = sum of the per-workgroup partials l2[1 .. n] in a fixed order (fp64): thread t adds partials t, t + 256, ...; then a
-// fixed tree over the 256 threads
-__global__ void __launch_bounds__(256) adam_l2_final_kernel(float* l2, int n) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += (double)l2[1 + i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) l2[0] = (float)red[0];
-}
-
-// ------------------------------------------------------------------------------------------------ elastic weight consolidation
-// Importance-weighted pull towards the anchor (build-defined): g += lam_ewc * omega * (p - old), on top of the
-// uniform L2 term above (same anchor).  A kernel of its own so that adam_kernel -- what every step without consolidation launches --
-// stays exactly what it was.  hyper[6] = lam_ewc.  36 B / parameter (p, g, m, v, old, omega read; p, m, v written).
-// ewc_accum[1 + block] = this workgroup's sum omega d^2, l2_accum[1 + block] (optional) = its sum d^2; adam_l2_final_kernel adds each in
-// a fixed order.
-__global__ void __launch_bounds__(256) adam_consolidated_kernel(const AdamTensor* __restrict__ tensors,
-                                                                const float* const* __restrict__ importance,
-                                                                const AdamChunk* __restrict__ chunks,
-                                                                const float* __restrict__ hyper, const float* __restrict__ derived,
-                                                                float* ewc_accum, float* l2_accum) {
-    const AdamChunk c = chunks[blockIdx.x];
-    const AdamTensor t = tensors[c.tensor];
-    const float* __restrict__ om = importance[c.tensor];
-    const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], gs = hyper[4], l2 = hyper[5], lam = hyper[6];
-    const float step_size = derived[0], bc2s = derived[1];
-    const float w1 = 1.f - b1, w2 = 1.f - b2;
-    const long long base = (long long)c.chunk * ADAM_CHUNK;
-    float l2sum = 0.f, esum = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
-        const long long i = base + k * 256 + threadIdx.x;
-        if (i < t.n) {
-            float g = t.g[i] * gs;
-            const float p = t.p[i];
-            const float d = p - t.old[i], w = om[i];
-            g += 2.f * l2 * d;
-            g += lam * w * d;
-            l2sum += d * d;
-            esum += w * (d * d);
-            float m = t.m[i], v = t.v[i];
-            m = (w1 < 0.5f) ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);       // torch lerp, as adam_kernel
-            v = v * b2 + (w2 * g) * g;
-            const float denom = sqrtf(v) / bc2s + eps;
-            t.p[i] = p - step_size * (m / denom);
-            t.m[i] = m; t.v[i] = v;
-        }
-    }
-    __shared__ float wsum[2][4];
-    esum = wave_sum(esum);
-    l2sum = wave_sum(l2sum);
-    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = esum; wsum[1][threadIdx.x >> 6] = l2sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ewc_accum[1 + blockIdx.x] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
-        if (l2_accum) l2_accum[1 + blockIdx.x] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
-    }
-}
-
-// dst = decay * dst + scale * (SQUARE ? src * src : src) over every tensor of a table, one workgroup per (tensor, chunk) job as in the Adam
-// kernels.  12 B / element.  16-byte accesses: a chunk is shifted by the tensor's `head` (elements up to dst's first 16-byte boundary, peeled
-// by chunk 0), so every vector store is aligned; src may sit at another phase (the engine packs its gradients tightly) and is read through a
-// 4-byte-aligned vector type (gfx9 global memory takes dword-aligned wide accesses).  The last, partial group of a tensor goes element-wise.
-struct ImportanceTensor { float* dst; const float* src; long long n; };
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-template <bool SQUARE>
-__global__ void __launch_bounds__(256) importance_accum_kernel(const ImportanceTensor* __restrict__ tensors,
-                                                               const AdamChunk* __restrict__ chunks, float decay, float scale) {
-    const AdamChunk c = chunks[blockIdx.x];
-    const ImportanceTensor t = tensors[c.tensor];
-    const int head = (int)((4u - (unsigned)(((size_t)t.dst >> 2) & 3u)) & 3u);
-    auto one = [&](long long i) {
-        const float s = t.src[i];
-        t.dst[i] = decay * t.dst[i] + scale * (SQUARE ? s * s : s);
-    };
-    if (c.chunk == 0 && (int)threadIdx.x < head && (long long)threadIdx.x < t.n) one(threadIdx.x);
-    const long long base = (long long)c.chunk * ADAM_CHUNK + head;
-#pragma unroll
-    for (int k = 0; k < ADAM_CHUNK / 1024; ++k) {
-        const long long i = base + 4 * (k * 256 + (int)threadIdx.x);
-        if (i + 4 <= t.n) {
-            const f32x4_a4 s = *(const f32x4_a4*)(t.src + i);
-            float4 d = *(const float4*)(t.dst + i);
-            d.x = decay * d.x + scale * (SQUARE ? s.x * s.x : s.x);
-            d.y = decay * d.y + scale * (SQUARE ? s.y * s.y : s.y);
-            d.z = decay * d.z + scale * (SQUARE ? s.z * s.z : s.z);
-            d.w = decay * d.w + scale * (SQUARE ? s.w * s.w : s.w);
-            *(float4*)(t.dst + i) = d;
-        } else {
-            for (long long j = i; j < t.n; ++j) one(j);
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ metrics
 // arg-max over classes (first maximum wins, as torch.max / argmax) fused with the confusion-matrix histogram
 // conf[K*t + p] += 1 for 0 <= t < K  (metrics.py:32-38).  pred is optional (int64 [B,H,W]).
@@ -610,10 +456,6 @@ __global__ void fill_kernel(float* p, long long n, float v) {
 
 using namespace clamd;
 
-void clamd_launch_partial_sum(float* accum, int n, hipStream_t stream) {
-    hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, stream, accum, n);
-}
-
 int clamd_launch_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, const FoldBias* fold, hipStream_t stream) {
     if (njobs <= 0 || total_blocks <= 0) return clamd_fail("pack: empty job table");
     const FoldBias f = fold ? *fold : FoldBias{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 9};
@@ -633,9 +475,6 @@ extern "C" {
 const char* clamd_last_error(void) { return g_err; }
 int clamd_version(void) { return 100; }
 int clamd_sizeof_pack_job(void) { return (int)sizeof(PackJob); }
-int clamd_sizeof_adam_tensor(void) { return (int)sizeof(AdamTensor); }
-int clamd_adam_chunk_elems(void) { return ADAM_CHUNK; }
-int clamd_sizeof_importance_tensor(void) { return (int)sizeof(ImportanceTensor); }
 int clamd_pack_tile(void) { return PACK_TILE; }
 int clamd_bn_bwd_nsums(void) { return 5; }
 
@@ -654,50 +493,6 @@ int clamd_scale_by_device_scalar_nhwc(void* p, long long n, int dtype, const flo
     else if (dtype == CLAMD_SPLIT) hipLaunchKernelGGL(scale_by_dev_t_kernel<split_t>, dim3((unsigned)g), dim3(256), 0, s, (split_t*)p, n / 8, scale_dev, also_f32, n_f32);
     else return clamd_fail("scale_by_device_scalar_nhwc: bad dtype");
     return clamd_check_launch("scale_by_device_scalar_nhwc");
-}
-
-int clamd_adam_step(const void* tensors_dev, const void* chunks_dev, int nchunks, const float* hyper_dev, int* step_dev,
-                    float* derived_dev, float* l2_accum_dev, void* stream) {
-    if (nchunks <= 0) return clamd_fail("adam: no chunks");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, hyper_dev, step_dev, derived_dev);
-    hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors_dev,
-                       (const AdamChunk*)chunks_dev, hyper_dev, derived_dev, l2_accum_dev);
-    if (l2_accum_dev) hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, s, l2_accum_dev, nchunks);
-    return clamd_check_launch("adam_step");
-}
-
-int clamd_adam_step_consolidated(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks,
-                                 const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev,
-                                 void* stream) {
-    if (nchunks <= 0) return clamd_fail("adam_step_consolidated: no chunks");
-    if (!tensors_dev || !chunks_dev) return clamd_fail("adam_step_consolidated: null tensor or chunk table");
-    if (!importance_dev) return clamd_fail("adam_step_consolidated: null importance table");
-    if (!hyper_dev || !step_dev || !derived_dev) return clamd_fail("adam_step_consolidated: null hyper / step / derived buffer");
-    if (!ewc_accum_dev) return clamd_fail("adam_step_consolidated: null penalty buffer (1 + nchunks floats)");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, hyper_dev, step_dev, derived_dev);
-    hipLaunchKernelGGL(adam_consolidated_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors_dev,
-                       (const float* const*)importance_dev, (const AdamChunk*)chunks_dev, hyper_dev, derived_dev, ewc_accum_dev, l2_accum_dev);
-    hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, s, ewc_accum_dev, nchunks);
-    if (l2_accum_dev) hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, s, l2_accum_dev, nchunks);
-    return clamd_check_launch("adam_step_consolidated");
-}
-
-int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double scale, int power, void* stream) {
-    if (nchunks <= 0) return clamd_fail("importance_accum: no chunks");
-    if (!tensors_dev || !chunks_dev) return clamd_fail("importance_accum: null tensor or chunk table");
-    if (power != 1 && power != 2) return clamd_fail("importance_accum: power must be 1 or 2");
-    if (!(decay >= 0.0) || !(decay <= 3.0e38)) return clamd_fail("importance_accum: decay must be finite and >= 0");
-    if (!(scale >= 0.0) || !(scale <= 3.0e38)) return clamd_fail("importance_accum: scale must be finite and >= 0");
-    hipStream_t s = (hipStream_t)stream;
-    if (power == 2)
-        hipLaunchKernelGGL(importance_accum_kernel<true>, dim3(nchunks), dim3(256), 0, s, (const ImportanceTensor*)tensors_dev,
-                           (const AdamChunk*)chunks_dev, (float)decay, (float)scale);
-    else
-        hipLaunchKernelGGL(importance_accum_kernel<false>, dim3(nchunks), dim3(256), 0, s, (const ImportanceTensor*)tensors_dev,
-                           (const AdamChunk*)chunks_dev, (float)decay, (float)scale);
-    return clamd_check_launch("importance_accum");
 }
 
 int clamd_argmax_confusion(const float* logits, const long long* labels, long long* pred, unsigned long long* conf,

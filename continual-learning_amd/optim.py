@@ -1,4 +1,4 @@
-"""Fused multi-tensor Adam on libclamd (one launch for all 82 parameter tensors).
+"""Fused multi-tensor optimisers on libclamd (csrc/optim.hip): one launch for all 82 parameter tensors.
 
 ``FusedAdam(params, lr, betas)`` mirrors ``torch.optim.Adam`` as the reference constructs it (trainer.py:108-110:
 weight_decay 0, amsgrad off, eps 1e-8) including the ``state_dict()`` layout ('step', 'exp_avg', 'exp_avg_sq' per
@@ -10,34 +10,102 @@ Optional L2-to-old-weights regulariser (build-defined): ``se
 2*lam*(theta - theta_old) to every gradient inside the same kernel.
 
 Optional elastic weight consolidation (build-defined as well): ``set_consolidation(old_params, importance, lam)`` adds
-lam*omega*(theta - theta_old); such a step runs ``clamd_adam_step_consolidated`` (36 B / parameter), every other step the unchanged
+lam*omega*(theta - theta_old); such a step runs ``clamd_adam_step_consolidated`` (36 B / parameter), every other step
 ``clamd_adam_step``.
 
-``FusedSGD`` (below) is the second optimiser: torch.optim.SGD with momentum, Nesterov and weight decay in one launch of
-``clamd_sgd_step`` (csrc/sgd.hip), with the same surface and the same two anchor terms (shared through ``_AnchorTerms``).
+``FusedSGD`` is the second optimiser: torch.optim.SGD with momentum, Nesterov and weight decay in one launch of ``clamd_sgd_step``.  Both
+are a ``_FusedOptimizer``, which owns everything they do alike: the step protocol, the device tables, the two anchor terms, head growth
+and checkpoints.  A subclass says how one table row is filled, which eight hyper-parameters it uploads, how its state is laid out in flat
+buffers and grows, and which entry point it launches.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call, ptr
-
-_TENSOR_DT = np.dtype([('p', 'u8'), ('g', 'u8'), ('m', 'u8'), ('v', 'u8'), ('old', 'u8'), ('n', 'i8')])
+from ._lib import ptr
 
 
-class _AnchorTerms:
-    """The two build-defined pulls towards an anchor that FusedAdam and FusedSGD share (one anchor pointer per tensor serves both): the
-    L2-to-old-weights term and elastic weight consolidation.  The optimiser provides param_groups, _NAME, _table, _hyper_host and, after a
-    step, _l2acc / _ewcacc."""
+class _FusedOptimizer(torch.optim.Optimizer):
+    """One parameter group of contiguous fp32 GPU tensors behind one device table (rows of _ROW_DT, checked against the library's
+    _SIZEOF()).  The two build-defined pulls towards an anchor (one anchor pointer per tensor serves both) live here: the L2-to-old-weights
+    term and elastic weight consolidation."""
 
-    def _init_anchor_terms(self):
+    def __init__(self, params, defaults, grad_scale):
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError(f'{self._NAME} supports a single parameter group ({self._ONE_GROUP})')
+        self.grad_scale = grad_scale
+        self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
+        self._table = None
+        self._hyper_host = None
+        self._state_dev = None        # device of the flat state buffers; None: they are laid out (again) at the next step
         self._l2_lambda = 0.0
         self._anchor = None
         self._l2_on = False           # the anchor serves the L2 term, the consolidation term, or both
+        self._l2acc = None            # [0] = sum ||theta - theta_old||^2 of the last step, [1..] = per-workgroup partials
         self._importance = None
         self._ewc_lambda = 0.0
         self._ewcacc = None
 
+    # -- the step ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for h in self.pre_step_hooks:
+            h()
+        params = self.param_groups[0]['params']
+        key = []
+        for p in params:
+            gr = p.grad
+            if gr is None:
+                raise RuntimeError(f'{self._NAME}: every parameter must have a gradient (the UNet backward produces all of them)')
+            key.append((p.data_ptr(), gr.data_ptr()))
+        if self._table != key:       # first step, or parameters / gradients moved: validate and rebuild the device table
+            for p in params:
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise RuntimeError(f'{self._NAME} needs contiguous fp32 GPU parameters and gradients: there is no CPU fallback')
+            dev = params[0].device
+            if self._state_dev != dev:
+                self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+                self._hyper_host = None       # a new device buffer: sync_hyper uploads again
+                self._init_state(params, dev)
+                self._state_dev = dev
+            self._build_table(params, dev)
+            self._table = key
+        self.sync_hyper()
+        self._launch()
+        return loss
+
+    def _build_table(self, params, dev):
+        rows = [self._row(p, self._anchor[i].data_ptr() if self._anchor is not None else 0) for i, p in enumerate(params)]
+        numels = [p.numel() for p in params]
+        self._tensors_dev, self._chunks_dev, self._nchunks = _lib.job_table(self._ROW_DT, rows, numels, dev, self._SIZEOF)
+        self._numel = int(sum(numels))
+        self._l2acc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+        self._ewcacc = self._importance_dev = None
+        if self._importance is not None:
+            self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
+            self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+
+    def sync_hyper(self):
+        """Upload the eight hyper-parameters (learning rate, ..., gradient scale, L2 and consolidation weights) to device memory if they
+        changed on the host (LambdaLR writes param_groups[0]['lr']).  step() calls this; a replayed HIP graph of the step
+        (tools/graphed_step.py) calls it before every replay, because the captured kernel reads the values from that device buffer."""
+        hyper = self._hyper_tuple(self.param_groups[0]) + (float(self.grad_scale), float(self._l2_lambda), float(self._ewc_lambda), 0.0)
+        if hyper != self._hyper_host:
+            self._hyper.copy_(torch.tensor(hyper, dtype=torch.float32))
+            self._hyper_host = hyper
+
+    def note_replayed_step(self, n=1):
+        """FusedAdam mirrors its device step counter here; nothing to do without one."""
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._table = None            # the restored state is re-homed into the flat buffers at the next step
+        self._hyper_host = None
+        self._state_dev = None
+
+    # -- class-incremental head growth ---------------------------------------------------------------------
     @staticmethod
     def _grown(old, new_shape, fill):
         """`old` with rows appended along dim 0 up to new_shape; the new rows take `fill`'s (None: zero)."""
@@ -47,8 +115,14 @@ class _AnchorTerms:
             out[old.shape[0]:].copy_(fill[old.shape[0]:])
         return out
 
-    def _growth_plan(self, mapping):
-        """Validates a replace_params mapping -> [(index in the group, old parameter, new parameter)]."""
+    @torch.no_grad()
+    def replace_params(self, mapping):
+        """Class-incremental head growth (UNet.expand_classes): swaps parameter objects inside the group and re-homes their state.
+        mapping: {old_param: new_param}; new_param has more rows along dim 0 and the same trailing shape (anything else: ValueError).
+        The state of the leading rows is kept, the new rows start at zero, a shared step counter stays.  The L2 / consolidation anchor of
+        the new rows is their current (initial) value and their importance zero: nothing pulls on classes the finished task never had.
+        The importance list is replaced (grown copies); a Consolidation re-installs its own views after Consolidation.grow.  Flat state
+        and device tables are laid out again at the next step."""
         params = self.param_groups[0]['params']
         index = {id(p): i for i, p in enumerate(params)}
         todo = []
@@ -60,15 +134,26 @@ class _AnchorTerms:
             if new.device != old.device or new.dtype != old.dtype:
                 raise ValueError(f'{self._NAME}.replace_params: the new parameter must keep the device and dtype')
             todo.append((index[id(old)], old, new))
-        return todo
+        states = [self.state.get(p) for p in params]
+        for i, old, new in todo:
+            if states[i]:
+                states[i] = self._grow_state(states[i], new.shape)
+            if self._anchor is not None:
+                self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
+            if self._importance is not None:
+                self._importance[i] = self._grown(self._importance[i], new.shape, None)
+            self.state.pop(old, None)
+            params[i] = new
+        for p, st in zip(params, states):
+            if st:
+                self.state[p] = self._rekeyed_state(st)
+        self._state_dev = None
+        self._table = None
 
-    def _grow_anchor_terms(self, i, new):
-        """The anchor of the new rows is their current (initial) value and their importance zero."""
-        if self._anchor is not None:
-            self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
-        if self._importance is not None:
-            self._importance[i] = self._grown(self._importance[i], new.shape, None)
+    def _rekeyed_state(self, st):
+        return dict(st)
 
+    # -- the two anchor terms ------------------------------------------------------------------------------
     def set_l2_anchor(self, old_params, lam):
         """old_params: list of tensors aligned with this optimiser's parameters (a frozen task-1 snapshot).  With a consolidation set the
         anchor is shared (one pointer per tensor in the device table): it has to be the same snapshot."""
@@ -141,36 +226,25 @@ class _AnchorTerms:
         return self._ewcacc[:1] * (0.5 * self._ewc_lambda)
 
 
-class FusedAdam(_AnchorTerms, torch.optim.Optimizer):
+class FusedAdam(_FusedOptimizer):
     _NAME = 'FusedAdam'
+    _ONE_GROUP = 'as trainer.py:108 builds'
+    _ROW_DT = np.dtype([('p', 'u8'), ('g', 'u8'), ('m', 'u8'), ('v', 'u8'), ('old', 'u8'), ('n', 'i8')])
+    _SIZEOF = 'clamd_sizeof_adam_tensor'
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
-        betas = tuple(betas)
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
                         capturable=False, differentiable=False, fused=None)
-        super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError('FusedAdam supports a single parameter group (as trainer.py:108 builds)')
-        self.grad_scale = grad_scale
-        self._init_anchor_terms()
-        self._table = None
-        self._hyper_host = None
-        self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
+        super().__init__(params, defaults, grad_scale)
 
-    # -- device state ------------------------------------------------------------------------------------
-    def _init_state(self, params):
-        dev = params[0].device
-        lib = _lib.load()
-        assert lib.clamd_sizeof_adam_tensor() == _TENSOR_DT.itemsize
+    def _init_state(self, params, dev):
+        """Lays exp_avg / exp_avg_sq out in two flat buffers and re-homes what load_state_dict or replace_params left in self.state."""
         n = sum(p.numel() for p in params)
         prev = [self.state.get(p) for p in params]
         self._m = torch.zeros(n, dtype=torch.float32, device=dev)
         self._v = torch.zeros(n, dtype=torch.float32, device=dev)
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._derived = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
-        self._hyper_host = None       # a new device buffer: sync_hyper uploads again
-        self._l2acc = None            # [0] = sum ||theta - theta_old||^2 of the last step, [1..] = per-workgroup partials
         off, steps0 = 0, set()
         self._step_host = torch.tensor(0.0)          # ONE host-side step counter shared by every parameter's state
         for p, st in zip(params, prev):
@@ -189,116 +263,42 @@ class FusedAdam(_AnchorTerms, torch.optim.Optimizer):
         self._step_host.fill_(steps0.pop())
         self._step_dev.fill_(int(self._step_host))
 
-    def _build_table(self, params):
-        chunk = _lib.load().clamd_adam_chunk_elems()
-        t = np.zeros(len(params), dtype=_TENSOR_DT)
-        chunks = []
-        for i, p in enumerate(params):
-            st = self.state[p]
-            old = self._anchor[i].data_ptr() if self._anchor is not None else 0
-            t[i] = (p.data_ptr(), p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), old, p.numel())
-            chunks += [(i, c) for c in range((p.numel() + chunk - 1) // chunk)]
-        dev = params[0].device
-        self._tensors_dev = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
-        self._chunks_dev = torch.tensor(chunks, dtype=torch.int32, device=dev)
-        self._nchunks = len(chunks)
-        self._numel = int(sum(p.numel() for p in params))
-        self._l2acc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
-        self._ewcacc = self._importance_dev = None
-        if self._importance is not None:
-            self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
-            self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
-        self._table = [(p.data_ptr(), p.grad.data_ptr()) for p in params]
+    def _row(self, p, old):
+        st = self.state[p]
+        return (p.data_ptr(), p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), old, p.numel())
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._table = None            # restored exp_avg / exp_avg_sq are re-homed into the flat buffers at the next step
-        if hasattr(self, '_m'):
-            del self._m
+    def _hyper_tuple(self, group):
+        return (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]), float(group['eps']))
 
-    @torch.no_grad()
-    def replace_params(self, mapping):
-        """Class-incremental head growth (UNet.expand_classes): swaps parameter objects inside the group and re-homes their state.
-        mapping: {old_param: new_param}; new_param has more rows along dim 0 and the same trailing shape (anything else: ValueError).
-        exp_avg / exp_avg_sq of the leading rows are kept, the new rows start at zero, the shared step counter stays.  The L2 /
-        consolidation anchor of the new rows is their current (initial) value and their importance zero: nothing pulls on classes the
-        finished task never had.  The importance list is replaced (grown copies); a Consolidation re-installs its own views after
-        Consolidation.grow.  Device tables are rebuilt at the next step."""
-        params = self.param_groups[0]['params']
-        todo = self._growth_plan(mapping)
-        states = [self.state.get(p) for p in params]
-        for i, old, new in todo:
-            st = states[i]
-            if st:       # moments of the leading rows; _init_state re-homes them into new flat buffers at the next step
-                states[i] = {'step': st['step'], 'exp_avg': self._grown(st['exp_avg'], new.shape, None),
-                             'exp_avg_sq': self._grown(st['exp_avg_sq'], new.shape, None)}
-            self._grow_anchor_terms(i, new)
-            self.state.pop(old, None)
-            params[i] = new
-        step = float(self._step_host) if hasattr(self, '_step_host') else None
-        for p, st in zip(params, states):
-            if st:
-                self.state[p] = dict(st, step=torch.tensor(step) if step is not None else st['step'])
-        if hasattr(self, '_m'):
-            del self._m              # as after load_state_dict: the flat moment buffers are laid out again
-        self._table = None
+    def _grow_state(self, st, shape):
+        return {'step': st['step'], 'exp_avg': self._grown(st['exp_avg'], shape, None), 'exp_avg_sq': self._grown(st['exp_avg_sq'], shape, None)}
 
-    def sync_hyper(self):
-        """Upload lr / betas / eps / gradient scale / L2 and consolidation weights to device memory if they changed on the host (LambdaLR
-        writes param_groups[0]['lr']).  step() calls this; a replayed HIP graph of the step (tools/graphed_step.py) calls it
-        before every replay, because the captured Adam kernel reads the values from that device buffer."""
-        group = self.param_groups[0]
-        hyper = (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]), float(group['eps']),
-                 float(self.grad_scale), float(self._l2_lambda), float(self._ewc_lambda), 0.0)
-        if hyper != self._hyper_host:
-            self._hyper.copy_(torch.tensor(hyper, dtype=torch.float32))
-            self._hyper_host = hyper
+    def _rekeyed_state(self, st):
+        return dict(st, step=torch.tensor(float(self._step_host))) if hasattr(self, '_step_host') else dict(st)
 
     def note_replayed_step(self, n=1):
         """Host-side mirror of the device step counter after a graph replay executed the Adam kernel (n = -1 after the
         capture itself, which runs step() on the host without executing anything)."""
         self._step_host += n
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        for h in self.pre_step_hooks:
-            h()
-        group = self.param_groups[0]
-        params = group['params']
-        key = []
-        for p in params:
-            gr = p.grad
-            if gr is None:
-                raise RuntimeError('FusedAdam: every parameter must have a gradient (the UNet backward produces all of them)')
-            key.append((p.data_ptr(), gr.data_ptr()))
-        if self._table != key:       # first step, or parameters / gradients moved: validate and rebuild the device table
-            for p in params:
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
-                    raise RuntimeError('FusedAdam needs contiguous fp32 GPU parameters and gradients: there is no CPU fallback')
-            if not hasattr(self, '_m') or self._m.device != params[0].device:
-                self._init_state(params)
-            self._build_table(params)
-        self.sync_hyper()
+    def _launch(self):
         from . import unet as U
+        l2acc = ptr(self._l2acc) if self._l2_on else None
         if self._importance is not None:
             U._hbm('adam', 36 * self._numel,      # p, g, m, v, old, importance read; p, m, v written
                    'clamd_adam_step_consolidated', ptr(self._tensors_dev), ptr(self._importance_dev), ptr(self._chunks_dev), self._nchunks,
-                   ptr(self._hyper), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc),
-                   ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
+                   ptr(self._hyper), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc), l2acc, _lib.stream_ptr())
         else:
             U._hbm('adam', 28 * self._numel,      # p, g, m, v read; p, m, v written (SURVEY 8d)
                    'clamd_adam_step', ptr(self._tensors_dev), ptr(self._chunks_dev), self._nchunks, ptr(self._hyper),
-                   ptr(self._step_dev), ptr(self._derived), ptr(self._l2acc) if self._anchor is not None else None,
-                   _lib.stream_ptr())
+                   ptr(self._step_dev), ptr(self._derived), l2acc, _lib.stream_ptr())
         self._step_host += 1                # host-side mirror of the device counter (shared by all param states)
-        return loss
 
 
 _SGD_TENSOR_DT = np.dtype([('p', 'u8'), ('g', 'u8'), ('buf', 'u8'), ('old', 'u8'), ('n', 'i8'), ('decay_mult', 'f4'), ('pad', 'f4')])
 
 
-class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
+class FusedSGD(_FusedOptimizer):
     """Fused multi-tensor SGD with momentum, Nesterov and weight decay: ``torch.optim.SGD`` semantics (dampening 0, maximize off) in one
     launch of ``clamd_sgd_step`` over all parameters, with the same surface as FusedAdam (grad_scale, pre_step_hooks, sync_hyper,
     set_l2_anchor, set_consolidation, replace_params), so the trainer, ddp.GradSync and Consolidation work with either.
@@ -311,6 +311,9 @@ class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
         buf = momentum * buf + g;  p -= lr * (nesterov ? g + momentum * buf : buf)
     """
     _NAME = 'FusedSGD'
+    _ONE_GROUP = 'the anchor and importance lists follow model.parameters()'
+    _ROW_DT = _SGD_TENSOR_DT
+    _SIZEOF = 'clamd_sizeof_sgd_tensor'
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, no_decay=(), grad_scale=1.0):
         if not lr >= 0.0:
@@ -325,31 +328,18 @@ class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
             raise ValueError('FusedSGD: Nesterov momentum requires a momentum and zero dampening')
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False,
                         foreach=None, differentiable=False, fused=None)
-        super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError('FusedSGD supports a single parameter group (the anchor and importance lists follow model.parameters())')
+        super().__init__(params, defaults, grad_scale)
         own = {id(p) for p in self.param_groups[0]['params']}
         self._no_decay = set()
         for p in no_decay:
             if id(p) not in own:
                 raise ValueError('FusedSGD: a tensor of no_decay is not a parameter of this optimiser')
             self._no_decay.add(id(p))
-        self.grad_scale = grad_scale
-        self._init_anchor_terms()
-        self._table = None
-        self._hyper_host = None
-        self._l2acc = None
-        self.pre_step_hooks = []      # e.g. ddp.GradSync.wait
 
-    # -- device state ------------------------------------------------------------------------------------
-    def _init_state(self, params):
+    def _init_state(self, params, dev):
         """Lays the momentum buffers out in one flat buffer (each tensor's slice starts on 16 bytes, as the parameters themselves do; the
         kernel does not depend on it) and re-homes what load_state_dict or replace_params left in self.state."""
-        dev = params[0].device
-        assert _lib.load().clamd_sizeof_sgd_tensor() == _SGD_TENSOR_DT.itemsize
         prev = [self.state.get(p) for p in params]
-        self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
-        self._hyper_host = None       # a new device buffer: sync_hyper uploads again
         self._with_momentum = float(self.param_groups[0]['momentum']) > 0
         self._flat = None
         for p in params:
@@ -365,97 +355,30 @@ class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
             self.state[p] = {'momentum_buffer': buf}
             off += (p.numel() + 3) // 4 * 4
 
-    def _build_table(self, params):
-        chunk = _lib.load().clamd_adam_chunk_elems()
-        t = np.zeros(len(params), dtype=_SGD_TENSOR_DT)
-        chunks = []
-        for i, p in enumerate(params):
-            buf = self.state[p]['momentum_buffer'].data_ptr() if self._with_momentum else 0
-            old = self._anchor[i].data_ptr() if self._anchor is not None else 0
-            t[i] = (p.data_ptr(), p.grad.data_ptr(), buf, old, p.numel(), 0.0 if id(p) in self._no_decay else 1.0, 0.0)
-            chunks += [(i, c) for c in range((p.numel() + chunk - 1) // chunk)]
-        dev = params[0].device
-        self._tensors_dev = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
-        self._chunks_dev = torch.tensor(chunks, dtype=torch.int32, device=dev)
-        self._nchunks = len(chunks)
-        self._numel = int(sum(p.numel() for p in params))
-        self._l2acc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
-        self._ewcacc = self._importance_dev = None
-        if self._importance is not None:
-            self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
-            self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
-        self._table = [(p.data_ptr(), p.grad.data_ptr()) for p in params]
+    def _row(self, p, old):
+        buf = self.state[p]['momentum_buffer'].data_ptr() if self._with_momentum else 0
+        return (p.data_ptr(), p.grad.data_ptr(), buf, old, p.numel(), 0.0 if id(p) in self._no_decay else 1.0, 0.0)
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._table = None            # restored momentum buffers are re-homed into the flat buffer at the next step
-        self._hyper_host = None
-        if hasattr(self, '_flat'):
-            del self._flat
+    def _hyper_tuple(self, group):
+        if group['dampening'] != 0 or group['maximize']:
+            raise ValueError('FusedSGD: dampening and maximize are not supported')
+        return (float(group['lr']), float(group['momentum']), float(group['weight_decay']), 1.0 if group['nesterov'] else 0.0)
+
+    def _grow_state(self, st, shape):
+        if st.get('momentum_buffer') is None:
+            return st
+        return {'momentum_buffer': self._grown(st['momentum_buffer'], shape, None)}
 
     @torch.no_grad()
     def replace_params(self, mapping):
-        """Class-incremental head growth, as FusedAdam.replace_params: swaps parameter objects inside the group and re-homes their state.
-        The momentum buffer's leading rows are kept and the new rows start at zero; anchors and importance grow as in FusedAdam (the new
-        rows' anchor is their current value, their importance zero); a no_decay flag follows the swapped parameter.  Device tables are
-        rebuilt at the next step."""
-        params = self.param_groups[0]['params']
-        todo = self._growth_plan(mapping)
-        states = [self.state.get(p) for p in params]
-        for i, old, new in todo:
-            st = states[i]
-            if st and st.get('momentum_buffer') is not None:
-                states[i] = {'momentum_buffer': self._grown(st['momentum_buffer'], new.shape, None)}
-            self._grow_anchor_terms(i, new)
+        """As _FusedOptimizer.replace_params; a no_decay flag follows the swapped parameter."""
+        super().replace_params(mapping)
+        for old, new in mapping.items():
             if id(old) in self._no_decay:
                 self._no_decay.discard(id(old))
                 self._no_decay.add(id(new))
-            self.state.pop(old, None)
-            params[i] = new
-        for p, st in zip(params, states):
-            if st:
-                self.state[p] = dict(st)
-        if hasattr(self, '_flat'):
-            del self._flat            # as after load_state_dict: the flat momentum buffer is laid out again
-        self._table = None
 
-    def sync_hyper(self):
-        """Upload lr / momentum / weight decay / Nesterov flag / gradient scale / L2 and consolidation weights to device memory if they
-        changed on the host (LambdaLR writes param_groups[0]['lr']).  step() calls this; a replayed HIP graph of the step calls it before
-        every replay, because the captured kernel reads the values from that device buffer."""
-        group = self.param_groups[0]
-        if group['dampening'] != 0 or group['maximize']:
-            raise ValueError('FusedSGD: dampening and maximize are not supported')
-        hyper = (float(group['lr']), float(group['momentum']), float(group['weight_decay']), 1.0 if group['nesterov'] else 0.0,
-                 float(self.grad_scale), float(self._l2_lambda), float(self._ewc_lambda), 0.0)
-        if hyper != self._hyper_host:
-            self._hyper.copy_(torch.tensor(hyper, dtype=torch.float32))
-            self._hyper_host = hyper
-
-    def note_replayed_step(self, n=1):
-        """FusedAdam mirrors its device step counter here; SGD has none, so there is nothing to do."""
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        for h in self.pre_step_hooks:
-            h()
-        group = self.param_groups[0]
-        params = group['params']
-        key = []
-        for p in params:
-            gr = p.grad
-            if gr is None:
-                raise RuntimeError('FusedSGD: every parameter must have a gradient (the UNet backward produces all of them)')
-            key.append((p.data_ptr(), gr.data_ptr()))
-        if self._table != key:       # first step, or parameters / gradients moved: validate and rebuild the device table
-            for p in params:
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
-                    raise RuntimeError('FusedSGD needs contiguous fp32 GPU parameters and gradients: there is no CPU fallback')
-            if not hasattr(self, '_flat') or self._hyper.device != params[0].device:
-                self._init_state(params)
-            self._build_table(params)
-        self.sync_hyper()
+    def _launch(self):
         from . import unet as U
         ewc = self._importance is not None
         # p, g read and p written; buf read and written; the anchor and the importance read
@@ -463,4 +386,3 @@ class FusedSGD(_AnchorTerms, torch.optim.Optimizer):
         U._hbm('sgd', per_param * self._numel, 'clamd_sgd_step', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None,
                ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._ewcacc) if ewc else None,
                ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
-        return loss

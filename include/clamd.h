@@ -366,7 +366,7 @@ int clamd_nhwc_to_nchw(const void* src, int ldc, float* dst, int B, int C, int H
 /* NCHW fp32 image -> NHWC with the 3x3 neighbourhood folded into channels: dst[p, c*9 + ky*3 + kx] (9*C <= Cp). */
 int clamd_nchw_im2col3(const float* src, void* dst, int ldc, int B, int C, int H, int W, int Cp, int dtype, void* stream);
 
-/* ---- parameters, optimiser, metrics (misc.hip); the loss (loss.hip) -------------------------------------------
+/* ---- parameters, metrics (misc.hip); the loss (loss.hip); the optimisers further down (optim.hip) ------------
  * clamd_pack: one fused launch re-packing every fp32 master parameter into the layouts above (job table built by
  * the host). */
 int clamd_pack(const void* jobs_dev, int njobs, int total_blocks, int dtype, void* stream);

@@ -1,5 +1,5 @@
 """Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py, test_conv3_grid_gpu.py,
-test_wino_wgrad_grid_gpu.py): poisoned buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit
+test_wino_wgrad_grid_gpu.py, test_sgd_gpu.py, test_adam_grid_gpu.py): poisoned buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit
 expectations, the two-runs check, the storage rounding of the three dtypes, the per-element comparison against a float64 reference and the
 float64 weight-gradient reference (a sum over pixels per tap)."""
 import math
@@ -77,6 +77,36 @@ class Rows:
         a = self.buf.clone()
         a[GUARD:GUARD + self.n * self.per] = self.before[GUARD:GUARD + self.n * self.per]
         return torch.equal(_raw(a), _raw(self.before))
+
+
+class Banded:
+    """fp32 tensors of `sizes` inside one flat poisoned buffer, tensor i starting at element phase phases[i] (mod 4) behind a guard band."""
+
+    def __init__(self, sizes, phases, values=None):
+        offs, cur = [], 0
+        for n, ph in zip(sizes, phases):
+            start = (cur + 3) // 4 * 4 + GUARD + ph
+            offs.append(start)
+            cur = start + n
+        self.offs = offs
+        self.flat = torch.full((cur + GUARD + 3,), POISON, dtype=torch.float32, device=DEV)
+        assert self.flat.data_ptr() % 16 == 0
+        self.views = [self.flat[o:o + n] for o, n in zip(offs, sizes)]
+        self.guard = torch.ones(self.flat.shape, dtype=torch.bool, device=DEV)
+        for o, n in zip(offs, sizes):
+            self.guard[o:o + n] = False
+        if values is not None:
+            for v, x in zip(self.views, values):
+                v.copy_(x)
+        self.before = self.flat.clone()
+        for v, ph in zip(self.views, phases):
+            assert (v.data_ptr() // 4) % 4 == ph
+
+    def restore(self):
+        self.flat.copy_(self.before)
+
+    def guards_intact(self):
+        return bool(torch.equal(self.flat[self.guard].view(torch.int32), self.before[self.guard].view(torch.int32)))
 
 
 def _twice(what, launch):

@@ -1,4 +1,4 @@
-"""CPU-only tests of elastic weight consolidation's host side: the two entry points validate before any launch, FusedAdam.set_consolidation
+"""CPU-only tests of elastic weight consolidation's host side: the entry points validate before any launch, FusedAdam.set_consolidation
 validates its arguments, Consolidation.state_dict round-trips by parameter name, and checkpoints with and without the optional
 'consolidation_state' key load.  No kernel is launched here."""
 import ctypes
@@ -44,6 +44,13 @@ def test_ewc_entry_points_reject_bad_arguments_before_any_launch(C):
         ('null hyper / step / derived', 'clamd_adam_step_consolidated', (a, a, a, 4, a, None, a, a, None, None)),
         ('null hyper / step / derived', 'clamd_adam_step_consolidated', (a, a, a, 4, a, a, None, a, None, None)),
         ('null penalty buffer', 'clamd_adam_step_consolidated', (a, a, a, 4, a, a, a, None, None, None)),
+        ('no chunks', 'clamd_adam_step', (a, a, 0, a, a, a, None, None)),
+        ('no chunks', 'clamd_adam_step', (a, a, -1, a, a, a, None, None)),
+        ('null tensor or chunk table', 'clamd_adam_step', (None, a, 4, a, a, a, None, None)),
+        ('null tensor or chunk table', 'clamd_adam_step', (a, None, 4, a, a, a, None, None)),
+        ('null hyper / step / derived', 'clamd_adam_step', (a, a, 4, None, a, a, None, None)),
+        ('null hyper / step / derived', 'clamd_adam_step', (a, a, 4, a, None, a, None, None)),
+        ('null hyper / step / derived', 'clamd_adam_step', (a, a, 4, a, a, None, None, None)),
     ]
     for needle, name, args in cases:
         with pytest.raises(RuntimeError) as e:

@@ -1,4 +1,4 @@
-"""GPU: the fused SGD step (csrc/sgd.hip, optim.FusedSGD) -- per element against the float64 restatement of tests/sgd_ref.py across its
+"""GPU: the fused SGD step (csrc/optim.hip, optim.FusedSGD) -- per element against the float64 restatement of tests/sgd_ref.py across its
 grid of settings, the exact cases, a trajectory against torch.optim.SGD with checkpoints handed over both ways, the two penalty sums, a
 whole small UNet against the stock-torch module in float64, and the trainer with optimizer='sgd' and the per-iteration schedule."""
 import numpy as np
@@ -8,14 +8,12 @@ import torch.nn as nn
 
 import sgd_ref
 from conftest import rel_l2
-from grid_util import _per_element
+from grid_util import Banded, POISON, _per_element
 from oracle import torch_cpu as TC
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device('cuda', 0)
-POISON = 7.5
-GUARD = 64
 SIZES = (1, 3, 257, 4095, 4096, 8195)
 NO_DECAY = 2                                   # index of the tensor with decay_mult 0
 f32 = lambda v: float(np.float32(v))           # the value the kernel reads from its fp32 hyper buffer
@@ -26,36 +24,6 @@ def C():
     import continual_learning_amd as C
     C._lib.load()
     return C
-
-
-class Banded:
-    """Tensors of SIZES inside one flat poisoned buffer, tensor i starting at element phase phases[i] (mod 4) behind a guard band."""
-
-    def __init__(self, phases, values=None):
-        offs, cur = [], 0
-        for n, ph in zip(SIZES, phases):
-            start = (cur + 3) // 4 * 4 + GUARD + ph
-            offs.append(start)
-            cur = start + n
-        self.offs = offs
-        self.flat = torch.full((cur + GUARD + 3,), POISON, dtype=torch.float32, device=DEV)
-        assert self.flat.data_ptr() % 16 == 0
-        self.views = [self.flat[o:o + n] for o, n in zip(offs, SIZES)]
-        self.guard = torch.ones(self.flat.shape, dtype=torch.bool, device=DEV)
-        for o, n in zip(offs, SIZES):
-            self.guard[o:o + n] = False
-        if values is not None:
-            for v, x in zip(self.views, values):
-                v.copy_(x)
-        self.before = self.flat.clone()
-        for v, ph in zip(self.views, phases):
-            assert (v.data_ptr() // 4) % 4 == ph
-
-    def restore(self):
-        self.flat.copy_(self.before)
-
-    def guards_intact(self):
-        return bool(torch.equal(self.flat[self.guard].view(torch.int32), self.before[self.guard].view(torch.int32)))
 
 
 _INPUTS = {}
@@ -111,12 +79,12 @@ def test_sgd_step_per_element(C, mu, nesterov, wd, terms, gs):
     lr = 0.1
     l2_lam = 0.3 if terms in ('l2', 'both') else 0.0
     ewc_lam = 0.7 if terms in ('ewc', 'both') else 0.0
-    P = Banded((0, 0, 0, 1, 0, 0), inp['p'])
-    G = Banded((0, 1, 2, 3, 1, 2), inp['g'])
-    Bf = Banded((0, 3, 0, 0, 2, 1), inp['buf']) if mu > 0 else None
+    P = Banded(SIZES, (0, 0, 0, 1, 0, 0), inp['p'])
+    G = Banded(SIZES, (0, 1, 2, 3, 1, 2), inp['g'])
+    Bf = Banded(SIZES, (0, 3, 0, 0, 2, 1), inp['buf']) if mu > 0 else None
     anchored = terms != 'none'
-    old = Banded((1, 2, 0, 3, 0, 3), inp['old']).views if anchored else None
-    omega = Banded((2, 0, 1, 0, 0, 3), inp['omega']).views if ewc_lam else None
+    old = Banded(SIZES, (1, 2, 0, 3, 0, 3), inp['old']).views if anchored else None
+    omega = Banded(SIZES, (2, 0, 1, 0, 0, 3), inp['omega']).views if ewc_lam else None
     hyper = [lr, mu, wd, 1.0 if nesterov else 0.0, gs, l2_lam, ewc_lam, 0.0]
     ewc, l2 = _launch(C, P, G, Bf, old, omega, hyper, l2_lam > 0)
     got_p, got_b = P.flat.clone(), (Bf.flat.clone() if Bf is not None else None)
