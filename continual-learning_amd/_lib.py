@@ -142,6 +142,10 @@ SIGNATURES = {
     'clamd_importance_accum': (_I, [_P, _P, _I, _D, _D, _I, _P]),
     'clamd_sizeof_sgd_tensor': (_I, []),
     'clamd_sgd_step': (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    'clamd_adam_step_tracked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    'clamd_sgd_step_tracked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    'clamd_sizeof_path_tensor': (_I, []),
+    'clamd_path_importance': (_I, [_P, _P, _I, _D, _D, _P]),
     'clamd_argmax_confusion': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'clamd_voc_prepare': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'clamd_label_to_rgb': (_I, [_P, _P, _LL, _LL, _P]),

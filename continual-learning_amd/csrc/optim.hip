@@ -1,4 +1,5 @@
-// The multi-tensor passes: fused Adam (plain and with elastic weight consolidation), fused SGD and the importance accumulation.  All four
+// The multi-tensor passes: fused Adam (plain and with elastic weight consolidation), fused SGD, both with or without the path integral of
+// Synaptic Intelligence, the importance accumulation and the path integral's task boundary.  All
 // walk one job list of (tensor, ADAM_CHUNK-element chunk), one 256-thread workgroup per job, over a device table of per-tensor rows; they
 // share the job list, the pull towards an anchor, the fixed-order penalty sums and the host-side checks below.
 //
@@ -19,7 +20,12 @@
 // HBM-bound: 20 B / parameter with momentum (p, g, buf read; p, buf written), +4 B with an anchor, +4 B with importance, 12 B without
 // momentum.
 //
-// SGD and the importance pass use 16-byte accesses: a chunk is shifted by the tensor's `head` (elements up to the written tensor's first
+// Path integral (Synaptic Intelligence, Zenke et al. 2017; build-defined): the TRACK instantiations of both steps also do
+//   omega += -(grad * grad_scale) * (p_new - p_old)
+// with the gradient as it was handed over (before weight decay and the pulls) and the fp32 values read and stored: +8 B / parameter.  At a
+// task boundary path_importance_kernel turns it into importance = decay * importance + max(0, omega) / ((p - start)^2 + xi), 20 B / element.
+//
+// SGD and the two importance passes use 16-byte accesses: a chunk is shifted by the tensor's `head` (elements up to the written tensor's first
 // 16-byte boundary, peeled by chunk 0), so every vector store is aligned; the tensors that are only read may sit at any element phase (the
 // engine packs gradients tightly) and go through a 4-byte-aligned vector type (gfx9 global memory takes dword-aligned wide accesses).  The
 // last, partial group of a tensor goes element-wise.  Nothing outside [0, n) of any tensor is read or written.
@@ -47,6 +53,14 @@ __device__ __forceinline__ void anchor_pull(float p, float old, float om, float 
         g += lam * om * d;
         esum += om * (d * d);
     }
+}
+
+// The scaled gradient once more, for the path integral, from a copy of the raw gradient that the compiler cannot see through: the step's
+// own grad * scale gains no second use, so its expressions contract as they do in the untracked instantiation and tracking leaves the
+// step's results as they are.
+__device__ __forceinline__ float task_gradient(float grad, float gs) {
+    asm volatile("" : "+v"(grad));
+    return grad * gs;
 }
 
 // out[j][1 + block] = this workgroup's sum of v[j], for every non-null out[j].  No float atomics: one partial per workgroup (shuffle tree,
@@ -98,10 +112,12 @@ __global__ void adam_prepare_kernel(const float* hyper, int* step, float* derive
 }
 
 // Element i of one tensor.  EWC: the row has an anchor and `om` its importance; otherwise the anchor is optional and pulls uniformly.
-template <bool EWC>
-__device__ __forceinline__ void adam_element(const AdamTensor& t, const float* __restrict__ om, long long i, const AdamHyper& h,
-                                             float& l2sum, float& esum) {
-    float g = t.g[i] * h.gs;
+// TRACK: `path` is the row's path integral, which takes -(the scaled gradient) * (the stored value - the value read).
+template <bool EWC, bool TRACK>
+__device__ __forceinline__ void adam_element(const AdamTensor& t, const float* __restrict__ om, float* __restrict__ path, long long i,
+                                             const AdamHyper& h, float& l2sum, float& esum) {
+    const float grad = t.g[i];
+    float g = grad * h.gs;
     const float p = t.p[i];
     if (EWC) anchor_pull<true>(p, t.old[i], om[i], h.l2x2, h.lam, g, l2sum, esum);
     else if (t.old) anchor_pull<false>(p, t.old[i], 0.f, h.l2x2, h.lam, g, l2sum, esum);
@@ -110,19 +126,23 @@ __device__ __forceinline__ void adam_element(const AdamTensor& t, const float* _
     m = (h.w1 < 0.5f) ? m + h.w1 * (g - m) : g - (g - m) * (1.f - h.w1);
     v = v * h.b2 + (h.w2 * g) * g;
     const float denom = sqrtf(v) / h.bc2s + h.eps;
-    t.p[i] = p - h.step_size * (m / denom);
+    const float pn = p - h.step_size * (m / denom);
+    t.p[i] = pn;
     t.m[i] = m; t.v[i] = v;
+    if (TRACK) path[i] = path[i] - task_gradient(grad, h.gs) * (pn - p);
 }
 
-// EWC = false is what every step without consolidation launches (importance and ewc_accum null).  EWC = true: ewc_accum[1 + block] = this
-// workgroup's sum omega d^2; either way l2_accum[1 + block] (optional) = its sum d^2.
-template <bool EWC>
+// EWC = false, TRACK = false is what every step without consolidation and tracking launches (importance, path and ewc_accum null).
+// EWC = true: ewc_accum[1 + block] = this workgroup's sum omega d^2; either way l2_accum[1 + block] (optional) = its sum d^2.
+template <bool EWC, bool TRACK>
 __global__ void __launch_bounds__(256) adam_kernel(const AdamTensor* __restrict__ tensors, const float* const* __restrict__ importance,
-                                                   const AdamChunk* __restrict__ chunks, const float* __restrict__ hyper,
-                                                   const float* __restrict__ derived, float* ewc_accum, float* l2_accum) {
+                                                   float* const* __restrict__ paths, const AdamChunk* __restrict__ chunks,
+                                                   const float* __restrict__ hyper, const float* __restrict__ derived, float* ewc_accum,
+                                                   float* l2_accum) {
     const AdamChunk c = chunks[blockIdx.x];
     const AdamTensor t = tensors[c.tensor];
     const float* __restrict__ om = EWC ? importance[c.tensor] : nullptr;
+    float* __restrict__ path = TRACK ? paths[c.tensor] : nullptr;
     const float b1 = hyper[1], b2 = hyper[2];
     const AdamHyper h = {b2, hyper[3], hyper[4], 2.f * hyper[5], EWC ? hyper[6] : 0.f, derived[0], derived[1], 1.f - b1, 1.f - b2};
     const long long base = (long long)c.chunk * ADAM_CHUNK;
@@ -130,7 +150,7 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamTensor* __restrict_
 #pragma unroll 4
     for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
         const long long i = base + k * 256 + threadIdx.x;
-        if (i < t.n) adam_element<EWC>(t, om, i, h, l2sum, esum);
+        if (i < t.n) adam_element<EWC, TRACK>(t, om, path, i, h, l2sum, esum);
     }
     if (EWC) block_sums<2>({esum, l2sum}, {ewc_accum, l2_accum});
     else if (l2_accum) block_sums<1>({l2sum}, {l2_accum});
@@ -156,21 +176,25 @@ __device__ __forceinline__ float sgd_element(float p, float grad, float& buf, fl
     return p - h.lr * u;
 }
 
-// A thread issues the loads of all its four groups before the first store, so up to 20 16-byte loads per lane are in flight.
-template <bool BUF, bool OLD, bool OM>
-__device__ __forceinline__ void sgd_chunk(const SgdTensor& t, const float* __restrict__ om, int chunk, const SgdHyper& h, float& l2sum,
-                                          float& esum) {
+// A thread issues the loads of all its four groups before the first store, so up to 24 16-byte loads per lane are in flight.
+// TRACK: `pa` is the row's path integral; it takes -(grad * grad_scale) * (the stored value - the value read), outside sgd_element.
+template <bool BUF, bool OLD, bool OM, bool TRACK>
+__device__ __forceinline__ void sgd_chunk(const SgdTensor& t, const float* __restrict__ om, float* __restrict__ pa, int chunk,
+                                          const SgdHyper& h, float& l2sum, float& esum) {
     constexpr int GROUPS = ADAM_CHUNK / 1024;
     const int head = chunk_head(t.p);
     auto one = [&](long long i) {
         float b = BUF ? t.buf[i] : 0.f;
-        t.p[i] = sgd_element<BUF, OLD, OM>(t.p[i], t.g[i], b, OLD ? t.old[i] : 0.f, OM ? om[i] : 0.f, h, l2sum, esum);
+        const float p0 = t.p[i], gr = t.g[i];
+        const float p1 = sgd_element<BUF, OLD, OM>(p0, gr, b, OLD ? t.old[i] : 0.f, OM ? om[i] : 0.f, h, l2sum, esum);
+        t.p[i] = p1;
         if (BUF) t.buf[i] = b;
+        if (TRACK) pa[i] = pa[i] - task_gradient(gr, h.gs) * (p1 - p0);
     };
     if (chunk == 0 && (int)threadIdx.x < head && (long long)threadIdx.x < t.n) one(threadIdx.x);
     const long long base = (long long)chunk * ADAM_CHUNK + head;
     float4 p[GROUPS];
-    f32x4_a4 g[GROUPS], b[GROUPS], o[GROUPS], w[GROUPS];
+    f32x4_a4 g[GROUPS], b[GROUPS], o[GROUPS], w[GROUPS], a[GROUPS];
 #pragma unroll
     for (int k = 0; k < GROUPS; ++k) {
         const long long i = base + 4 * (k * 256 + (int)threadIdx.x);
@@ -180,6 +204,7 @@ __device__ __forceinline__ void sgd_chunk(const SgdTensor& t, const float* __res
             if (BUF) b[k] = *(const f32x4_a4*)(t.buf + i);
             if (OLD) o[k] = *(const f32x4_a4*)(t.old + i);
             if (OM) w[k] = *(const f32x4_a4*)(om + i);
+            if (TRACK) a[k] = *(const f32x4_a4*)(pa + i);
         }
     }
 #pragma unroll
@@ -194,33 +219,39 @@ __device__ __forceinline__ void sgd_chunk(const SgdTensor& t, const float* __res
             q.w = sgd_element<BUF, OLD, OM>(p[k].w, g[k].w, b3, OLD ? o[k].w : 0.f, OM ? w[k].w : 0.f, h, l2sum, esum);
             *(float4*)(t.p + i) = q;
             if (BUF) *(f32x4_a4*)(t.buf + i) = f32x4_a4{b0, b1, b2, b3};
+            if (TRACK)
+                *(f32x4_a4*)(pa + i) = f32x4_a4{a[k].x - task_gradient(g[k].x, h.gs) * (q.x - p[k].x),
+                                                a[k].y - task_gradient(g[k].y, h.gs) * (q.y - p[k].y),
+                                                a[k].z - task_gradient(g[k].z, h.gs) * (q.z - p[k].z),
+                                                a[k].w - task_gradient(g[k].w, h.gs) * (q.w - p[k].w)};
         } else {
             for (long long j = i; j < t.n; ++j) one(j);
         }
     }
 }
 
-// EWC: an importance table was given.  A row without an anchor takes neither pull, whatever the table says.
-template <bool EWC>
+// EWC: an importance table was given.  A row without an anchor takes neither pull, whatever the table says.  TRACK: a path table was given.
+template <bool EWC, bool TRACK>
 __global__ void __launch_bounds__(256) sgd_kernel(const SgdTensor* __restrict__ tensors, const float* const* __restrict__ importance,
-                                                  const AdamChunk* __restrict__ chunks, const float* __restrict__ hyper,
-                                                  float* ewc_accum, float* l2_accum) {
+                                                  float* const* __restrict__ paths, const AdamChunk* __restrict__ chunks,
+                                                  const float* __restrict__ hyper, float* ewc_accum, float* l2_accum) {
     const AdamChunk c = chunks[blockIdx.x];
     SgdTensor t = tensors[c.tensor];
     SgdHyper h;
     h.lr = hyper[0]; h.mu = hyper[1]; h.wd = hyper[2] * t.decay_mult; h.nesterov = hyper[3] != 0.f;
     h.gs = hyper[4]; h.l2x2 = 2.f * hyper[5]; h.lam = hyper[6];
     float l2sum = 0.f, esum = 0.f;
+    float* pa = TRACK ? paths[c.tensor] : nullptr;
     if (EWC && t.old) {
         const float* om = importance[c.tensor];
-        if (t.buf) sgd_chunk<true, true, true>(t, om, c.chunk, h, l2sum, esum);
-        else sgd_chunk<false, true, true>(t, om, c.chunk, h, l2sum, esum);
+        if (t.buf) sgd_chunk<true, true, true, TRACK>(t, om, pa, c.chunk, h, l2sum, esum);
+        else sgd_chunk<false, true, true, TRACK>(t, om, pa, c.chunk, h, l2sum, esum);
     } else if (t.old) {
-        if (t.buf) sgd_chunk<true, true, false>(t, nullptr, c.chunk, h, l2sum, esum);
-        else sgd_chunk<false, true, false>(t, nullptr, c.chunk, h, l2sum, esum);
+        if (t.buf) sgd_chunk<true, true, false, TRACK>(t, nullptr, pa, c.chunk, h, l2sum, esum);
+        else sgd_chunk<false, true, false, TRACK>(t, nullptr, pa, c.chunk, h, l2sum, esum);
     } else {
-        if (t.buf) sgd_chunk<true, false, false>(t, nullptr, c.chunk, h, l2sum, esum);
-        else sgd_chunk<false, false, false>(t, nullptr, c.chunk, h, l2sum, esum);
+        if (t.buf) sgd_chunk<true, false, false, TRACK>(t, nullptr, pa, c.chunk, h, l2sum, esum);
+        else sgd_chunk<false, false, false, TRACK>(t, nullptr, pa, c.chunk, h, l2sum, esum);
     }
     if (EWC || l2_accum) block_sums<2>({esum, l2sum}, {EWC ? ewc_accum : nullptr, l2_accum});
 }
@@ -258,6 +289,41 @@ __global__ void __launch_bounds__(256) importance_accum_kernel(const ImportanceT
     }
 }
 
+// The task boundary of the path integral: importance = decay * importance + max(0, path) / ((p - start)^2 + xi).  path, p and start are
+// only read.  20 B / element.
+struct PathTensor { float* importance; const float* path; const float* p; const float* start; long long n; };
+static_assert(sizeof(PathTensor) == 40, "the host side builds 40-byte rows");
+
+__device__ __forceinline__ float path_importance(float imp, float path, float p, float start, float decay, float xi) {
+    const float d = p - start;
+    return decay * imp + fmaxf(path, 0.f) / (d * d + xi);
+}
+
+__global__ void __launch_bounds__(256) path_importance_kernel(const PathTensor* __restrict__ tensors, const AdamChunk* __restrict__ chunks,
+                                                              float decay, float xi) {
+    const AdamChunk c = chunks[blockIdx.x];
+    const PathTensor t = tensors[c.tensor];
+    const int head = chunk_head(t.importance);
+    auto one = [&](long long i) { t.importance[i] = path_importance(t.importance[i], t.path[i], t.p[i], t.start[i], decay, xi); };
+    if (c.chunk == 0 && (int)threadIdx.x < head && (long long)threadIdx.x < t.n) one(threadIdx.x);
+    const long long base = (long long)c.chunk * ADAM_CHUNK + head;
+#pragma unroll
+    for (int k = 0; k < ADAM_CHUNK / 1024; ++k) {
+        const long long i = base + 4 * (k * 256 + (int)threadIdx.x);
+        if (i + 4 <= t.n) {
+            const f32x4_a4 a = *(const f32x4_a4*)(t.path + i), p = *(const f32x4_a4*)(t.p + i), s = *(const f32x4_a4*)(t.start + i);
+            float4 w = *(const float4*)(t.importance + i);
+            w.x = path_importance(w.x, a.x, p.x, s.x, decay, xi);
+            w.y = path_importance(w.y, a.y, p.y, s.y, decay, xi);
+            w.z = path_importance(w.z, a.z, p.z, s.z, decay, xi);
+            w.w = path_importance(w.w, a.w, p.w, s.w, decay, xi);
+            *(float4*)(t.importance + i) = w;
+        } else {
+            for (long long j = i; j < t.n; ++j) one(j);
+        }
+    }
+}
+
 }  // namespace clamd
 
 using namespace clamd;
@@ -275,21 +341,58 @@ static void launch_partial_sum(float* accum, int n, hipStream_t s) {
     hipLaunchKernelGGL(adam_l2_final_kernel, dim3(1), dim3(256), 0, s, accum, n);
 }
 
-// both Adam entry points: importance_dev selects the instantiation
-static int launch_adam(const char* what, const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks,
-                       const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev, void* stream) {
+// the three Adam entry points: importance_dev and path_dev select the instantiation
+template <bool EWC, bool TRACK>
+static void launch_adam_kernel(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                               const float* hyper_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev, hipStream_t s) {
+    hipLaunchKernelGGL((adam_kernel<EWC, TRACK>), dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors_dev,
+                       (const float* const*)importance_dev, (float* const*)path_dev, (const AdamChunk*)chunks_dev, hyper_dev, derived_dev,
+                       ewc_accum_dev, l2_accum_dev);
+}
+
+static int launch_adam(const char* what, const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev,
+                       int nchunks, const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev,
+                       void* stream) {
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, hyper_dev, step_dev, derived_dev);
-    if (importance_dev) {
-        hipLaunchKernelGGL(adam_kernel<true>, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors_dev,
-                           (const float* const*)importance_dev, (const AdamChunk*)chunks_dev, hyper_dev, derived_dev, ewc_accum_dev, l2_accum_dev);
-        launch_partial_sum(ewc_accum_dev, nchunks, s);
-    } else {
-        hipLaunchKernelGGL(adam_kernel<false>, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors_dev,
-                           (const float* const*)nullptr, (const AdamChunk*)chunks_dev, hyper_dev, derived_dev, (float*)nullptr, l2_accum_dev);
-    }
+    auto launch = importance_dev ? (path_dev ? launch_adam_kernel<true, true> : launch_adam_kernel<true, false>)
+                                 : (path_dev ? launch_adam_kernel<false, true> : launch_adam_kernel<false, false>);
+    launch(tensors_dev, importance_dev, path_dev, chunks_dev, nchunks, hyper_dev, derived_dev, importance_dev ? ewc_accum_dev : nullptr,
+           l2_accum_dev, s);
+    if (importance_dev) launch_partial_sum(ewc_accum_dev, nchunks, s);
     if (l2_accum_dev) launch_partial_sum(l2_accum_dev, nchunks, s);
     return clamd_check_launch(what);
+}
+
+// both SGD entry points, after their checks
+template <bool EWC, bool TRACK>
+static void launch_sgd_kernel(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                              const float* hyper_dev, float* ewc_accum_dev, float* l2_accum_dev, hipStream_t s) {
+    hipLaunchKernelGGL((sgd_kernel<EWC, TRACK>), dim3(nchunks), dim3(256), 0, s, (const SgdTensor*)tensors_dev,
+                       (const float* const*)importance_dev, (float* const*)path_dev, (const AdamChunk*)chunks_dev, hyper_dev, ewc_accum_dev,
+                       l2_accum_dev);
+}
+
+static int launch_sgd(const char* what, const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev,
+                      int nchunks, const float* hyper_dev, float* ewc_accum_dev, float* l2_accum_dev, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    auto launch = importance_dev ? (path_dev ? launch_sgd_kernel<true, true> : launch_sgd_kernel<true, false>)
+                                 : (path_dev ? launch_sgd_kernel<false, true> : launch_sgd_kernel<false, false>);
+    launch(tensors_dev, importance_dev, path_dev, chunks_dev, nchunks, hyper_dev, importance_dev ? ewc_accum_dev : nullptr, l2_accum_dev, s);
+    if (importance_dev) launch_partial_sum(ewc_accum_dev, nchunks, s);
+    if (l2_accum_dev) launch_partial_sum(l2_accum_dev, nchunks, s);
+    return clamd_check_launch(what);
+}
+
+// the checks of the two SGD entry points behind check_jobs
+static int check_sgd(const char* who, const float* hyper_dev, const void* importance_dev, const float* ewc_accum_dev) {
+    const char* what = !hyper_dev ? "null hyper buffer"
+                       : (importance_dev && !ewc_accum_dev) ? "an importance table needs a penalty buffer (1 + nchunks floats)"
+                       : (!importance_dev && ewc_accum_dev) ? "a consolidation penalty buffer without an importance table" : nullptr;
+    if (!what) return 0;
+    char msg[128];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return clamd_fail(msg);
 }
 
 extern "C" {
@@ -303,7 +406,8 @@ int clamd_adam_step(const void* tensors_dev, const void* chunks_dev, int nchunks
                     float* derived_dev, float* l2_accum_dev, void* stream) {
     if (int e = check_jobs("adam", tensors_dev, chunks_dev, nchunks)) return e;
     if (!hyper_dev || !step_dev || !derived_dev) return clamd_fail("adam: null hyper / step / derived buffer");
-    return launch_adam("adam_step", tensors_dev, nullptr, chunks_dev, nchunks, hyper_dev, step_dev, derived_dev, nullptr, l2_accum_dev, stream);
+    return launch_adam("adam_step", tensors_dev, nullptr, nullptr, chunks_dev, nchunks, hyper_dev, step_dev, derived_dev, nullptr, l2_accum_dev,
+                       stream);
 }
 
 int clamd_adam_step_consolidated(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks,
@@ -313,27 +417,48 @@ int clamd_adam_step_consolidated(const void* tensors_dev, const void* importance
     if (!importance_dev) return clamd_fail("adam_step_consolidated: null importance table");
     if (!hyper_dev || !step_dev || !derived_dev) return clamd_fail("adam_step_consolidated: null hyper / step / derived buffer");
     if (!ewc_accum_dev) return clamd_fail("adam_step_consolidated: null penalty buffer (1 + nchunks floats)");
-    return launch_adam("adam_step_consolidated", tensors_dev, importance_dev, chunks_dev, nchunks, hyper_dev, step_dev, derived_dev,
+    return launch_adam("adam_step_consolidated", tensors_dev, importance_dev, nullptr, chunks_dev, nchunks, hyper_dev, step_dev, derived_dev,
+                       ewc_accum_dev, l2_accum_dev, stream);
+}
+
+int clamd_adam_step_tracked(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                            const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev,
+                            void* stream) {
+    if (int e = check_jobs("adam_step_tracked", tensors_dev, chunks_dev, nchunks)) return e;
+    if (!path_dev) return clamd_fail("adam_step_tracked: null path table");
+    if (!hyper_dev || !step_dev || !derived_dev) return clamd_fail("adam_step_tracked: null hyper / step / derived buffer");
+    if (importance_dev && !ewc_accum_dev)
+        return clamd_fail("adam_step_tracked: an importance table needs a penalty buffer (1 + nchunks floats)");
+    if (!importance_dev && ewc_accum_dev) return clamd_fail("adam_step_tracked: a consolidation penalty buffer without an importance table");
+    return launch_adam("adam_step_tracked", tensors_dev, importance_dev, path_dev, chunks_dev, nchunks, hyper_dev, step_dev, derived_dev,
                        ewc_accum_dev, l2_accum_dev, stream);
 }
 
 int clamd_sgd_step(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks, const float* hyper_dev,
                    float* ewc_accum_dev, float* l2_accum_dev, void* stream) {
     if (int e = check_jobs("sgd_step", tensors_dev, chunks_dev, nchunks)) return e;
-    if (!hyper_dev) return clamd_fail("sgd_step: null hyper buffer");
-    if (importance_dev && !ewc_accum_dev) return clamd_fail("sgd_step: an importance table needs a penalty buffer (1 + nchunks floats)");
-    if (!importance_dev && ewc_accum_dev) return clamd_fail("sgd_step: a consolidation penalty buffer without an importance table");
-    hipStream_t s = (hipStream_t)stream;
-    if (importance_dev) {
-        hipLaunchKernelGGL(sgd_kernel<true>, dim3(nchunks), dim3(256), 0, s, (const SgdTensor*)tensors_dev,
-                           (const float* const*)importance_dev, (const AdamChunk*)chunks_dev, hyper_dev, ewc_accum_dev, l2_accum_dev);
-        launch_partial_sum(ewc_accum_dev, nchunks, s);
-    } else {
-        hipLaunchKernelGGL(sgd_kernel<false>, dim3(nchunks), dim3(256), 0, s, (const SgdTensor*)tensors_dev,
-                           (const float* const*)nullptr, (const AdamChunk*)chunks_dev, hyper_dev, (float*)nullptr, l2_accum_dev);
-    }
-    if (l2_accum_dev) launch_partial_sum(l2_accum_dev, nchunks, s);
-    return clamd_check_launch("sgd_step");
+    if (int e = check_sgd("sgd_step", hyper_dev, importance_dev, ewc_accum_dev)) return e;
+    return launch_sgd("sgd_step", tensors_dev, importance_dev, nullptr, chunks_dev, nchunks, hyper_dev, ewc_accum_dev, l2_accum_dev, stream);
+}
+
+int clamd_sgd_step_tracked(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                           const float* hyper_dev, float* ewc_accum_dev, float* l2_accum_dev, void* stream) {
+    if (int e = check_jobs("sgd_step_tracked", tensors_dev, chunks_dev, nchunks)) return e;
+    if (!path_dev) return clamd_fail("sgd_step_tracked: null path table");
+    if (int e = check_sgd("sgd_step_tracked", hyper_dev, importance_dev, ewc_accum_dev)) return e;
+    return launch_sgd("sgd_step_tracked", tensors_dev, importance_dev, path_dev, chunks_dev, nchunks, hyper_dev, ewc_accum_dev, l2_accum_dev,
+                      stream);
+}
+
+int clamd_sizeof_path_tensor(void) { return (int)sizeof(PathTensor); }
+
+int clamd_path_importance(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double xi, void* stream) {
+    if (int e = check_jobs("path_importance", tensors_dev, chunks_dev, nchunks)) return e;
+    if (!(decay >= 0.0) || !(decay <= 3.0e38)) return clamd_fail("path_importance: decay must be finite and >= 0");
+    if (!(xi > 0.0) || !(xi <= 3.0e38) || !((float)xi > 0.f)) return clamd_fail("path_importance: xi must be finite and > 0 (in fp32)");
+    hipLaunchKernelGGL(path_importance_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const PathTensor*)tensors_dev,
+                       (const AdamChunk*)chunks_dev, (float)decay, (float)xi);
+    return clamd_check_launch("path_importance");
 }
 
 int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double scale, int power, void* stream) {

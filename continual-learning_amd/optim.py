@@ -13,6 +13,10 @@ Optional elastic weight consolidation (build-defined as well): ``set_consolidati
 lam*omega*(theta - theta_old); such a step runs ``clamd_adam_step_consolidated`` (36 B / parameter), every other step
 ``clamd_adam_step``.
 
+Optional path integral of Synaptic Intelligence (build-defined too): ``set_path_integral(omega)`` makes every step also accumulate
+omega += -(grad * grad_scale) * (theta_new - theta_old) inside the same kernel (``clamd_adam_step_tracked`` / ``clamd_sgd_step_tracked``,
++8 B / parameter); without it the step launches what it always did.
+
 ``FusedSGD`` is the second optimiser: torch.optim.SGD with momentum, Nesterov and weight decay in one launch of ``clamd_sgd_step``.  Both
 are a ``_FusedOptimizer``, which owns everything they do alike: the step protocol, the device tables, the two anchor terms, head growth
 and checkpoints.  A subclass says how one table row is filled, which eight hyper-parameters it uploads, how its state is laid out in flat
@@ -46,6 +50,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._importance = None
         self._ewc_lambda = 0.0
         self._ewcacc = None
+        self._path = None             # per-parameter path integrals (Synaptic Intelligence): the step launches the tracked entry point
+        self._path_dev = None
 
     # -- the step ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -86,6 +92,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
         if self._importance is not None:
             self._importance_dev = torch.tensor([w.data_ptr() for w in self._importance], dtype=torch.int64).to(dev)
             self._ewcacc = torch.zeros(1 + self._nchunks, dtype=torch.float32, device=dev)
+        self._path_dev = None
+        if self._path is not None:
+            for i, (p, w) in enumerate(zip(params, self._path)):
+                if w.device != p.device:
+                    raise RuntimeError(f'{self._NAME}: path integral {i} is on {w.device}, its parameter on {p.device}')
+            self._path_dev = torch.tensor([w.data_ptr() for w in self._path], dtype=torch.int64).to(dev)
 
     def sync_hyper(self):
         """Upload the eight hyper-parameters (learning rate, ..., gradient scale, L2 and consolidation weights) to device memory if they
@@ -121,7 +133,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         mapping: {old_param: new_param}; new_param has more rows along dim 0 and the same trailing shape (anything else: ValueError).
         The state of the leading rows is kept, the new rows start at zero, a shared step counter stays.  The L2 / consolidation anchor of
         the new rows is their current (initial) value and their importance zero: nothing pulls on classes the finished task never had.
-        The importance list is replaced (grown copies); a Consolidation re-installs its own views after Consolidation.grow.  Flat state
+        The importance list is replaced (grown copies); a Consolidation re-installs its own views after Consolidation.grow.  The path
+        integrals grow the same way (old rows kept, new rows zero); a PathIntegral re-installs its views after PathIntegral.grow.  Flat state
         and device tables are laid out again at the next step."""
         params = self.param_groups[0]['params']
         index = {id(p): i for i, p in enumerate(params)}
@@ -142,6 +155,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 self._anchor[i] = self._grown(self._anchor[i], new.shape, new.detach().float())
             if self._importance is not None:
                 self._importance[i] = self._grown(self._importance[i], new.shape, None)
+            if self._path is not None:
+                self._path[i] = self._grown(self._path[i], new.shape, None)
             self.state.pop(old, None)
             params[i] = new
         for p, st in zip(params, states):
@@ -219,6 +234,31 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._table = None
         self._hyper_host = None
 
+    # -- the path integral (Synaptic Intelligence) -----------------------------------------------------------
+    def set_path_integral(self, omega):
+        """Synaptic Intelligence (Zenke et al. 2017): every step also does omega += -(grad * grad_scale) * (theta_new - theta_old) inside
+        the optimiser's kernel, with the gradient as it is handed over (before weight decay and both pulls) -- +8 B / parameter.
+        omega: list of contiguous fp32 tensors aligned with this optimiser's parameters (same shapes, on their device), written in place: a
+        consolidate.PathIntegral owns them.  None switches tracking off: the step then launches exactly what it launched before.  omega
+        is not optimiser state (state_dict() is unchanged); it composes with set_l2_anchor and set_consolidation in any order."""
+        if omega is None:
+            self._path = None
+            self._table = None
+            return
+        params = self.param_groups[0]['params']
+        omega = list(omega)
+        if len(omega) != len(params):
+            raise ValueError(f'{self._NAME}.set_path_integral: {len(params)} parameters, {len(omega)} path tensors')
+        for i, (p, w) in enumerate(zip(params, omega)):
+            if w.shape != p.shape:
+                raise ValueError(f'{self._NAME}.set_path_integral: parameter {i} has shape {tuple(p.shape)}, path {tuple(w.shape)}')
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                raise ValueError(f'{self._NAME}.set_path_integral: path {i} must be contiguous fp32')
+            if w.device != p.device:
+                raise ValueError(f'{self._NAME}.set_path_integral: parameter {i} is on {p.device}, path on {w.device}')
+        self._path = [w.detach() for w in omega]
+        self._table = None
+
     def consolidation_penalty(self):
         """(lam / 2) * sum importance * (theta - theta_old)^2 as accumulated by the LAST step (device scalar)."""
         if self._ewcacc is None:
@@ -284,7 +324,14 @@ class FusedAdam(_FusedOptimizer):
     def _launch(self):
         from . import unet as U
         l2acc = ptr(self._l2acc) if self._l2_on else None
-        if self._importance is not None:
+        ewc = self._importance is not None
+        if self._path is not None:
+            # the plain step's 28 B, the path integral read and written, the anchor and the importance read
+            U._hbm('adam', (36 + (8 if ewc else 4 if self._anchor is not None else 0)) * self._numel,
+                   'clamd_adam_step_tracked', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None, ptr(self._path_dev),
+                   ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._step_dev), ptr(self._derived),
+                   ptr(self._ewcacc) if ewc else None, l2acc, _lib.stream_ptr())
+        elif ewc:
             U._hbm('adam', 36 * self._numel,      # p, g, m, v, old, importance read; p, m, v written
                    'clamd_adam_step_consolidated', ptr(self._tensors_dev), ptr(self._importance_dev), ptr(self._chunks_dev), self._nchunks,
                    ptr(self._hyper), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc), l2acc, _lib.stream_ptr())
@@ -383,6 +430,10 @@ class FusedSGD(_FusedOptimizer):
         ewc = self._importance is not None
         # p, g read and p written; buf read and written; the anchor and the importance read
         per_param = 12 + (8 if self._with_momentum else 0) + (4 if self._anchor is not None else 0) + (4 if ewc else 0)
-        U._hbm('sgd', per_param * self._numel, 'clamd_sgd_step', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None,
-               ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._ewcacc) if ewc else None,
-               ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
+        tail = (ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._ewcacc) if ewc else None,
+                ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
+        if self._path is not None:      # the path integral read and written on top
+            U._hbm('sgd', (per_param + 8) * self._numel, 'clamd_sgd_step_tracked', ptr(self._tensors_dev),
+                   ptr(self._importance_dev) if ewc else None, ptr(self._path_dev), *tail)
+        else:
+            U._hbm('sgd', per_param * self._numel, 'clamd_sgd_step', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None, *tail)

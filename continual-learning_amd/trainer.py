@@ -14,7 +14,9 @@ Out of scope here: JPEG dumps, prints, checkpoint file
 Continual learning (config 4): ``begin_task2(c_old, ...)`` snapshots the model and switches the criterion to
 DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined); ``freeze_bn=True`` also trains task 2 with
 every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0`` estimates the finished task's per-parameter importance
-(``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py).
+(``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py);
+``cfg.path_integral=True`` tracks Synaptic Intelligence's path integral inside every optimiser step from the first one
+(consolidate.PathIntegral, ``self.path``) and ``begin_task2(si_lambda=c)`` consolidates with it instead of the Fisher estimate.
 Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
 of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
 confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`` adds Local POD distillation of the logits (build-defined,
@@ -38,7 +40,7 @@ from torch.optim.lr_scheduler import LambdaLR
 from .loss import CrossEntropyLoss, DiceCrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam, FusedSGD
-from .consolidate import Consolidation
+from .consolidate import Consolidation, PathIntegral
 from .pseudo import PseudoLabeler
 from .pod import LocalPODLoss
 from .replay import ReplayMemory
@@ -53,7 +55,7 @@ def default_config(**kw):
                w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False,
                augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0,
                optimizer='adam', momentum=0.9, nesterov=True, weight_decay=1e-4, decay_norm_and_bias=True, lr_schedule='epoch',
-               max_iters=None,
+               max_iters=None, path_integral=False, si_xi=0.1,
                loss='ce', dice_weight=1.0, dice_smooth=1e-5, dice_include_background=True, dice_present_only=True, dice_per_image=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
@@ -109,6 +111,7 @@ class Trainer:
         self.pod_channels = 0
         self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
         self.ewc_lambda = 0.0
+        self.path = None                  # consolidate.PathIntegral when cfg.path_integral is set (build_model): tracked from the first step
         self.replay = None                # replay.ReplayMemory once begin_task2(replay > 0) ran
         self.replay_batch = 0             # exemplars mixed into every batch
         self.replay_boundary = None       # c_old of the last call that added a segment: the next segment's first class
@@ -138,6 +141,10 @@ class Trainer:
                                   no_decay=no_decay)
         else:
             raise ValueError(f"optimizer must be 'adam' or 'sgd', not {kind!r}")
+        self.path = None
+        if getattr(cfg, 'path_integral', False):     # Synaptic Intelligence has to watch task 1: tracking is on from the first step
+            self.path = PathIntegral(self.model.named_parameters(), xi=getattr(cfg, 'si_xi', 0.1))
+            self.optim.set_path_integral(self.path.omega)
         self.per_iteration = getattr(cfg, 'lr_schedule', 'epoch') == 'iteration'
         loader = self.train_data_loader
         self.scheduler = make_scheduler(self.optim, cfg, len(loader) if self.per_iteration and hasattr(loader, '__len__') else None)
@@ -194,7 +201,7 @@ class Trainer:
                     importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background',
                     pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None,
                     pod_lambda=0.0, pod_levels=3, replay=0, replay_batch=0, replay_loader=None, replay_storage='uint8', replay_flip=True,
-                    replay_min_pixels=1, replay_seed=0):
+                    replay_min_pixels=1, replay_seed=0, si_lambda=0.0):
         """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
         trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
         still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
@@ -226,7 +233,20 @@ class Trainer:
         B + replay_batch rows, and so do the returned outputs; the caller's batch is rows [0, B).  replay == 0 leaves a memory from earlier
         calls (and its replay_batch, unless a new one >= 1 is given) in place and adds nothing.  Data parallelism: each rank keeps its own
         memory, filled from its own shard and sampled with replay_seed + rank; the gradients are averaged as always, no collective is
-        added."""
+        added.
+        Synaptic Intelligence (build-defined, consolidate.PathIntegral): si_lambda = c > 0 needs cfg.path_integral (the optimiser has been
+        accumulating omega since the first step) and is refused together with ewc_lambda > 0 (one importance buffer; the combination is
+        Riemannian Walk).  Where the EWC estimate would run, the path integral of the finished task becomes a Consolidation -- importance
+        <- previous + max(0, omega) / ((theta - theta_start)^2 + si_xi), anchor = the current weights --, omega and theta_start restart, and
+        the consolidation term runs with ewc_lambda = 2 c: consolidation_penalty() is c * sum Omega (theta - theta*)^2.  It composes with
+        everything ewc_lambda composes with; si_lambda == 0 leaves an earlier consolidation in place; tracking goes on for the next boundary."""
+        if not si_lambda >= 0:
+            raise ValueError('si_lambda must be >= 0')
+        if si_lambda > 0 and getattr(self, 'path', None) is None:
+            raise ValueError('si_lambda > 0 needs cfg.path_integral=True: the path integral has to be tracked from the first step of the task')
+        if si_lambda > 0 and ewc_lambda > 0:
+            raise ValueError('si_lambda > 0 with ewc_lambda > 0: there is one importance buffer (the combination, Riemannian Walk, is not '
+                             'provided)')
         if replay < 0 or replay_batch < 0:
             raise ValueError('replay and replay_batch must be >= 0')
         if replay > 0 and replay_batch < 1:
@@ -264,6 +284,11 @@ class Trainer:
             if self.consolidation is not None:
                 cons.merge_from(self.consolidation, ewc_gamma)
             self.consolidation, self.ewc_lambda = cons, float(ewc_lambda)
+        if si_lambda > 0:
+            self.consolidation = self.path.consolidate(self.model.named_parameters(), previous=self.consolidation)
+            self.path.restart(self.model.parameters())
+            self.ewc_lambda = 2.0 * float(si_lambda)
+        consolidated = ewc_lambda > 0 or si_lambda > 0
         # a fresh module with a CLONE of the state (not copy.deepcopy: that would duplicate the engine's multi-GB activation
         # buffers and, under data parallelism, the GradSync object with its process group and stream)
         m = self.model
@@ -284,11 +309,11 @@ class Trainer:
                                         ignore_index=self.c_loss.ignore_index)
             group = m.grad_sync.group if getattr(m, 'grad_sync', None) is not None else None
             self.pseudo.calibrate(self.old_model, self.train_data_loader if pseudo_loader is None else pseudo_loader, self.device, group=group)
-        if ewc_lambda > 0:
+        if consolidated:
             self.optim.set_l2_anchor(None, 0.0)        # an earlier task's L2 anchor is another snapshot than the new consolidation anchor
             self._apply_consolidation()
         if l2_lambda > 0:
-            self.optim.set_l2_anchor(self.consolidation.anchor if ewc_lambda > 0 else [p.detach().clone() for p in self.old_model.parameters()],
+            self.optim.set_l2_anchor(self.consolidation.anchor if consolidated else [p.detach().clone() for p in self.old_model.parameters()],
                                      l2_lambda)
         if new_classes > 0:
             self.grow_head(new_classes, head_init)
@@ -335,7 +360,12 @@ class Trainer:
         if self.consolidation is not None:
             self.consolidation.grow(names[id(ow)], nw)
             self.consolidation.grow(names[id(ob)], nb)
+        if self.path is not None:      # the same order for the path integral: its own buffers first, then the optimiser reads the new views
+            self.path.grow(names[id(ow)], nw, ow)     # the old parameters too: start follows what the initialisation does to old rows
+            self.path.grow(names[id(ob)], nb, ob)
         self.optim.replace_params({ow: nw, ob: nb})
+        if self.path is not None:
+            self.optim.set_path_integral(self.path.omega)
         if self.consolidation is not None and self.ewc_lambda > 0:
             l2 = self.optim.l2_lambda
             self.optim.set_l2_anchor(None, 0.0)
@@ -372,6 +402,11 @@ class Trainer:
                 cons_host = {'anchor': {n: t.to('cpu', non_blocking=True) for n, t in cs['anchor'].items()},
                              'importance': {n: t.to('cpu', non_blocking=True) for n, t in cs['importance'].items()},
                              'lambda': self.ewc_lambda, 'gamma': cs['gamma'], 'n_batches': cs['n_batches']}
+            path_host = None
+            if self.path is not None:                # one more optional key: the running path integral and the task's starting weights
+                ps = self.path.state_dict()
+                path_host = {'omega': {n: t.to('cpu', non_blocking=True) for n, t in ps['omega'].items()},
+                             'start': {n: t.to('cpu', non_blocking=True) for n, t in ps['start'].items()}, 'xi': ps['xi']}
             replay_host = None
             if self.replay is not None:              # a second optional key
                 rs = self.replay.state_dict()
@@ -383,6 +418,8 @@ class Trainer:
                 'scheduler_state': self.scheduler.state_dict(), '_event': done}
         if cons_host is not None:
             snap['consolidation_state'] = cons_host
+        if path_host is not None:
+            snap['path_state'] = path_host
         if replay_host is not None:
             snap['replay_state'] = replay_host
         if self.augment is not None:                 # a third optional key: the configuration and the generator state (a host tensor)
@@ -394,7 +431,8 @@ class Trainer:
         scheduler_state (loadable by the reference's load_network and by torch.optim.Adam); with elastic weight consolidation
         active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores; with an exemplar memory
         replay_state (ReplayMemory.state_dict() on the host, replay_batch and the class boundary), ignored by the reference too; with
-        augmentation augment_state (RandomScaleCrop.state_dict(): configuration and generator state), likewise."""
+        augmentation augment_state (RandomScaleCrop.state_dict(): configuration and generator state), likewise; with cfg.path_integral
+        path_state (PathIntegral.state_dict(): omega and the task's starting weights by name, and xi), likewise."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -414,9 +452,20 @@ class Trainer:
         self.optim.load_state_dict(ck['optimizer_state'])
         self.scheduler.load_state_dict(ck['scheduler_state'])
         self.load_consolidation_state(ck.get('consolidation_state'))
+        self.load_path_state(ck.get('path_state'))
         self.load_replay_state(ck.get('replay_state'))
         self.load_augment_state(ck.get('augment_state'))
         return True
+
+    def load_path_state(self, state):
+        """Restores what snapshot() stored under 'path_state' (None, e.g. a checkpoint without the key: nothing changes -- a path integral
+        built by cfg.path_integral stays as built).  A trainer without one starts tracking with the restored state."""
+        if state is None:
+            return
+        if self.path is None:
+            self.path = PathIntegral(self.model.named_parameters(), xi=state['xi'])
+        self.path.load_state_dict(state)
+        self.optim.set_path_integral(self.path.omega)
 
     def load_augment_state(self, state):
         """Restores what snapshot() stored under 'augment_state' (None, e.g. a checkpoint without the key: nothing changes): the next step

@@ -616,6 +616,30 @@ int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int 
 int clamd_sizeof_sgd_tensor(void);
 int clamd_sgd_step(const void* tensors_dev, const void* importance_dev, const void* chunks_dev, int nchunks, const float* hyper_dev,
                    float* ewc_accum_dev, float* l2_accum_dev, void* stream);
+/* Synaptic Intelligence (Zenke et al. 2017; build-defined like the two pulls): the steps above with the path integral accumulated in the
+ * same launch.  Per element, on top of clamd_adam_step[_consolidated] / clamd_sgd_step:
+ *   omega += -(grad * grad_scale) * (p_new - p_old)
+ * with the gradient as handed over -- before weight decay and both pulls -- and the fp32 values the kernel read and stored, so the
+ * per-step differences telescope to theta_end - theta_start.  path_dev (required): device array of one `float*` per table row, omega of
+ * the row's shape, read and written with 4-byte alignment only; nothing outside [0, n) of a row is touched.  importance_dev (optional):
+ * as in clamd_adam_step_consolidated (every row then needs an anchor) / clamd_sgd_step, with ewc_accum_dev required beside it and refused
+ * without it; l2_accum_dev optional.  The row structs are unchanged.  Adam 36 B / parameter (44 B with importance); SGD 28 B with
+ * momentum, 20 B without, +4 B with an anchor, +4 B with importance.  p, m, v / buf and the penalty sums are what the untracked entry
+ * points compute (to rounding where the compiler may contract differently).  Enqueue only: no allocation, no synchronisation, no atomics,
+ * no process state. */
+int clamd_adam_step_tracked(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                            const float* hyper_dev, int* step_dev, float* derived_dev, float* ewc_accum_dev, float* l2_accum_dev,
+                            void* stream);
+int clamd_sgd_step_tracked(const void* tensors_dev, const void* importance_dev, const void* path_dev, const void* chunks_dev, int nchunks,
+                           const float* hyper_dev, float* ewc_accum_dev, float* l2_accum_dev, void* stream);
+/* The task boundary of the path integral: importance = decay * importance + max(0, path) / ((p - start)^2 + xi) over every tensor of a
+ * device table of clamd_sizeof_path_tensor()-byte rows {float* importance; const float* path; const float* p; const float* start; long
+ * long n}, in ONE launch through the (tensor, chunk) job list of clamd_importance_accum.  path, p and start are only read.  decay must be
+ * finite and >= 0 (1: Zenke's running sum), xi finite and > 0 (also as fp32).  20 B / element; every pointer needs 4-byte alignment only
+ * (16-byte accesses from importance's first 16-byte boundary).  Enqueue only: no allocation, no synchronisation, no atomics; element-wise,
+ * so bit-reproducible. */
+int clamd_sizeof_path_tensor(void);
+int clamd_path_importance(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double xi, void* stream);
 /* argmax over classes + confusion matrix (trainer.py:183-188, metrics.py:32-38). */
 int clamd_argmax_confusion(const float* logits, const long long* labels, long long* pred, unsigned long long* conf,
                            int B, int K, int Kc, int H, int W, void* stream);
