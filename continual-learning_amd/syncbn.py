@@ -22,6 +22,11 @@ def initialized():
     return dist.is_available() and dist.is_initialized()
 
 
+def rank():
+    """This process's rank in the default group; 0 while no process group is initialised."""
+    return dist.get_rank() if initialized() else 0
+
+
 def bn_group():
     """The dedicated group over the world for the BatchNorm sums of modules whose process_group is None (made again after the
     default group was destroyed and initialised anew)."""

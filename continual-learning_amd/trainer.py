@@ -3,32 +3,23 @@
 Same construction and ordering as the reference:
   model  = UNet(num_classes, in_dim=3, conv_dim=64)                       trainer.py:107 (num_classes is a knob here, Q8)
   optim  = Adam(model.parameters(), lr, betas=[beta1, beta2])             trainer.py:108-110 -> FusedAdam
-           (cfg.optimizer='sgd', build-defined: FusedSGD with cfg.momentum, nesterov, weight_decay; cfg.lr_schedule='iteration': the
-            polynomial decay stepped after every optimiser step over cfg.max_iters instead of once per epoch)
   sched  = LambdaLR(optim, lambda n: (1 - n/n_iters) ** lr_exp)           trainer.py:111-112
   c_loss = CrossEntropyLoss()                                             trainer.py:113
   per epoch: scheduler.step() FIRST (trainer.py:147), then for each batch
       outputs = model(inputs); zero_grad(); loss = c_loss(outputs, labels); loss.backward(); optim.step()   :172-176
-Out of scope here: JPEG dumps, prints, checkpoint files; the every-10th-iteration statistics
-(trainer.py:177-189) are computed on the GPU by metrics.argmax_confusion instead of .cpu() round trips.
-Continual learning (config 4): ``begin_task2(c_old, ...)`` snapshots the model and switches the criterion to
-DistillationCrossEntropy and/or enables the L2-to-old-weights term (both build-defined); ``freeze_bn=True`` also trains task 2 with
-every BatchNorm in eval mode (running statistics, not updated); ``ewc_lambda > 0`` estimates the finished task's per-parameter importance
-(``estimate_importance``) and enables elastic weight consolidation inside the Adam kernel (build-defined too, consolidate.py);
-``cfg.path_integral=True`` tracks Synaptic Intelligence's path integral inside every optimiser step from the first one
-(consolidate.PathIntegral, ``self.path``) and ``begin_task2(si_lambda=c)`` consolidates with it instead of the Fisher estimate.
-Data parallel: ``sync_bn=True`` converts the model's BatchNorm layers to nn.SyncBatchNorm when a process group is initialised (statistics
-of the global batch, syncbn.py).  ``begin_task2(pseudo_label=True)`` relabels the background of the new task's batches with the old model's
-confident predictions (build-defined, pseudo.py); ``begin_task2(pod_lambda=...)`` adds Local POD distillation of the logits (build-defined,
-pod.py); ``begin_task2(replay=M, replay_batch=R)`` keeps M exemplars of the finished task in an on-device memory and mixes R of them into
-every batch (build-defined, replay.py).  ``cfg.augment=True`` (with augment_scale, augment_flip, augment_seed) rescales, crops or pads and
-flips every training batch -- the replayed rows included -- in one launch before the forward pass (build-defined, augment.py); off by
-default, and then nothing on the step's path changes.  ``cfg.loss='ce_dice'`` (build-defined, loss.DiceCrossEntropyLoss with dice_weight,
-dice_smooth, dice_include_background, dice_present_only, dice_per_image) makes the step's criterion cross-entropy + soft Dice; the default
-'ce' changes nothing.  ``begin_task2(pod_lambda=...)`` adds on top of it; not with distill_lambda > 0, unbiased=True or pseudo_adaptive=True
-(those criteria have no Dice term, this one no per-image weight).  ``estimate_importance`` keeps differentiating the plain log-likelihood.
-Data parallel: each rank's Dice sums cover its own batch, like non-synchronised BatchNorm; no collective is added.
+Out of scope here: JPEG dumps, prints, checkpoint files; the every-10th-iteration statistics (trainer.py:177-189)
+are computed on the GPU by metrics.argmax_confusion instead of .cpu() round trips.
+Configuration: ``default_config`` is the one table of defaults and ``complete_config`` fills what a caller's cfg lacks from it, so the
+code below reads plain ``cfg.name``.  The build-defined switches are off by default, and nothing on the step's path changes then:
+``optimizer='sgd'`` (FusedSGD with momentum, nesterov, weight_decay), ``lr_schedule='iteration'`` (make_scheduler), ``sync_bn``
+(syncbn.py), ``augment`` (every training batch, replayed rows included, rescaled, cropped or padded and flipped in one launch
+before the forward pass, augment.py), ``loss='ce_dice'`` (loss.DiceCrossEntropyLoss as the step's criterion: each rank's Dice sums cover
+its own batch, and ``estimate_importance`` keeps the plain log-likelihood), ``path_integral`` (consolidate.PathIntegral: Synaptic
+Intelligence's path integral, tracked inside every optimiser step from the first one).
+Continual learning (config 4): ``Trainer.begin_task2`` is the task boundary; its docstring numbers the stages once and places every
+feature at its stage.  What a feature adds to the trainer is declared once, at the top of the class.
 """
+import contextlib
 import os
 import warnings
 from types import SimpleNamespace
@@ -61,17 +52,25 @@ def default_config(**kw):
     return SimpleNamespace(**cfg)
 
 
+def complete_config(cfg):
+    """Sets every field of default_config() that `cfg` (any attribute namespace) lacks, on that same object, and returns it: a default
+    is written in default_config and nowhere else.  The caller's object is kept: grow_head writes cfg.num_classes back to it."""
+    for name, value in vars(default_config()).items():
+        if not hasattr(cfg, name):
+            setattr(cfg, name, value)
+    return cfg
+
+
 def make_scheduler(optim, cfg, iters_per_epoch=None):
-    """The learning-rate schedule of cfg.lr_schedule on any optimiser.  'epoch' (the default, the reference's trainer.py:111-112):
-    (1 - n/n_iters) ** lr_exp, stepped once at the start of every epoch.  'iteration' (build-defined, what the class-incremental
-    segmentation papers train with): max(0, 1 - n/max_iters) ** lr_exp, stepped after every optimiser step; cfg.max_iters None means
-    n_iters * iters_per_epoch."""
-    kind = getattr(cfg, 'lr_schedule', 'epoch')
+    """The learning-rate schedule of cfg.lr_schedule on any optimiser.  'epoch' (the default, the reference's trainer.py:111-112): (1 - n/n_iters)
+    ** lr_exp, stepped once at the start of every epoch.  'iteration' (build-defined, what the class-incremental segmentation papers train
+    with): max(0, 1 - n/max_iters) ** lr_exp, stepped after every optimiser step; cfg.max_iters None means n_iters * iters_per_epoch."""
+    kind = complete_config(cfg).lr_schedule
     if kind == 'epoch':
         return LambdaLR(optim, lr_lambda=lambda n: (1 - n / cfg.n_iters) ** cfg.lr_exp)
     if kind != 'iteration':
         raise ValueError(f"lr_schedule must be 'epoch' or 'iteration', not {kind!r}")
-    max_iters = getattr(cfg, 'max_iters', None)
+    max_iters = cfg.max_iters
     if max_iters is None:
         if iters_per_epoch is None:
             raise ValueError("lr_schedule='iteration' needs max_iters or a loader with a length")
@@ -99,154 +98,210 @@ def check_optimizer_state(state_dict, kind):
                          f"(cfg.optimizer): an optimiser state loads only into its own kind")
 
 
+def _host_copy(obj):
+    """A nested state for a checkpoint: dicts, lists and tuples rebuilt, CUDA tensors copied out on the current stream, the rest as it is."""
+    if isinstance(obj, dict):
+        return {k: _host_copy(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_host_copy(v) for v in obj)
+    if torch.is_tensor(obj) and obj.is_cuda:
+        return obj.to('cpu', non_blocking=True)
+    return obj
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """model.eval() inside the block; on the way out, after an error too, every module gets its own training flag back."""
+    modes = [(mod, mod.training) for mod in model.modules()]
+    model.eval()
+    try:
+        yield
+    finally:
+        for mod, mode in modes:
+            mod.training = mode
+
+
 class Trainer:
+    old_model = None           # the frozen snapshot of the finished task's model (begin_task2); this and the following: off until they are set
+    distill = None             # the distillation criterion that replaces c_loss in the step (begin_task2(distill_lambda > 0 or unbiased))
+    pseudo = None              # pseudo.PseudoLabeler once begin_task2(pseudo_label=True) ran
+    pod = None                 # pod.LocalPODLoss once begin_task2(pod_lambda > 0) ran
+    pod_channels = 0           # the c_old that loss compares
+    consolidation = None       # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0 or si_lambda > 0) ran
+    ewc_lambda = 0.0           # the weight the optimiser applies it with
+    path = None                # consolidate.PathIntegral when cfg.path_integral is set (build_model): tracked from the first step
+    replay = None              # replay.ReplayMemory once begin_task2(replay > 0) ran
+    replay_batch = 0           # exemplars mixed into every batch
+    replay_boundary = None     # c_old of the last call that added a segment: the next segment's first class
+    augment = None             # augment.RandomScaleCrop when cfg.augment is set (build_model)
+    step_labels = None         # the labels the last train_step's loss was computed against, rows [0, B), before pseudo-labelling
+
     def __init__(self, train_data_loader, cfg, device='cuda'):
-        self.cfg = cfg
+        self.cfg = complete_config(cfg)
         self.train_data_loader = train_data_loader
         self.device = torch.device(device)
         self.start_epoch = 0
-        self.old_model = None
-        self.pseudo = None                # pseudo.PseudoLabeler once begin_task2(pseudo_label=True) ran
-        self.pod = None                   # pod.LocalPODLoss once begin_task2(pod_lambda > 0) ran
-        self.pod_channels = 0
-        self.consolidation = None         # consolidate.Consolidation of the finished task(s) once begin_task2(ewc_lambda > 0) ran
-        self.ewc_lambda = 0.0
-        self.path = None                  # consolidate.PathIntegral when cfg.path_integral is set (build_model): tracked from the first step
-        self.replay = None                # replay.ReplayMemory once begin_task2(replay > 0) ran
-        self.replay_batch = 0             # exemplars mixed into every batch
-        self.replay_boundary = None       # c_old of the last call that added a segment: the next segment's first class
-        self.augment = None               # augment.RandomScaleCrop when cfg.augment is set (build_model)
-        self.step_labels = None           # the labels the last train_step's loss was computed against, rows [0, B), before pseudo-labelling
         self.build_model()
 
     def build_model(self):
         cfg = self.cfg
         self.model = UNet(num_classes=cfg.num_classes, in_dim=3, conv_dim=cfg.conv_dim,
                           compute_dtype=cfg.compute_dtype).to(self.device)
-        if getattr(cfg, 'sync_bn', False) and syncbn.initialized():
+        if cfg.sync_bn and syncbn.initialized():
             self.model = nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
-        kind = getattr(cfg, 'optimizer', 'adam')
-        if kind == 'adam':
-            self.optim = FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
-        elif kind == 'sgd':
-            no_decay = []
-            if not getattr(cfg, 'decay_norm_and_bias', True):      # every BatchNorm parameter and every bias
-                for mod in self.model.modules():
-                    if isinstance(mod, nn.modules.batchnorm._BatchNorm):
-                        no_decay += list(mod.parameters(recurse=False))
-                    elif getattr(mod, 'bias', None) is not None and isinstance(mod.bias, nn.Parameter):
-                        no_decay.append(mod.bias)
-            self.optim = FusedSGD(self.model.parameters(), lr=cfg.lr, momentum=getattr(cfg, 'momentum', 0.9),
-                                  nesterov=getattr(cfg, 'nesterov', True), weight_decay=getattr(cfg, 'weight_decay', 1e-4),
-                                  no_decay=no_decay)
-        else:
-            raise ValueError(f"optimizer must be 'adam' or 'sgd', not {kind!r}")
-        self.path = None
-        if getattr(cfg, 'path_integral', False):     # Synaptic Intelligence has to watch task 1: tracking is on from the first step
-            self.path = PathIntegral(self.model.named_parameters(), xi=getattr(cfg, 'si_xi', 0.1))
+        self.optim = self._make_optimizer()
+        self.path = PathIntegral(self.model.named_parameters(), xi=cfg.si_xi) if cfg.path_integral else None
+        if self.path is not None:     # Synaptic Intelligence has to watch task 1: tracking is on from the first step
             self.optim.set_path_integral(self.path.omega)
-        self.per_iteration = getattr(cfg, 'lr_schedule', 'epoch') == 'iteration'
+        self.per_iteration = cfg.lr_schedule == 'iteration'
         loader = self.train_data_loader
         self.scheduler = make_scheduler(self.optim, cfg, len(loader) if self.per_iteration and hasattr(loader, '__len__') else None)
         self.c_loss = CrossEntropyLoss().to(self.device)
         self.likelihood_loss = self.c_loss       # estimate_importance differentiates the plain log-likelihood whatever the step's criterion
-        kind = getattr(cfg, 'loss', 'ce')
-        if kind == 'ce_dice':
-            self.c_loss = DiceCrossEntropyLoss(1.0, getattr(cfg, 'dice_weight', 1.0), getattr(cfg, 'dice_smooth', 1e-5),
-                                               getattr(cfg, 'dice_include_background', True), getattr(cfg, 'dice_present_only', True),
-                                               getattr(cfg, 'dice_per_image', False)).to(self.device)
-        elif kind != 'ce':
-            raise ValueError(f"loss must be 'ce' or 'ce_dice', not {kind!r}")
-        self.augment = None
-        if getattr(cfg, 'augment', False):       # each rank draws its own scales, crops and flips
-            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
-            self.augment = RandomScaleCrop(scale=getattr(cfg, 'augment_scale', (0.5, 2.0)), flip=getattr(cfg, 'augment_flip', True),
-                                           ignore_index=self.c_loss.ignore_index, seed=int(getattr(cfg, 'augment_seed', 0)) + rank)
+        if cfg.loss == 'ce_dice':
+            self.c_loss = DiceCrossEntropyLoss(1.0, cfg.dice_weight, cfg.dice_smooth, cfg.dice_include_background, cfg.dice_present_only,
+                                               cfg.dice_per_image).to(self.device)
+        elif cfg.loss != 'ce':
+            raise ValueError(f"loss must be 'ce' or 'ce_dice', not {cfg.loss!r}")
+        self.augment = RandomScaleCrop(scale=cfg.augment_scale, flip=cfg.augment_flip, ignore_index=self.c_loss.ignore_index,
+                                       seed=int(cfg.augment_seed) + syncbn.rank()) if cfg.augment else None      # each rank draws its own
+
+    def _make_optimizer(self):
+        cfg = self.cfg
+        if cfg.optimizer == 'adam':
+            return FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
+        if cfg.optimizer != 'sgd':
+            raise ValueError(f"optimizer must be 'adam' or 'sgd', not {cfg.optimizer!r}")
+        no_decay = []
+        if not cfg.decay_norm_and_bias:      # every BatchNorm parameter and every bias
+            for mod in self.model.modules():
+                if isinstance(mod, nn.modules.batchnorm._BatchNorm):
+                    no_decay += list(mod.parameters(recurse=False))
+                elif getattr(mod, 'bias', None) is not None and isinstance(mod.bias, nn.Parameter):
+                    no_decay.append(mod.bias)
+        return FusedSGD(self.model.parameters(), lr=cfg.lr, momentum=cfg.momentum, nesterov=cfg.nesterov, weight_decay=cfg.weight_decay,
+                        no_decay=no_decay)
+
+    def _group(self):
+        sync = self.model.grad_sync       # the process group of the gradient exchange; None (the default group) without one
+        return sync.group if sync is not None else None
 
     def reset_grad(self):
         self.optim.zero_grad()
 
     def estimate_importance(self, data_loader, max_batches=None):
-        """Diagonal empirical Fisher information of the current model over a loader -> consolidate.Consolidation (finished; its anchor is
-        a clone of the current weights).  Every module in eval mode (BatchNorm on its running statistics, nothing updated), one
-        CrossEntropyLoss backward per batch, the squared gradients averaged over the batches; no optimizer step.  A loader of batch size 1
-        gives the per-image estimate, larger batches the square of the batch-mean gradient (consolidate.py).  Under an initialised process
-        group every rank ends with the mean over all ranks' batches.  Each module's own mode is restored and the gradients are cleared."""
+        """Diagonal empirical Fisher information of the current model over a loader -> consolidate.Consolidation (finished; its anchor is a
+        clone of the current weights).  Every module in eval mode (BatchNorm on its running statistics, nothing updated), one CrossEntropyLoss
+        backward per batch, the squared gradients averaged over the batches; no optimizer step.  A loader of batch size 1 gives the per-image
+        estimate, larger batches the square of the batch-mean gradient (consolidate.py).  Under an initialised process group every rank ends
+        with the mean over all ranks' batches.  Each module's own mode is restored and the gradients are cleared."""
         model = self.model
-        modes = [(mod, mod.training) for mod in model.modules()]
         sync, model.grad_sync = model.grad_sync, None      # the gradient exchange would average the gradients BEFORE they are squared
         cons = Consolidation(model.named_parameters())
         params = list(model.parameters())
         try:
-            model.eval()
-            for i, (images, masks) in enumerate(data_loader):
-                if max_batches is not None and i >= max_batches:
-                    break
-                outputs = model(images.to(self.device, non_blocking=True))
-                self.reset_grad()
-                self.likelihood_loss(outputs, masks.to(self.device, non_blocking=True)).backward()
-                cons.accumulate(params)
-            cons.finish()
+            with _eval_mode(model):
+                for i, (images, masks) in enumerate(data_loader):
+                    if max_batches is not None and i >= max_batches:
+                        break
+                    outputs = model(images.to(self.device, non_blocking=True))
+                    self.reset_grad()
+                    self.likelihood_loss(outputs, masks.to(self.device, non_blocking=True)).backward()
+                    cons.accumulate(params)
+                cons.finish()
         finally:
             self.reset_grad()
-            for mod, mode in modes:
-                mod.training = mode
             model.grad_sync = sync
         return cons
 
-    def _apply_consolidation(self):
+    def _install_consolidation(self, l2_lambda):
+        """Hands self.consolidation to the optimiser, with the L2 term on its anchor when l2_lambda > 0.  An L2 anchor from before goes
+        first: it is another snapshot than the consolidation's, and set_consolidation compares a kept L2 anchor with the one it is given."""
+        self.optim.set_l2_anchor(None, 0.0)
         self.optim.set_consolidation(self.consolidation.anchor, self.consolidation.importance, self.ewc_lambda)
+        if l2_lambda > 0:
+            self.optim.set_l2_anchor(self.consolidation.anchor, l2_lambda)
 
     def begin_task2(self, c_old, distill_lambda=1.0, temperature=2.0, l2_lambda=0.0, freeze_bn=False, ewc_lambda=0.0,
                     importance_loader=None, ewc_gamma=1.0, new_classes=0, unbiased=False, head_init='background',
                     pseudo_label=False, pseudo_bins=100, pseudo_adaptive=False, pseudo_min_factor=0.0, pseudo_loader=None,
                     pod_lambda=0.0, pod_levels=3, replay=0, replay_batch=0, replay_loader=None, replay_storage='uint8', replay_flip=True,
                     replay_min_pixels=1, replay_seed=0, si_lambda=0.0):
-        """Freeze a snapshot of the current model (task 1) and regularise further training towards it.  freeze_bn: every BatchNorm of the
-        trained model goes to eval mode -- task 2 normalises with task 1's running statistics and leaves them unchanged (the gradients
-        still reach gamma and beta).  ewc_lambda > 0: elastic weight consolidation -- the importance of the finished task is estimated on
-        importance_loader (default: the training loader) before anything of the new task is switched on, merged with the previous tasks'
-        (importance <- ewc_gamma * previous + new, online EWC) when this is not the first call, and the Adam kernel adds
-        ewc_lambda * importance * (theta - theta_old) to every gradient.
-        Class-incremental step (build-defined): new_classes > 0 grows the trained model's head by that many outputs AFTER the importance
-        estimate and the snapshot (the old model keeps its width; UNet.expand_classes(new_classes, head_init)), carrying Adam's moments and
-        the anchors over; unbiased=True distils with UnbiasedDistillationCrossEntropy(c_old, distill_lambda) (no temperature) instead of
-        DistillationCrossEntropy.  A later call (task 3) snapshots the grown model: c_old is then the grown width.
-        Pseudo-labels (build-defined, pseudo.py): pseudo_label=True calibrates a PseudoLabeler(c_old, pseudo_bins, pseudo_adaptive,
-        pseudo_min_factor) with the snapshot on pseudo_loader (default: the training loader -- it should hold the NEW task's data, whose
-        old-class pixels are labelled 0); every step then runs the old model's forward, also with distill_lambda == 0, relabels the
-        background pixels it is confident about, ignores the others, and (pseudo_adaptive) weights each image's loss by the accepted share.
-        Not with unbiased=True (that criterion treats every label < c_old alike: pseudo-labels would change nothing), and pseudo_adaptive
-        not with distill_lambda > 0 (DistillationCrossEntropy's kernel has no per-image weight).  The canonical setting is
-        begin_task2(c_old, distill_lambda=0, pseudo_label=True, pseudo_adaptive=True).
-        Local POD (build-defined, pod.py): pod_lambda > 0 keeps LocalPODLoss(pod_levels, square=False, normalize=True, lam=pod_lambda); every
-        step then runs the old model's forward, also with distill_lambda == 0 and without pseudo-labels, and adds
-        pod(outputs, old, channels=c_old, merge_extra=True) to the criterion's loss -- the old background against the new background plus
-        the new classes.  It combines with every criterion above; PLOP's step is begin_task2(c_old, distill_lambda=0, pseudo_label=True,
-        pseudo_adaptive=True, pod_lambda=...).  pod_lambda == 0 leaves the step as it is.
-        Exemplar replay (build-defined, replay.py): replay > 0 adds a segment of that many slots to ``self.replay`` (a ReplayMemory with
-        replay_storage, replay_flip and replay_seed, created on first use) for the FINISHED task's own classes -- [1, c_old) on the first
-        call, [c_old of the previous such call, c_old) later -- and fills it from replay_loader (default: the training loader, with the
-        same meaning as importance_loader) by the class-balanced policy with replay_min_pixels, before the snapshot, the criterion switch
-        and the growing of the head.  Every step then starts with ``inputs, labels = self.replay.mix(inputs, labels, replay_batch)``
-        (replay_batch >= 1 is required): the old model's forward, the pseudo-labels, the distillation terms and the loss all see the
-        B + replay_batch rows, and so do the returned outputs; the caller's batch is rows [0, B).  replay == 0 leaves a memory from earlier
-        calls (and its replay_batch, unless a new one >= 1 is given) in place and adds nothing.  Data parallelism: each rank keeps its own
-        memory, filled from its own shard and sampled with replay_seed + rank; the gradients are averaged as always, no collective is
-        added.
-        Synaptic Intelligence (build-defined, consolidate.PathIntegral): si_lambda = c > 0 needs cfg.path_integral (the optimiser has been
-        accumulating omega since the first step) and is refused together with ewc_lambda > 0 (one importance buffer; the combination is
-        Riemannian Walk).  Where the EWC estimate would run, the path integral of the finished task becomes a Consolidation -- importance
-        <- previous + max(0, omega) / ((theta - theta_start)^2 + si_xi), anchor = the current weights --, omega and theta_start restart, and
-        the consolidation term runs with ewc_lambda = 2 c: consolidation_penalty() is c * sum Omega (theta - theta*)^2.  It composes with
-        everything ewc_lambda composes with; si_lambda == 0 leaves an earlier consolidation in place; tracking goes on for the next boundary."""
+        """The task boundary: freeze a snapshot of the current model (the finished task) and regularise further training towards it.
+        The stages, in this order (every loader defaults to the training loader):
+          1. every argument check (_check_task2, whose messages say what is refused and why): nothing has changed when one raises;
+          2. replay fill: the exemplar memory takes its segment of the FINISHED task's data (_fill_replay), and replay_batch;
+          3. consolidation of the finished task (_consolidate_finished_task): the EWC estimate and merge, or the path integral;
+          4. the snapshot ``self.old_model`` (_freeze_old_model): the un-grown model, in eval mode, without gradients;
+          5. the criteria: ``distill``, ``pod`` / ``pod_channels``, and ``pseudo`` with its calibration on the snapshot;
+          6. the optimiser's anchors: the consolidation (_install_consolidation), or the L2 term alone on clones of the snapshot;
+          7. head growth (grow_head: optimiser state, anchors, consolidation and path integral carried over), then the BatchNorm freeze.
+        freeze_bn (stage 7): every BatchNorm of the trained model goes to eval mode: task 1's running statistics, unchanged; gamma and beta train.
+        EWC (stages 3, 6): ewc_lambda > 0 estimates the finished task's importance on importance_loader, merges the previous tasks' into
+        it on a later call (importance <- ewc_gamma * previous + new, online EWC), and the optimiser's kernel adds ewc_lambda * importance
+        * (theta - theta_old) to every gradient.
+        Class-incremental step (build-defined; stages 5, 7): new_classes > 0 grows the trained model's head by that many outputs
+        (UNet.expand_classes(new_classes, head_init); the old model keeps its width, and a later call, task 3, snapshots the grown model: its
+        c_old is the grown width); unbiased=True distils with UnbiasedDistillationCrossEntropy(c_old, distill_lambda), no temperature.
+        Pseudo-labels (build-defined, pseudo.py; stage 5): pseudo_label=True calibrates a PseudoLabeler(c_old, pseudo_bins, pseudo_adaptive,
+        pseudo_min_factor) on pseudo_loader (the NEW task's data, whose old-class pixels are labelled 0); every step then runs the old
+        model's forward, also with distill_lambda == 0, relabels the background pixels it is confident about, ignores the others, and
+        (pseudo_adaptive) weights each image's loss by the accepted share; canonical: distill_lambda=0, pseudo_label=True, pseudo_adaptive=True.
+        Local POD (build-defined, pod.py; stage 5): pod_lambda > 0 keeps LocalPODLoss(pod_levels, square=False, normalize=True,
+        lam=pod_lambda); every step then runs the old model's forward and adds pod(outputs, old, channels=c_old, merge_extra=True) to the
+        criterion's loss -- the old background against the new background plus the new classes.  It combines with every criterion above:
+        PLOP's step is the canonical pseudo-label setting with pod_lambda > 0.
+        Exemplar replay (build-defined, replay.py; stage 2): replay > 0 adds a segment of that many slots to ``self.replay`` (a ReplayMemory
+        with replay_storage, replay_flip and replay_seed + rank, created on first use; each rank keeps its own) for the finished task's own
+        classes -- [1, c_old) on the first call, [c_old of the previous such call, c_old) later -- filled from replay_loader by the
+        class-balanced policy with replay_min_pixels.  Every step then starts with ``self.replay.mix(inputs, labels, replay_batch)``: all
+        that follows, and the returned outputs, see B + replay_batch rows, the caller's batch being rows [0, B).  replay == 0 leaves an
+        earlier memory (and its replay_batch, unless a new one >= 1 is given) in place.
+        Synaptic Intelligence (build-defined, consolidate.PathIntegral; stages 3, 6): si_lambda = c > 0 turns the finished task's path
+        integral into the Consolidation -- importance <- previous + max(0, omega) / ((theta - theta_start)^2 + si_xi), anchor = the
+        current weights --, omega and theta_start restart, and the term runs with ewc_lambda = 2 c: consolidation_penalty() is
+        c * sum Omega (theta - theta*)^2.  si_lambda == 0 leaves an earlier consolidation in place."""
+        self._check_task2(c_old, distill_lambda, ewc_lambda, unbiased, pseudo_label, pseudo_adaptive, pod_lambda, pod_levels, replay,
+                          replay_batch, si_lambda)
+        if replay > 0:
+            self._fill_replay(c_old, replay, self.train_data_loader if replay_loader is None else replay_loader, replay_storage, replay_flip,
+                              replay_min_pixels, replay_seed)
+        if replay_batch >= 1:
+            self.replay_batch = int(replay_batch)
+        consolidated = self._consolidate_finished_task(ewc_lambda, importance_loader, ewc_gamma, si_lambda)
+        self._freeze_old_model()
+        if unbiased:
+            self.distill = UnbiasedDistillationCrossEntropy(c_old, distill_lambda)
+        else:
+            self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
+        self.pod = LocalPODLoss(pod_levels, square=False, normalize=True, lam=pod_lambda) if pod_lambda > 0 else None
+        self.pod_channels = int(c_old)
+        self.pseudo = None
+        if pseudo_label:
+            self.pseudo = PseudoLabeler(c_old, bins=pseudo_bins, adaptive=pseudo_adaptive, min_factor=pseudo_min_factor,
+                                        ignore_index=self.c_loss.ignore_index)
+            self.pseudo.calibrate(self.old_model, self.train_data_loader if pseudo_loader is None else pseudo_loader, self.device,
+                                  group=self._group())
+        if consolidated:
+            self._install_consolidation(l2_lambda)
+        elif l2_lambda > 0:       # the L2 term alone pulls towards the snapshot itself
+            self.optim.set_l2_anchor([p.detach().clone() for p in self.old_model.parameters()], l2_lambda)
+        if new_classes > 0:
+            self.grow_head(new_classes, head_init)
+        if freeze_bn:
+            for mod in self.model.modules():
+                if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
+                    mod.eval()
+
+    def _check_task2(self, c_old, distill_lambda, ewc_lambda, unbiased, pseudo_label, pseudo_adaptive, pod_lambda, pod_levels, replay,
+                     replay_batch, si_lambda):
+        """Stage 1 of begin_task2: raises ValueError for what the boundary refuses; reads only."""
         if not si_lambda >= 0:
             raise ValueError('si_lambda must be >= 0')
-        if si_lambda > 0 and getattr(self, 'path', None) is None:
+        if si_lambda > 0 and self.path is None:
             raise ValueError('si_lambda > 0 needs cfg.path_integral=True: the path integral has to be tracked from the first step of the task')
         if si_lambda > 0 and ewc_lambda > 0:
-            raise ValueError('si_lambda > 0 with ewc_lambda > 0: there is one importance buffer (the combination, Riemannian Walk, is not '
-                             'provided)')
+            raise ValueError('si_lambda > 0 with ewc_lambda > 0: there is one importance buffer (the combination, Riemannian Walk, is not provided)')
         if replay < 0 or replay_batch < 0:
             raise ValueError('replay and replay_batch must be >= 0')
         if replay > 0 and replay_batch < 1:
@@ -263,7 +318,7 @@ class Trainer:
         if pseudo_label and pseudo_adaptive and distill_lambda > 0:
             raise ValueError('pseudo_adaptive=True with distill_lambda > 0: DistillationCrossEntropy has no per-image weight '
                              '(use distill_lambda=0, or pseudo_adaptive=False)')
-        if getattr(getattr(self, 'cfg', None), 'loss', 'ce') == 'ce_dice':
+        if self.cfg.loss == 'ce_dice':
             if unbiased:
                 raise ValueError("loss='ce_dice' with unbiased=True: the Dice term is not defined inside the unbiased criterion "
                                  "(labels below c_old mean 'background or any old class' there)")
@@ -271,13 +326,10 @@ class Trainer:
                 raise ValueError("loss='ce_dice' with distill_lambda > 0: DistillationCrossEntropy has no Dice term "
                                  "(use distill_lambda=0, with pod_lambda > 0 for distillation)")
             if pseudo_label and pseudo_adaptive:
-                raise ValueError("loss='ce_dice' with pseudo_adaptive=True: DiceCrossEntropyLoss has no per-image weight "
-                                 "(use pseudo_adaptive=False)")
-        if replay > 0:
-            self._fill_replay(c_old, replay, self.train_data_loader if replay_loader is None else replay_loader, replay_storage, replay_flip,
-                              replay_min_pixels, replay_seed)
-        if replay_batch >= 1:
-            self.replay_batch = int(replay_batch)
+                raise ValueError("loss='ce_dice' with pseudo_adaptive=True: DiceCrossEntropyLoss has no per-image weight (use pseudo_adaptive=False)")
+
+    def _consolidate_finished_task(self, ewc_lambda, importance_loader, ewc_gamma, si_lambda):
+        """Stage 3 of begin_task2: self.consolidation and self.ewc_lambda from the Fisher estimate or the path integral; -> whether either ran."""
         if ewc_lambda > 0:
             cons = self.estimate_importance(self.train_data_loader if importance_loader is None else importance_loader)
             cons.gamma = float(ewc_gamma)
@@ -288,50 +340,27 @@ class Trainer:
             self.consolidation = self.path.consolidate(self.model.named_parameters(), previous=self.consolidation)
             self.path.restart(self.model.parameters())
             self.ewc_lambda = 2.0 * float(si_lambda)
-        consolidated = ewc_lambda > 0 or si_lambda > 0
-        # a fresh module with a CLONE of the state (not copy.deepcopy: that would duplicate the engine's multi-GB activation
-        # buffers and, under data parallelism, the GradSync object with its process group and stream)
+        return ewc_lambda > 0 or si_lambda > 0
+
+    def _freeze_old_model(self):
+        """Stage 4 of begin_task2: a fresh module with a CLONE of the state (not copy.deepcopy: that would duplicate the engine's multi-GB
+        activation buffers and, under data parallelism, the GradSync object with its process group and stream)."""
         m = self.model
         self.old_model = UNet(m.num_classes, m.in_dim, m.conv_dim, compute_dtype=m.compute_dtype).to(self.device)
         self.old_model.load_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()}, strict=True)
         self.old_model.eval()
         for p in self.old_model.parameters():
             p.requires_grad_(False)
-        if unbiased:
-            self.distill = UnbiasedDistillationCrossEntropy(c_old, distill_lambda)
-        else:
-            self.distill = DistillationCrossEntropy(c_old, temperature, distill_lambda) if distill_lambda > 0 else None
-        self.pod = LocalPODLoss(pod_levels, square=False, normalize=True, lam=pod_lambda) if pod_lambda > 0 else None
-        self.pod_channels = int(c_old)
-        self.pseudo = None
-        if pseudo_label:
-            self.pseudo = PseudoLabeler(c_old, bins=pseudo_bins, adaptive=pseudo_adaptive, min_factor=pseudo_min_factor,
-                                        ignore_index=self.c_loss.ignore_index)
-            group = m.grad_sync.group if getattr(m, 'grad_sync', None) is not None else None
-            self.pseudo.calibrate(self.old_model, self.train_data_loader if pseudo_loader is None else pseudo_loader, self.device, group=group)
-        if consolidated:
-            self.optim.set_l2_anchor(None, 0.0)        # an earlier task's L2 anchor is another snapshot than the new consolidation anchor
-            self._apply_consolidation()
-        if l2_lambda > 0:
-            self.optim.set_l2_anchor(self.consolidation.anchor if consolidated else [p.detach().clone() for p in self.old_model.parameters()],
-                                     l2_lambda)
-        if new_classes > 0:
-            self.grow_head(new_classes, head_init)
-        if freeze_bn:
-            for mod in m.modules():
-                if isinstance(mod, nn.modules.batchnorm._BatchNorm):       # nn.BatchNorm2d and nn.SyncBatchNorm
-                    mod.eval()
 
     def _fill_replay(self, c_old, capacity, loader, storage, flip, min_pixels, seed):
         """One more segment of the exemplar memory for the classes [previous boundary or 1, c_old), filled from `loader`."""
         lo = 1 if self.replay_boundary is None else self.replay_boundary
-        rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         mem = self.replay
         for images, masks in loader:
             x, y = images.to(self.device, non_blocking=True), masks.to(self.device, non_blocking=True)
             if mem is None:       # the image shape is the data's
                 mem = ReplayMemory(c_old, tuple(x.shape[1:]), storage=storage, ignore_index=self.c_loss.ignore_index, flip=flip,
-                                   seed=int(seed) + rank)
+                                   seed=int(seed) + syncbn.rank())
             if mem.open is None:
                 mem.num_classes = max(mem.num_classes, int(c_old))      # the head has grown since the memory was created
                 mem.add_task((lo, c_old), capacity, min_pixels)
@@ -348,15 +377,13 @@ class Trainer:
         m = self.model
         names = {id(p): k for k, p in m.named_parameters()}
         ow, ob, nw, nb = m.expand_classes(n, init)
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            group = m.grad_sync.group if m.grad_sync is not None else None
+        if syncbn.initialized():
             for t in (nw, nb):
-                torch.distributed.broadcast(t.data, src=0, group=group)
+                torch.distributed.broadcast(t.data, src=0, group=self._group())
         # The order matters.  (1) The Consolidation grows first: it owns the importance (one flat buffer, laid out again) and the anchors,
         # and takes the new rows' anchor from the (broadcast) new parameters.  (2) replace_params swaps the parameter objects and re-homes
         # Adam's moments; it also grows the optimiser's own anchor / importance entries, which is all there is when only the L2 term is on.
-        # (3) With a consolidation the optimiser must read the Consolidation's NEW importance views and anchors, so both terms are set
-        # again from it (set_l2_anchor(None) first: set_consolidation compares a kept L2 anchor with the one it is given).
+        # (3) With a consolidation the optimiser must read the Consolidation's NEW importance views and anchors: both terms are set again.
         if self.consolidation is not None:
             self.consolidation.grow(names[id(ow)], nw)
             self.consolidation.grow(names[id(ob)], nb)
@@ -367,16 +394,11 @@ class Trainer:
         if self.path is not None:
             self.optim.set_path_integral(self.path.omega)
         if self.consolidation is not None and self.ewc_lambda > 0:
-            l2 = self.optim.l2_lambda
-            self.optim.set_l2_anchor(None, 0.0)
-            self._apply_consolidation()
-            if l2 > 0:
-                self.optim.set_l2_anchor(self.consolidation.anchor, l2)
+            self._install_consolidation(self.optim.l2_lambda)
         self.cfg.num_classes = m.num_classes
 
-    # ---- checkpoints: same file name and keys as trainer.py:68-102, but the model never leaves
-    # the GPU: the reference does network.cpu() ... network.cuda() (a full D2H + H2D round trip of 124 MB every
-    # epoch, trainer.py:75,80-81,258); here the state is copied into pinned host buffers on a side stream.
+    # ---- checkpoints: same file name and keys as trainer.py:68-102, but the model never leaves the GPU: the reference
+    # does network.cpu() ... network.cuda() (124 MB each way every epoch, trainer.py:75,80-81,258); here a side stream copies the state out.
     def snapshot(self, epoch):
         """Starts an asynchronous device->pinned-host copy of model/optimizer state; returns a handle for write()."""
         if not hasattr(self, '_snap_stream'):
@@ -393,46 +415,27 @@ class Trainer:
                 buf.copy_(v, non_blocking=True)
                 host[k] = buf
             opt = self.optim.state_dict()
-            opt_host = {'param_groups': opt['param_groups'],
-                        'state': {i: {n: (t.to('cpu', non_blocking=True) if torch.is_tensor(t) and t.is_cuda else t)
-                                      for n, t in s.items()} for i, s in opt['state'].items()}}
-            cons_host = None
-            if self.consolidation is not None:       # one optional key beside the reference's four
-                cs = self.consolidation.state_dict()
-                cons_host = {'anchor': {n: t.to('cpu', non_blocking=True) for n, t in cs['anchor'].items()},
-                             'importance': {n: t.to('cpu', non_blocking=True) for n, t in cs['importance'].items()},
-                             'lambda': self.ewc_lambda, 'gamma': cs['gamma'], 'n_batches': cs['n_batches']}
-            path_host = None
-            if self.path is not None:                # one more optional key: the running path integral and the task's starting weights
-                ps = self.path.state_dict()
-                path_host = {'omega': {n: t.to('cpu', non_blocking=True) for n, t in ps['omega'].items()},
-                             'start': {n: t.to('cpu', non_blocking=True) for n, t in ps['start'].items()}, 'xi': ps['xi']}
-            replay_host = None
-            if self.replay is not None:              # a second optional key
-                rs = self.replay.state_dict()
-                replay_host = {k: (v.to('cpu', non_blocking=True) if torch.is_tensor(v) and v.is_cuda else v) for k, v in rs.items()}
-                replay_host.update(batch=self.replay_batch, boundary=self.replay_boundary)
-            done = torch.cuda.Event()
-            done.record(st)
-        snap = {'epoch': epoch + 1, 'model_state': host, 'optimizer_state': opt_host,
-                'scheduler_state': self.scheduler.state_dict(), '_event': done}
-        if cons_host is not None:
-            snap['consolidation_state'] = cons_host
-        if path_host is not None:
-            snap['path_state'] = path_host
-        if replay_host is not None:
-            snap['replay_state'] = replay_host
-        if self.augment is not None:                 # a third optional key: the configuration and the generator state (a host tensor)
+            snap = {'epoch': epoch + 1, 'model_state': host,
+                    'optimizer_state': {'param_groups': opt['param_groups'], 'state': _host_copy(opt['state'])}}
+            # the optional keys beside the reference's four, each while its object exists: its state_dict() on the host + the trainer's scalars
+            if self.consolidation is not None:
+                snap['consolidation_state'] = dict(_host_copy(self.consolidation.state_dict()), **{'lambda': self.ewc_lambda})
+            if self.path is not None:                # the running path integral and the task's starting weights
+                snap['path_state'] = _host_copy(self.path.state_dict())
+            if self.replay is not None:
+                snap['replay_state'] = dict(_host_copy(self.replay.state_dict()), batch=self.replay_batch, boundary=self.replay_boundary)
+            snap['_event'] = torch.cuda.Event()
+            snap['_event'].record(st)
+        snap['scheduler_state'] = self.scheduler.state_dict()
+        if self.augment is not None:                 # the configuration and the generator state (a host tensor)
             snap['augment_state'] = self.augment.state_dict()
         return snap
 
     def save_network(self, network_label, epoch_label, epoch, save_dir):
-        """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/
-        scheduler_state (loadable by the reference's load_network and by torch.optim.Adam); with elastic weight consolidation
-        active one more key, consolidation_state (anchor, importance, lambda, gamma, n_batches), which the reference ignores; with an exemplar memory
-        replay_state (ReplayMemory.state_dict() on the host, replay_batch and the class boundary), ignored by the reference too; with
-        augmentation augment_state (RandomScaleCrop.state_dict(): configuration and generator state), likewise; with cfg.path_integral
-        path_state (PathIntegral.state_dict(): omega and the task's starting weights by name, and xi), likewise."""
+        """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/scheduler_state (loadable by
+        the reference's load_network and by torch.optim.Adam) and snapshot()'s optional keys, which the reference ignores: consolidation_state
+        (anchor, importance, n_batches, gamma; lambda), path_state (omega, start, xi), replay_state (ReplayMemory.state_dict(); batch,
+        boundary) and augment_state (RandomScaleCrop.state_dict())."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -448,7 +451,7 @@ class Trainer:
         ck = torch.load(path, map_location='cpu', weights_only=False)
         self.model.load_state_dict(ck['model_state'])
         self.start_epoch = ck['epoch']
-        check_optimizer_state(ck['optimizer_state'], getattr(self.cfg, 'optimizer', 'adam'))
+        check_optimizer_state(ck['optimizer_state'], self.cfg.optimizer)
         self.optim.load_state_dict(ck['optimizer_state'])
         self.scheduler.load_state_dict(ck['scheduler_state'])
         self.load_consolidation_state(ck.get('consolidation_state'))
@@ -492,14 +495,13 @@ class Trainer:
         cons = Consolidation(self.model.named_parameters())
         cons.load_state_dict(state)
         self.consolidation, self.ewc_lambda = cons, float(state['lambda'])
-        self._apply_consolidation()
+        self.optim.set_consolidation(self.consolidation.anchor, self.consolidation.importance, self.ewc_lambda)
 
     def train_step(self, inputs, labels):
         """trainer.py:172-176.  With an exemplar memory the batch is first extended by replay_batch exemplars: everything below, and the
         returned outputs, cover B + replay_batch rows, the caller's batch being rows [0, B).  With cfg.augment the (mixed) batch is then
-        rescaled, cropped or padded and flipped in one launch, exemplars included: everything below sees the augmented batch.
-        ``self.step_labels`` keeps the labels the loss is computed against, rows [0, B), before pseudo-labelling: the caller's own tensor
-        without augmentation."""
+        rescaled, cropped or padded and flipped in one launch, exemplars included: everything below sees the augmented batch.  ``self.step_labels``
+        keeps the labels the loss is computed against, rows [0, B), before pseudo-labelling: the caller's own tensor without augmentation."""
         self.step_labels = labels
         if self.replay is not None and self.replay_batch > 0:
             inputs, labels = self.replay.mix(inputs, labels, self.replay_batch)
@@ -508,7 +510,7 @@ class Trainer:
             self.step_labels = labels[:self.step_labels.shape[0]]
         outputs = self.model(inputs)
         self.reset_grad()
-        distill = getattr(self, 'distill', None) if self.old_model is not None else None
+        distill = self.distill if self.old_model is not None else None
         pod = self.pod if self.old_model is not None else None
         if distill is not None or self.pseudo is not None or pod is not None:
             with torch.no_grad():
@@ -533,17 +535,14 @@ class Trainer:
         """trainer.py:270-284: pixel accuracy (%) of the eval-mode model over a loader.  The arg-max of trainer.py:279 runs
         inside the head kernel (UNet.predict).  Unlike the reference (which never calls .train() again) the
         mode of every module is restored afterwards, each its own (frozen BatchNorm layers stay frozen)."""
-        modes = [(mod, mod.training) for mod in self.model.modules()]
-        self.model.eval()
         correct = torch.zeros((), dtype=torch.int64, device=self.device)
         total = 0
-        for images, masks in data_loader:
-            labels = masks.to(self.device, non_blocking=True)
-            predicted = self.model.predict(images.to(self.device, non_blocking=True))
-            total += labels.numel()
-            correct += (predicted == labels).sum()
-        for mod, mode in modes:
-            mod.training = mode
+        with _eval_mode(self.model):
+            for images, masks in data_loader:
+                labels = masks.to(self.device, non_blocking=True)
+                predicted = self.model.predict(images.to(self.device, non_blocking=True))
+                total += labels.numel()
+                correct += (predicted == labels).sum()
         return 100.0 * float(correct) / max(total, 1)
 
     def train_epoch(self, epoch):

@@ -191,6 +191,7 @@ def test_begin_task2_pod_arguments(C, monkeypatch):
     sig = inspect.signature(C.Trainer.begin_task2)
     assert sig.parameters['pod_lambda'].default == 0.0 and sig.parameters['pod_levels'].default == 3
     tr = C.Trainer.__new__(C.Trainer)
+    tr.cfg = C.default_config()
     for kw in (dict(pod_lambda=-1.0), dict(pod_lambda=float('nan')), dict(pod_lambda=0.5, pod_levels=4), dict(pod_lambda=0.5, pod_levels=0)):
         with pytest.raises(ValueError, match='pod_'):
             tr.begin_task2(3, distill_lambda=0, **kw)
