@@ -1,7 +1,8 @@
 """Shared helpers of the per-element GPU grid tests (test_bn_grid_gpu.py, test_pointwise_grid_gpu.py, test_conv3_grid_gpu.py,
-test_wino_wgrad_grid_gpu.py, test_sgd_gpu.py, test_adam_grid_gpu.py): poisoned buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit
+test_wino_wgrad_grid_gpu.py, test_wino_pre_fwd_grid_gpu.py, test_sgd_gpu.py, test_adam_grid_gpu.py): poisoned buffers with guard bands, the second half of a concat buffer, host-generated inputs, the bit-for-bit
 expectations, the two-runs check, the storage rounding of the three dtypes, the per-element comparison against a float64 reference and the
-float64 weight-gradient reference (a sum over pixels per tap)."""
+float64 weight-gradient reference (a sum over pixels per tap), and what the two Winograd files share: the transform matrices, the tile
+geometry of the pre-transformed forms and the V / Yt / U layouts."""
 import math
 
 import numpy as np
@@ -256,3 +257,156 @@ def _wgrad_ref(mode, a, b, shape):
         bv = b.double().view(B, H, 2, W, 2, Cp)
         taps = [bv[:, :, dy, :, dx].reshape(B * H * W, Cp) for dy in range(2) for dx in range(2)]
     return torch.stack([ad.T @ t for t in taps], -1), torch.stack([ad.abs().T @ t.abs() for t in taps], -1)
+
+
+# ------------------------------------------------------------------------------ Winograd: the matrices, as the kernel comments print them
+BT4 = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
+BT6 = [[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]]
+A4 = [[1, 0], [1, 1], [1, -1], [0, -1]]
+A6 = [[1, 0, 0, 0], [1, 1, 1, 1], [1, -1, 1, -1], [1, 2, 4, 8], [1, -2, 4, -8], [0, 0, 0, 1]]
+G4 = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]]
+G6 = [[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]]
+# th x tw output tile; (rows, columns) matrices; roundings of the two transforms and of the reduce's G^T . G, counted in the docstring of
+# test_wino_wgrad_grid_gpu.py
+FORM = {22: dict(th=2, tw=2, BT=(BT4, BT4), A=(A4, A4), G=(G4, G4), nV=2, nY=2, nG=4),
+        24: dict(th=2, tw=4, BT=(BT4, BT6), A=(A4, A6), G=(G4, G6), nV=3, nY=3, nG=7),
+        44: dict(th=4, tw=4, BT=(BT6, BT6), A=(A6, A6), G=(G6, G6), nV=4, nY=4, nG=10)}
+# sign conventions of what the kernels keep in memory, (plane rows i, plane columns j) that are stored negated (the reduce flips them back):
+# V of the pre-transformed F(2x4) form carries row 2 of B4^T negated; the in-kernel kernels leave out the sign of B4^T row 2 and of A4 row 3,
+# and F(2x2) also that of A4's column 3
+SIGN = {'pre24': ((2,), ()), 'pre44': ((), ()), 'ink24': ((2, 3), ()), 'ink22': ((2, 3), (3,))}
+
+
+def _m(rows, absolute=False):
+    t = torch.tensor(rows, dtype=torch.float64, device=DEV)
+    return t.abs() if absolute else t
+
+
+def _planes_n(form):
+    return len(FORM[form]['BT'][0]), len(FORM[form]['BT'][1])
+
+
+def _sign(kind, form):
+    """[ni * nj] float64: -1 where the stored plane is the negated true one."""
+    ni, nj = _planes_n(form)
+    s = torch.ones(ni, nj, dtype=torch.float64, device=DEV)
+    for i in SIGN[kind][0]:
+        s[i] *= -1
+    for j in SIGN[kind][1]:
+        s[:, j] *= -1
+    return s.reshape(-1)
+
+
+# --------------------------------------------------------------------------------------------------- Winograd: tile geometry and layouts
+def _geom(form, shape):
+    """Tile blocks of the pre-transformed forms: 32 tiles each, 8 across x 4 down (W >= 32) or 4 across x 8 down; tile t = 32 * block + tile in
+    block, blocks x fastest, then y, then the image (w24_tile / w44_block)."""
+    B, H, W = shape
+    th = FORM[form]['th']
+    TXN = 8 if W >= 32 else 4
+    TYN = 32 // TXN
+    PW, PH = 4 * TXN, th * TYN
+    bx, by = -(-W // PW), -(-H // PH)
+    return dict(TXN=TXN, TYN=TYN, PW=PW, PH=PH, bx=bx, by=by, ntm=B * bx * by, Tp=32 * B * bx * by, th=th)
+
+
+def _tile_origin(g, t):
+    """Tile t -> (image, first output row, first output column)."""
+    tm, r = divmod(t, 32)
+    b, rem = divmod(tm, g['bx'] * g['by'])
+    yb, xb = divmod(rem, g['bx'])
+    return b, yb * g['PH'] + g['th'] * (r // g['TXN']), xb * g['PW'] + 4 * (r % g['TXN'])
+
+
+def _tile_of(g, b, y, x):
+    """The tile that holds output pixel (b, y, x): the inverse of _tile_origin."""
+    yb, xb = y // g['PH'], x // g['PW']
+    r = ((y % g['PH']) // g['th']) * g['TXN'] + (x % g['PW']) // 4
+    return ((b * g['by'] + yb) * g['bx'] + xb) * 32 + r
+
+
+def _v_index(t, pl, c, Cp, P):
+    """Float offset of (tile t, plane pl = 6 i + j, channel c) in V [tile block][Cp / 8][P][2][32][4]."""
+    return (((t >> 5) * (Cp // 8) + c // 8) * P + pl) * 256 + ((c % 8) // 4) * 128 + (t & 31) * 4 + c % 4
+
+
+def _v_unindex(off, Cp, P):
+    off, e = divmod(off, 4)
+    off, r = divmod(off, 32)
+    off, h = divmod(off, 2)
+    off, pl = divmod(off, P)
+    tm, kc = divmod(off, Cp // 8)
+    return 32 * tm + r, pl, 8 * kc + 4 * h + e
+
+
+def _yt_index(t, pl, r, Tp, Rp):
+    """Float offset of (plane, tile, channel) in Yt [P][Tp][Rp]."""
+    return (pl * Tp + t) * Rp + r
+
+
+def _v_layout(V):
+    """[Tp, P, Cp] -> V as the kernels store it, [Tp / 32][Cp / 8][P][2][32][4], flat."""
+    Tp, P, Cp = V.shape
+    return V.reshape(Tp // 32, 32, P, Cp // 8, 2, 4).permute(0, 3, 2, 4, 1, 5).reshape(-1)
+
+
+def _patches(v, shape, th, tw, halo, Hp, Wp):
+    """[npix, Ch] -> float64 [B, Hp / th, Wp / tw, Ch, th + 2 halo, tw + 2 halo]: every tile's patch of the image zero-padded to Hp x Wp (+ halo)."""
+    B, H, W = shape
+    pad = torch.zeros(B, Hp + 2 * halo, Wp + 2 * halo, v.shape[1], dtype=torch.float64, device=v.device)
+    pad[:, halo:halo + H, halo:halo + W] = v.double().view(B, H, W, -1)
+    return pad.unfold(1, th + 2 * halo, th).unfold(2, tw + 2 * halo, tw)
+
+
+def _tile_order(p, g):
+    """[B, tiles down, tiles across, ...] -> [T, ...]: raster order (g None) or the block order of the pre-transformed forms."""
+    if g is None:
+        return p.reshape(-1, *p.shape[3:])
+    rest = tuple(range(5, 5 + p.dim() - 3))
+    p = p.reshape(p.shape[0], g['by'], g['TYN'], g['bx'], g['TXN'], *p.shape[3:]).permute(0, 1, 3, 2, 4, *rest)
+    return p.reshape(g['Tp'], *p.shape[5:])
+
+
+def _xform(form, which, v, shape, g, absolute=False):
+    """The float64 contraction M_rows patch M_cols^T of every tile with the TRUE matrices (BT: input side, halo 1; A: gradient side) ->
+    [T, P, Ch]; absolute: the same with |M| on |v| (what every partial sum of the transform is bounded by)."""
+    f = FORM[form]
+    B, H, W = shape
+    Hp, Wp = (g['by'] * g['PH'], g['bx'] * g['PW']) if g else (H, W)
+    p = _tile_order(_patches(v.abs() if absolute else v, shape, f['th'], f['tw'], 1 if which == 'BT' else 0, Hp, Wp), g).contiguous()
+    Mr, Mc = (_m(m, absolute) for m in f[which])
+    out = torch.einsum('ia,tcab,jb->tijc', Mr, p, Mc)
+    return out.reshape(out.shape[0], -1, out.shape[-1])
+
+
+def _wg_map(m, Lp):
+    """(L, seg0, seg0p) -> the physical channels that hold a logical one, in logical order (include/clamd.h)."""
+    L, seg0, seg0p = m
+    out = [p for p in range(Lp) if (p < seg0 if p < seg0p else seg0 + (p - seg0p) < L)]
+    assert len(out) == L
+    return torch.tensor(out, dtype=torch.long, device=DEV)
+
+
+def _u_index(c, pl, n, Np, P):
+    """Float offset of (input channel c, plane pl = 6 i + j, output channel n) in the packed filters U [Kp / 8][P][Np][8]."""
+    return (((c // 8) * P + pl) * Np + n) * 8 + c % 8
+
+
+def _u_unindex(off, Np, P):
+    off, k8 = divmod(off, 8)
+    off, n = divmod(off, Np)
+    kc, pl = divmod(off, P)
+    return 8 * kc + k8, pl, n
+
+
+def _u_layout(U):
+    """[Kp, P, Np] -> U as the pack kernels store it, [Kp / 8][P][Np][8], flat."""
+    Kp, P, Np = U.shape
+    return U.reshape(Kp // 8, 8, P, Np).permute(0, 2, 3, 1).reshape(-1)
+
+
+def _untile(y, g, shape):
+    """[Tp, th, 4, N] output tiles in the block order of the pre-transformed forms -> the image [B, H, W, N] (tiles outside it are cropped)."""
+    B, H, W = shape
+    y = y.reshape(B, g['by'], g['bx'], g['TYN'], g['TXN'], g['th'], 4, -1).permute(0, 1, 3, 5, 2, 4, 6, 7)
+    return y.reshape(B, g['by'] * g['PH'], g['bx'] * g['PW'], -1)[:, :H, :W]

@@ -783,6 +783,33 @@ def test_wino_wgrad_grid_layout_helpers_round_trip(wino_grid):
     wino_grid.check_wino_layout_helpers()
 
 
+@pytest.fixture
+def wino_fwd_grid(monkeypatch):
+    """tests/test_wino_pre_fwd_grid_gpu.py with its tensors on the host (as conv3_grid)."""
+    import grid_util
+    import test_wino_pre_fwd_grid_gpu as grid
+    for mod in (grid_util, grid):
+        monkeypatch.setattr(mod, 'DEV', torch.device('cpu'))
+    return grid
+
+
+def test_wino_pre_fwd_grid_cases_reach_every_plan(wino_fwd_grid):
+    """The rows of test_wino_pre_fwd_grid_gpu.py reach all four instantiations of both forward kernels with every K-loop length, every
+    output width and pitch, and the persistent grid's item classes (two and three items, a slab change, one item, both forced bands)."""
+    wino_fwd_grid.check_wino_fwd_plans()
+
+
+def test_wino_pre_fwd_grid_exact_cases_stay_below_2_24(wino_fwd_grid):
+    """Every hand-placed case keeps every output element and every row's first moments (the low-magnitude cases: the second moments too)
+    below 2^24, and the file's matrices and layouts reproduce the nine-tap direct sums in float64, from the references alone."""
+    wino_fwd_grid.check_wino_fwd_exact_conditions()
+
+
+def test_wino_pre_fwd_grid_layout_helpers_round_trip(wino_fwd_grid):
+    """The packed-filter index helpers round-trip and agree with the vectorised placement; tiles land where the tile order says."""
+    wino_fwd_grid.check_wino_fwd_layout_helpers()
+
+
 def test_bn_launchers_reject_null_pointers_short_pitches_and_empty_sizes(C):
     """clamd_bn_finalize / _apply / _bwd_reduce / _bwd_finalize / _bwd_apply / _bwd_apply_sums / _bwd_eval, clamd_maxpool2x2[_bwd] and
     clamd_channel_sum: a null pointer the selected kernel would dereference, a pitch below Cp, a non-positive B / H / W are refused by a host check -- status -1 (clamd_fail) and that check's message, never -2 (a launch
