@@ -9,9 +9,12 @@ No stock-torch operator is involved and there is no CPU path.
 """
 import torch
 
-from . import _lib, bnops, syncbn
+from . import _lib, bnops, convops, syncbn
 from ._lib import call, ptr
 from .ops import PackTable, TORCH_DT, cpad, from_nhwc, to_nhwc
+from .plan import ALGOS
+
+DIRECT = ALGOS['igemm']      # the generic direct kernels run every 3x3 convolution here, whatever the engine would plan
 
 def _stream():
     return _lib.stream_ptr()
@@ -37,7 +40,7 @@ class _BlockFn(torch.autograd.Function):
                 if (H | W) & 1:
                     raise ValueError('MaxPool2d(2,2) block: H and W must be even')
                 out = torch.empty(B, H // 2, W // 2, cur.shape[-1], dtype=T, device=dev)
-                call('clamd_maxpool2x2', ptr(cur), cur.shape[-1], None, ptr(out), out.shape[-1], B, H, W, cur.shape[-1], dcode, s)
+                convops.maxpool(call, ptr(cur), cur.shape[-1], None, ptr(out), out.shape[-1], B, H, W, cur.shape[-1], dcode, s)
                 saved.append(('pool', cur, H, W))
                 cur, H, W = out, H // 2, W // 2
             elif op[0] == 'crb':
@@ -57,14 +60,14 @@ class _BlockFn(torch.autograd.Function):
                 rows = _lib.stat_rows(_lib.OP_CONV3X3, B, H, W, cin_p, cout_p, dcode)
                 y = torch.empty(B, H, W, cout_p, dtype=T, device=dev)
                 stats = torch.empty(rows, 2, cout_p, dtype=torch.float32, device=dev) if training else None
-                call('clamd_conv3x3', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(y), cout_p, ptr(stats), None, None, rows, B, H, W,
-                     cin_p, cout_p, 1, 1 if 9 * cout_p > B * H * W else 0, dcode, None, s)
+                convops.conv3x3(call, DIRECT, ptr(cur), cin_p, None, ptr(wf), ptr(bias_p), ptr(y), cout_p, ptr(stats), rows, None, B, H, W,
+                                cin_p, cout_p, 1, dcode, None, s)
                 vec = torch.zeros(7, cout_p, dtype=torch.float32, device=dev)       # scale, shift, mean, istd, k0, k1, k2
                 # sync: the statistics of the global batch (as in the UNet engine)
                 red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev) if sync else None
                 bnops.fwd_finalize(stats, rows, gamma.detach(), beta.detach(), rm, rv, nbt, vec, cout_p, cout, float(B * H * W), training or sync, s, red, group)
                 out = torch.empty_like(y)
-                call('clamd_bn_apply', ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(out), cout_p, None, 0, B, H, W, cout_p, dcode, s)
+                convops.bn_apply(call, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(out), cout_p, None, 0, B, H, W, cout_p, dcode, s)
                 saved.append(('crb', cur, y, vec, wd, gamma.detach(), training, sync, (cin, cin_p, cout, cout_p, H, W)))
                 cur = out
             elif op[0] == 'convT':
@@ -80,7 +83,7 @@ class _BlockFn(torch.autograd.Function):
                 tab.vector(b.detach(), bias_p, cout)
                 tab.finalize(dev).run(dcode, s)
                 out = torch.empty(B, 2 * H, 2 * W, cout_p, dtype=T, device=dev)
-                call('clamd_convT2x2_fwd', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(out), cout_p, B, H, W, cin_p, cout_p, dcode, s)
+                convops.convT_fwd(call, ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(out), cout_p, B, H, W, cin_p, cout_p, dcode, s)
                 saved.append(('convT', cur, wd, (cin, cin_p, cout, cout_p, H, W)))
                 cur, H, W = out, 2 * H, 2 * W
             else:                                       # 'head': 1x1 convolution, fp32 NCHW logits straight from the epilogue
@@ -96,7 +99,7 @@ class _BlockFn(torch.autograd.Function):
                 tab.vector(b.detach(), bias_p, k)
                 tab.finalize(dev).run(dcode, s)
                 logits = torch.empty(B, k, H, W, dtype=torch.float32, device=dev)
-                call('clamd_conv1x1_logits', ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(logits), B, H, W, cin_p, kp, k, dcode, s)
+                convops.head_fwd(call, ptr(cur), cin_p, ptr(wf), ptr(bias_p), ptr(logits), None, B, H, W, cin_p, kp, k, dcode, s)
                 saved.append(('head', cur, wd, (cin, cin_p, k, kp, H, W)))
                 cur = None
         ctx.saved_ops, ctx.dcode, ctx.B, ctx.cin0, ctx.group = saved, dcode, B, C, group
@@ -118,32 +121,17 @@ class _BlockFn(torch.autograd.Function):
         gout = gout.contiguous().float()
         for rec in reversed(ctx.saved_ops):
             kind = rec[0]
-            if kind == 'head':
-                _, x, wd, (cin, cin_p, k, kp, H, W) = rec
-                dl = to_nhwc(gout, dcode, cp=kp)
-                gx = torch.empty(B, H, W, cin_p, dtype=T, device=dev)
-                call('clamd_conv1x1', ptr(dl), kp, ptr(wd), None, ptr(gx), cin_p, None, None, None, 0, B, H, W, kp, cin_p, 0, dcode, s)
-                wsb = max(lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_PW, B, H, W, kp, cin_p, dcode), lib.clamd_channel_sum_workspace_bytes(kp))
-                ws = torch.empty(wsb // 4 + 16, dtype=torch.float32, device=dev)
-                dw = torch.empty(k, cin, 1, 1, dtype=torch.float32, device=dev)
-                db = torch.empty(k, dtype=torch.float32, device=dev)
-                call('clamd_wgrad', _lib.WGRAD_PW, ptr(dl), kp, ptr(x), cin_p, ptr(ws), wsb, ptr(dw), B, H, W, kp, cin_p, k, cin,
-                     k, kp, cin, cin_p, dcode, None, s)
-                call('clamd_channel_sum', ptr(dl), kp, ptr(db), B * H * W, kp, k, dcode, ptr(ws), wsb, None, s)
-                grads = [dw, db] + grads
-                g = gx
-            elif kind == 'convT':
+            if kind in ('head', 'convT'):      # the tail: data gradient, then d weight in the parameter's own layout and d bias
                 _, x, wd, (cin, cin_p, cout, cout_p, H, W) = rec
                 gy = to_nhwc(gout, dcode, cp=cout_p) if g is None else g
                 gx = torch.empty(B, H, W, cin_p, dtype=T, device=dev)
-                call('clamd_convT2x2_dgrad', ptr(gy), cout_p, ptr(wd), ptr(gx), cin_p, None, None, 0, B, H, W, cin_p, cout_p, dcode, s)
-                wsb = max(lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_UP2, B, H, W, cin_p, cout_p, dcode), lib.clamd_channel_sum_workspace_bytes(cout_p))
-                ws = torch.empty(wsb // 4 + 16, dtype=torch.float32, device=dev)
-                dw = torch.empty(cin, cout, 2, 2, dtype=torch.float32, device=dev)
+                convops.tail_dgrad(call, kind, ptr(gy), cout_p, ptr(wd), ptr(gx), cin_p, None, B, H, W, cin_p, cout_p, dcode, s)
+                wsb = convops.tail_workspace_bytes(lib, kind, B, H, W, cin_p, cout_p, dcode)
+                ws = torch.empty(convops.workspace_floats(wsb), dtype=torch.float32, device=dev)
+                dw = torch.empty((cout, cin, 1, 1) if kind == 'head' else (cin, cout, 2, 2), dtype=torch.float32, device=dev)
                 db = torch.empty(cout, dtype=torch.float32, device=dev)
-                call('clamd_wgrad', _lib.WGRAD_UP2, ptr(x), cin_p, ptr(gy), cout_p, ptr(ws), wsb, ptr(dw), B, H, W, cin_p, cout_p, cin, cout,
-                     cin, cin_p, cout, cout_p, dcode, None, s)
-                call('clamd_channel_sum', ptr(gy), cout_p, ptr(db), B * 4 * H * W, cout_p, cout, dcode, ptr(ws), wsb, None, s)
+                convops.tail_wgrad(call, kind, ptr(x), cin_p, ptr(gy), cout_p, ptr(ws), wsb, ptr(dw), B, H, W, cin, cin_p, cout, cout_p, dcode, None, s)
+                convops.tail_bias_grad(call, kind, ptr(gy), cout_p, ptr(db), B, H, W, cout, cout_p, dcode, ptr(ws), wsb, None, s)
                 grads = [dw, db] + grads
                 g = gx
             elif kind == 'crb':
@@ -154,32 +142,31 @@ class _BlockFn(torch.autograd.Function):
                 if training:
                     rows = _lib.stat_rows(_lib.OP_BN_BWD_REDUCE, B, H, W, 0, cout_p, dcode)
                     sums = torch.empty(rows, lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float32, device=dev)
-                    call('clamd_bn_bwd_reduce', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
-                         B, H, W, cout_p, dcode, None, s)
+                    convops.bn_bwd_reduce(call, ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(sums), rows,
+                                          B, H, W, cout_p, dcode, None, s)
                     scratch = None
                     if sync:   # g_z from the sums of the global batch; d gamma, d beta, d conv-bias from this rank's own (as torch)
                         red = torch.empty(2 * cout_p + 1, dtype=torch.float64, device=dev)
                         scratch = (torch.empty(lib.clamd_bn_bwd_nsums(), cout_p, dtype=torch.float64, device=dev), red)
                     bnops.bwd_finalize(sums, rows, lib.clamd_bn_bwd_nsums(), gamma, vec, ptr(dgamma), ptr(dbeta), ptr(dbias), cout_p, cout,
                                        float(B * H * W), s, scratch, ctx.group)
-                    call('clamd_bn_bwd_apply', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
-                         B, H, W, cout_p, dcode, s)
+                    convops.bn_bwd_apply(call, ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(vec[4]), ptr(gz), cout_p,
+                                         B, H, W, cout_p, dcode, s)
                 else:      # running statistics: one pass writes g_z and the rows of the parameter gradients
                     rows = lib.clamd_bn_bwd_eval_rows(B, H, W, cout_p, 0)
                     if rows <= 0:
                         _lib.check(rows, 'clamd_bn_bwd_eval_rows')
                     er = torch.empty(rows, 3, cout_p, dtype=torch.float32, device=dev)
-                    call('clamd_bn_bwd_eval', ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(gz), cout_p, ptr(er), rows,
-                         B, H, W, cout_p, cout, dcode, s)
+                    convops.bn_bwd_eval(call, ptr(ga), cout_p, None, 0, ptr(y), cout_p, ptr(vec[0]), ptr(vec[1]), ptr(gz), cout_p, ptr(er), rows,
+                                        B, H, W, cout_p, cout, dcode, s)
                     bnops.bwd_eval_finalize(er, rows, 3, vec, False, ptr(dgamma), ptr(dbeta), ptr(dbias), cout_p, cout, s)
                 gx = torch.empty(B, H, W, cin_p, dtype=T, device=dev)
-                call('clamd_conv3x3', ptr(gz), cout_p, ptr(wd), None, ptr(gx), cin_p, None, None, None, 0, B, H, W, cout_p, cin_p, 0,
-                     1 if 9 * cin_p > B * H * W else 0, dcode, None, s)
-                wsb = lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_CONV3, B, H, W, cout_p, cin_p, dcode)
-                ws = torch.empty(wsb // 4 + 16, dtype=torch.float32, device=dev)
+                convops.conv3x3(call, DIRECT, ptr(gz), cout_p, None, ptr(wd), None, ptr(gx), cin_p, None, 0, None, B, H, W, cout_p, cin_p, 0, dcode, None, s)
+                wsb = DIRECT.wg_ws(lib, B, H, W, cout_p, cin_p, dcode)
+                ws = torch.empty(convops.workspace_floats(wsb), dtype=torch.float32, device=dev)
                 dw = torch.empty(cout, cin, 3, 3, dtype=torch.float32, device=dev)
-                call('clamd_wgrad', _lib.WGRAD_CONV3, ptr(gz), cout_p, ptr(x), cin_p, ptr(ws), wsb, ptr(dw), B, H, W, cout_p, cin_p, cout, cin,
-                     cout, cout_p, cin, cin_p, dcode, None, s)
+                convops.wgrad3x3(call, DIRECT, ptr(gz), cout_p, ptr(x), cin_p, None, None, ptr(ws), wsb, ptr(dw), B, H, W, cout_p, cin_p, cout, cin,
+                                 cin, cin_p, dcode, None, s)
                 grads = [dw, dbias, dgamma, dbeta] + grads
                 g = gx
             else:                                                       # 'pool'
@@ -187,7 +174,7 @@ class _BlockFn(torch.autograd.Function):
                 cp = x.shape[-1]
                 gp = to_nhwc(gout, dcode, cp=cp) if g is None else g
                 gx = torch.empty(B, H, W, cp, dtype=T, device=dev)
-                call('clamd_maxpool2x2_bwd', ptr(x), cp, None, ptr(gp), cp, ptr(gx), cp, B, H, W, cp, dcode, s)
+                convops.maxpool_bwd(call, ptr(x), cp, None, ptr(gp), cp, ptr(gx), cp, B, H, W, cp, dcode, s)
                 g = gx
         gin = from_nhwc(g, ctx.cin0, dcode) if ctx.needs_input_grad[0] else None
         return (gin, None) + tuple(grads)

@@ -3,11 +3,12 @@ schedules of the forward and backward pass.  `_Unit` / `_Tail` declare what a co
 `_Streams` owns the side streams and every wait between them; `_Engine` allocates, wires the BatchNorm placement and launches.  The
 switches and KERNEL_TIMING are attributes of unet.py (tests, tools and bench.py assign them there) and are read from it when used."""
 import weakref
+from functools import partial
 
 import torch
 import torch.nn as nn
 
-from . import _lib, bnops, syncbn, unet as U
+from . import _lib, bnops, convops, syncbn, unet as U
 from ._lib import call, ptr, tune_ptr
 from .ops import PackTable, WinoPackTable, cpad
 from .plan import ALGOS, plan_net
@@ -31,8 +32,10 @@ def _timed(tag, flops, nbytes, unit, name, *args):
     """A launch; with unet.KERNEL_TIMING set, between two HIP events on the current stream.  `unit` = (conv unit and direction, fraction
     of its algorithmic FLOPs the kernel executes -- Winograd: 16/36 or 24/72): _Unit.tag."""
     kt = U.KERNEL_TIMING
-    if kt is None:
-        call(name, *args)
+    if kt is None:         # _lib.call written out: the launches of a step come through here, and every Python frame in between is host time per launch
+        rc = getattr(_lib.load(), name)(*args)
+        if rc:
+            _lib.check(rc, name)
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -48,6 +51,11 @@ def _hbm(family, nbytes, name, *args):
     _timed('hbm:' + family, 0.0, nbytes, ('', 1.0), name, *args)
 
 
+def _hbm_run(family, nbytes):
+    """_hbm with family and bytes bound: the `run` of a convops launch."""
+    return partial(_timed, 'hbm:' + family, 0.0, nbytes, ('', 1.0))
+
+
 class _FoldSource:
     """What a folded convolution reads instead of a normalised tensor: the raw tensor (`y`, pitch `cout_p`) and the per-input-channel
     scale / shift (`vec[0]`, `vec[1]`) that live in its filters and bias table -- the interface of the producing _Unit the pair fold uses."""
@@ -58,8 +66,8 @@ class _FoldSource:
 
 
 def _sums_into(c):
-    """(y, sums, rows) arguments of a data-gradient launch that accumulates the BatchNorm-backward sums of unit c (plan.Unit.sums_by), or none."""
-    return (ptr(c.y), ptr(c.sums), c.sum_rows) if c is not None else (None, None, 0)
+    """convops' `fused`: the data-gradient launch accumulates the BatchNorm-backward sums of unit c (plan.Unit.sums_by), or None."""
+    return (ptr(c.y), ptr(c.sums), c.sum_rows) if c is not None else None
 
 
 class _Declared:
@@ -90,7 +98,7 @@ class _Unit(_Declared):
         'gz', 'g_in', 'g_src',              # d y; data-gradient target (None at enc1.0); (d out, its pitch, d pooled or None)
         'vx',                               # pre-transformed input, kept for the weight gradient (None unless f.pre)
         'wf', 'wd', 'bias_p', 'pack_late',  # packed forward / data-gradient (None at enc1.0) filters, padded bias; packed by the late tables?
-        'vec', 'm_fastest',                 # seven [Cout_p] rows: scale, shift, mean, istd, k0, k1, k2 (4-6 contiguous); direct forward grid order
+        'vec',                              # seven [Cout_p] rows: scale, shift, mean, istd, k0, k1, k2 (4-6 contiguous)
         # ---- BatchNorm placement (from the plan; one direction only, no cycles)
         'consumer', 'sum_src', 'fused_reduce',      # unit whose backward sums our data gradient accumulates; _Unit / _Tail that accumulates ours (is not None)
         'fold_src', 'apply_folded',         # unit whose BatchNorm our input transform applies; ours is applied by a reader's transform
@@ -369,7 +377,7 @@ class _Engine:
             u.wd = None if u.d is None else torch.zeros(u.d.taps * u.cin_p * u.cout_p, dtype=T, device=dev)
             u.bias_p = torch.zeros(u.cout_p, dtype=torch.float32, device=dev)
             u.vec = list(torch.zeros(7, u.cout_p, dtype=torch.float32, device=dev))
-            u.m_fastest, u.y_ldc = (1 if 9 * u.cout_p > B * u.h * u.width else 0), u.cout_p
+            u.y_ldc = u.cout_p
             u.fused_reduce = p.sums_by is not None                            # BatchNorm placement: wired from the plan below
             u.tag = {k: (f'{p.name} {k}', ALGOS[a].frac if a else 1.0) for k, a in (('fwd', p.fwd), ('dgrad', p.dgrad), ('wgrad', p.wgrad))}
             u.apply_folded = u.apply_in_filters = u.fold_on = u.pool_fold = False
@@ -458,10 +466,8 @@ class _Engine:
             ws = max(ws, lib.clamd_channel_sum_workspace_bytes(u.cout_p), u.g.wg_ws(lib, B, u.h, u.width, u.cout_p, u.cin_p, self.dcode),
                      ALGOS['igemm'].wg_ws(lib, B, u.h, u.width, u.cout_p, u.cin_p, self.dcode))
         for t in self.tails:
-            mode = _lib.WGRAD_UP2 if t.kind == 'convT' else _lib.WGRAD_PW
-            rp, cp_ = (t.cin_p, t.cout_p) if t.kind == 'convT' else (t.cout_p, t.cin_p)
-            ws = max(ws, lib.clamd_wgrad_workspace_bytes(mode, B, H >> t.level, W >> t.level, rp, cp_, self.dcode))
-        self.ws = torch.empty(ws // 4 + 16, dtype=torch.float32, device=dev)
+            ws = max(ws, convops.tail_workspace_bytes(lib, t.kind, B, H >> t.level, W >> t.level, t.cin_p, t.cout_p, self.dcode))
+        self.ws = torch.empty(convops.workspace_floats(ws), dtype=torch.float32, device=dev)
         # scratch of the pre-transformed kernels: the transformed gradient of the data-gradient launch (main stream) and the
         # gradient-side operand of the weight-gradient GEMM (second stream); launches on one stream are serialised, so one each
         nvg = max([getattr(lib, u.d.x_elems)(B, u.h, u.width, u.cout_p) for u in convs if u.d is not None and u.d.pre] + [0])
@@ -623,20 +629,21 @@ class _Engine:
                      ptr(t.bias_fold), t.cout, t.cin, t.cout_p, s)
                 tx, tx_ldc, tbias = fb.y, fb.cout_p, t.bias_fold
             if t.kind == 'convT':
-                _hbm('convT', self.esize * (B * h * w * (t.cin + 4 * t.cout) + 4 * t.cin * t.cout),
-                     'clamd_convT2x2_fwd', ptr(t.x), t.x.shape[-1], ptr(t.wf), ptr(t.bias_p), ptr(t.y_slice), t.y_ldc, B, h, w, t.cin_p, t.cout_p, dc, s)
-            elif predict and t.cout_p <= 64:      # arg-max fused into the head's epilogue: the logits never reach HBM
+                convops.convT_fwd(_hbm_run('convT', self.esize * (B * h * w * (t.cin + 4 * t.cout) + 4 * t.cin * t.cout)),
+                                  ptr(t.x), t.x.shape[-1], ptr(t.wf), ptr(t.bias_p), ptr(t.y_slice), t.y_ldc, B, h, w, t.cin_p, t.cout_p, dc, s)
+                continue
+            head, geo = (ptr(tx), tx_ldc, ptr(t.wf), ptr(tbias)), (B, h, w, t.cin_p, t.cout_p, self.K, dc, s)
+            if predict and t.cout_p <= 64:      # arg-max fused into the head's epilogue: the logits never reach HBM
                 logits = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
-                call('clamd_conv1x1_argmax', ptr(tx), tx_ldc, ptr(t.wf), ptr(tbias), ptr(logits), None, B, h, w, t.cin_p, t.cout_p, self.K, dc, s)
+                convops.head_fwd(call, *head, None, ptr(logits), *geo)
             elif predict:      # more than 64 (padded) classes: the fused epilogue holds one 64-class slab; logits, then arg-max
                 lg = torch.empty(B, self.K, H, W, dtype=torch.float32, device=self.dev)
-                call('clamd_conv1x1_logits', ptr(tx), tx_ldc, ptr(t.wf), ptr(tbias), ptr(lg), B, h, w, t.cin_p, t.cout_p, self.K, dc, s)
+                convops.head_fwd(call, *head, ptr(lg), None, *geo)
                 logits = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
                 call('clamd_argmax_confusion', ptr(lg), None, ptr(logits), None, B, self.K, 1, H, W, s)
             else:
                 logits = torch.empty(B, self.K, H, W, dtype=torch.float32, device=self.dev)
-                _hbm('head', B * h * w * (self.esize * t.cin + 4 * self.K),
-                     'clamd_conv1x1_logits', ptr(tx), tx_ldc, ptr(t.wf), ptr(tbias), ptr(logits), B, h, w, t.cin_p, t.cout_p, self.K, dc, s)
+                convops.head_fwd(_hbm_run('head', B * h * w * (self.esize * t.cin + 4 * self.K)), *head, ptr(logits), None, *geo)
         st_.join_forward()
         return logits
 
@@ -689,8 +696,8 @@ class _Engine:
         # the BatchNorm of the unit in front folded into the transform where nothing else reads its output (u.fold_src)
         f = u.fold_src
         xsrc, xldc, fs, fh = (f.y, f.cout_p, f.vec[0], f.vec[1]) if f is not None else (u.xin, u.xin_ldc, None, None)
-        _timed('wino_transform', 0.0, u.f.x_bytes * self.B * u.h * u.width * u.cin_p, u.tag['fwd'], u.f.xform, ptr(xsrc), xldc, ptr(fs), ptr(fh), ptr(u.vx),
-               self.B, u.h, u.width, u.cin_p, s)
+        convops.wino_transform(partial(_timed, 'wino_transform', 0.0, u.f.x_bytes * self.B * u.h * u.width * u.cin_p, u.tag['fwd']), u.f,
+                               ptr(xsrc), xldc, ptr(fs), ptr(fh), ptr(u.vx), self.B, u.h, u.width, u.cin_p, s)
 
     def _fwd_fold(self, u, s):
         """Forward filters of a fold candidate (bnfold.hip): packed here, behind the producer's bn_finalize -- with its scale and the
@@ -707,33 +714,22 @@ class _Engine:
 
     def _fwd_conv(self, u, training, s):
         """conv3x3 + bias + ReLU (+ BatchNorm statistics rows) of unit u."""
-        dc, tp = self.dcode, tune_ptr(self.tuning)
         if u.pack_late:
             self.streams.need_late_pack()
         elif u is self.convs[min(self.pack_late_at, len(self.convs) - 1)]:
             self.streams.release_late_pack()
-        Bl, tag = self.B, u.tag['fwd']
-        rows, st, y = u.stat_rows, (u.stats if training else None), u.y
+        if u.f.wino:
+            self.streams.need_wino_filters(u)
+        Bl = self.B
         xin, xin_ldc, bias, relu = u.xin, u.xin_ldc, u.bias_p, 1
         if u.fold_on:      # reads the producer's conv+ReLU output; its BatchNorm lives in the filters and in the bias table
             xin, xin_ldc, bias, relu = u.fold_a.y, u.fold_a.cout_p, u.cb, 3
-        flops = 2.0 * Bl * u.h * u.width * 9 * u.cin * u.cout
-        nbytes = self._conv_bytes(u)
-        if u.f.taps == 1:     # im2col
-            _hbm('enc1.0', self.esize * Bl * u.h * u.width * (u.cin_p + u.cout),
-                 'clamd_conv1x1', ptr(xin), u.xin_ldc, ptr(u.wf), ptr(u.bias_p), ptr(y), u.cout_p,
-                 ptr(st), None, None, rows, Bl, u.h, u.width, u.cin_p, u.cout_p, 1, dc, s)
-        elif u.f.wino:
-            self.streams.need_wino_filters(u)
-            if u.f.pre:
-                _timed('igemm_conv3x3', flops, nbytes, tag, u.f.conv, ptr(u.vx), ptr(u.wf), ptr(u.bias_p), ptr(y), u.cout_p,
-                       ptr(st), rows, Bl, u.h, u.width, u.cin_p, u.cout_p, 1, tp, s)
-            else:
-                _timed('igemm_conv3x3', flops, nbytes, tag, u.f.conv, ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.y_ldc, ptr(st), rows,
-                       Bl, u.h, u.width, u.cin_p, u.cout_p, relu, tp, s)
+        if u.f.taps == 1:     # im2col: HBM-bound, timed as such
+            run = _hbm_run('enc1.0', self.esize * Bl * u.h * u.width * (u.cin_p + u.cout))
         else:
-            _timed('igemm_conv3x3', flops, nbytes, tag, u.f.conv, ptr(xin), xin_ldc, ptr(u.wf), ptr(bias), ptr(y), u.cout_p,
-                   ptr(st), None, None, rows, Bl, u.h, u.width, u.cin_p, u.cout_p, relu, u.m_fastest, dc, tp, s)
+            run = partial(_timed, 'igemm_conv3x3', 2.0 * Bl * u.h * u.width * 9 * u.cin * u.cout, self._conv_bytes(u), u.tag['fwd'])
+        convops.conv3x3(run, u.f, ptr(xin), xin_ldc, ptr(u.vx), ptr(u.wf), ptr(bias), ptr(u.y), u.y_ldc, ptr(u.stats if training else None), u.stat_rows,
+                        None, Bl, u.h, u.width, u.cin_p, u.cout_p, relu, self.dcode, tune_ptr(self.tuning), s)
 
     def _fwd_finalize(self, u, training, s):
         # (num_batches_tracked += 1 inside the launch: it was a torch._foreach_add_ on the critical chain)
@@ -745,15 +741,15 @@ class _Engine:
         if u.apply_folded:          # the only reader of the BatchNorm output is the next convolution's input transform
             return
         if u.pool_fold:             # ... or the filters and bias tables of both readers of an encoder block's output: only the pooling is left
-            _hbm('bn_fwd', self.esize * self.B * u.h * u.width * u.cout * 5 // 4,
-                 'clamd_maxpool2x2', ptr(u.y), u.y_ldc, ptr(u.vec[0]), ptr(u.pooled), u.pooled.shape[-1], self.B, u.h, u.width, u.cout_p, self.dcode, s)
+            convops.maxpool(_hbm_run('bn_fwd', self.esize * self.B * u.h * u.width * u.cout * 5 // 4),
+                            ptr(u.y), u.y_ldc, ptr(u.vec[0]), ptr(u.pooled), u.pooled.shape[-1], self.B, u.h, u.width, u.cout_p, self.dcode, s)
             return
         if u.apply_in_filters:      # ... or its filters and bias table (bnfold.hip)
             return
         v = u.vec
-        _hbm('bn_fwd', self.esize * self.B * u.h * u.width * u.cout * (9 if u.pooled is not None else 8) // 4,
-             'clamd_bn_apply', ptr(u.y), u.cout_p, ptr(v[0]), ptr(v[1]), ptr(u.out), u.out_ldc,
-             ptr(u.pooled), u.pooled.shape[-1] if u.pooled is not None else 0, self.B, u.h, u.width, u.cout_p, self.dcode, s)
+        convops.bn_apply(_hbm_run('bn_fwd', self.esize * self.B * u.h * u.width * u.cout * (9 if u.pooled is not None else 8) // 4),
+                         ptr(u.y), u.cout_p, ptr(v[0]), ptr(v[1]), ptr(u.out), u.out_ldc,
+                         ptr(u.pooled), u.pooled.shape[-1] if u.pooled is not None else 0, self.B, u.h, u.width, u.cout_p, self.dcode, s)
 
     # ------------------------------------------------------------------------------------------ backward
     def backward(self, gout):
@@ -789,40 +785,28 @@ class _Engine:
             t = st.get('tail')
             if t is not None:
                 h, w = H >> t.level, W >> t.level
+                gy, gy_ldc, tx, tx_ldc, fb = t.gy_slice, t.y_ldc, t.x, t.x.shape[-1], t.fold_b
+                nbytes = self.esize * (B * h * w * (t.cin + 4 * t.cout) + 4 * t.cin * t.cout)
                 if t.kind == 'head':
                     src = self.dl_src
                     if not (src is not None and src[1:] == (gout.data_ptr(), gout._version, self.generation)):
                         # not the tensor this package's loss wrote beside its NHWC copy (another loss, a hook, a sum of gradients): convert
                         call('clamd_nchw_to_nhwc', ptr(gout), ptr(self.dl), self.Kp, B, self.K, H, W, self.Kp, 1.0, dc, s)
                     self.dl_src = None
-                    _hbm('head', self.esize * B * h * w * (self.Kp + t.cin),
-                         'clamd_conv1x1', ptr(self.dl), self.Kp, ptr(t.wd), None, ptr(t.g_x), t.g_x.shape[-1], None,
-                         *_sums_into(t.consumer), B, h, w, t.cout_p, t.cin_p, 0, dc, s)
-                    sw = self.streams.param_grad_stream()      # parameter gradients on the second stream, behind the data gradient (see _conv_bwd)
-                    fb = t.fold_b
-                    tx, tx_ldc = (fb.y, fb.cout_p) if fb is not None else (t.x, t.x.shape[-1])
-                    _hbm('head', self.esize * B * h * w * (self.Kp + t.cin),
-                         'clamd_wgrad', _lib.WGRAD_PW, ptr(self.dl), self.Kp, ptr(tx), tx_ldc, ptr(self.ws),
-                         self.ws_bytes, g[t.keys[0]], B, h, w, t.cout_p, t.cin_p, t.cout, t.cin,
-                         t.cout, t.cout_p, t.cin, t.cin_p, dc, tp, sw)
-                    _hbm('head', 0,                # algorithmically free: d logits was just streamed by the weight gradient above
-                         'clamd_channel_sum', ptr(self.dl), self.Kp, g[t.keys[1]], B * h * w, self.Kp, t.cout, dc,
-                         ptr(self.ws), self.ws_bytes, tp, sw)
-                    if fb is not None:      # the weight gradient ran on the un-normalised tensor: dW = scale * dW + shift * (bias gradient)
-                        call('clamd_bn_fold_wgrad_pointwise', g[t.keys[1]], ptr(fb.vec[0]), ptr(fb.vec[1]), g[t.keys[0]], t.cout, t.cin, sw)
-                else:
-                    ctb = self.esize * (B * h * w * (t.cin + 4 * t.cout) + 4 * t.cin * t.cout)
-                    _hbm('convT', ctb,
-                         'clamd_convT2x2_dgrad', ptr(t.gy_slice), t.y_ldc, ptr(t.wd), ptr(t.g_x), t.g_x.shape[-1],
-                         *_sums_into(t.consumer), B, h, w, t.cin_p, t.cout_p, dc, s)
-                    sw = self.streams.param_grad_stream()
-                    _hbm('convT', ctb,
-                         'clamd_wgrad', _lib.WGRAD_UP2, ptr(t.x), t.x.shape[-1], ptr(t.gy_slice), t.y_ldc, ptr(self.ws),
-                         self.ws_bytes, g[t.keys[0]], B, h, w, t.cin_p, t.cout_p, t.cin, t.cout,
-                         t.cin, t.cin_p, t.cout, t.cout_p, dc, tp, sw)
-                    _hbm('convT', 0,               # algorithmically free: the gradient was just streamed by the weight gradient above
-                         'clamd_channel_sum', ptr(t.gy_slice), t.y_ldc, g[t.keys[1]], B * 4 * h * w, t.cout_p,
-                         t.cout, dc, ptr(self.ws), self.ws_bytes, tp, sw)
+                    gy, gy_ldc, nbytes = self.dl, self.Kp, self.esize * B * h * w * (self.Kp + t.cin)
+                    if fb is not None:      # the folded head read the last unit's conv+ReLU output
+                        tx, tx_ldc = fb.y, fb.cout_p
+                run = _hbm_run(t.kind, nbytes)
+                convops.tail_dgrad(run, t.kind, ptr(gy), gy_ldc, ptr(t.wd), ptr(t.g_x), t.g_x.shape[-1], _sums_into(t.consumer),
+                                   B, h, w, t.cin_p, t.cout_p, dc, s)
+                sw = self.streams.param_grad_stream()      # parameter gradients on the second stream, behind the data gradient (see _conv_bwd)
+                convops.tail_wgrad(run, t.kind, ptr(tx), tx_ldc, ptr(gy), gy_ldc, ptr(self.ws), self.ws_bytes, g[t.keys[0]],
+                                   B, h, w, t.cin, t.cin_p, t.cout, t.cout_p, dc, tp, sw)
+                # algorithmically free: the gradient was just streamed by the weight gradient above
+                convops.tail_bias_grad(_hbm_run(t.kind, 0), t.kind, ptr(gy), gy_ldc, g[t.keys[1]], B, h, w, t.cout, t.cout_p, dc,
+                                       ptr(self.ws), self.ws_bytes, tp, sw)
+                if fb is not None:      # the weight gradient ran on the un-normalised tensor: dW = scale * dW + shift * (bias gradient)
+                    call('clamd_bn_fold_wgrad_pointwise', g[t.keys[1]], ptr(fb.vec[0]), ptr(fb.vec[1]), g[t.keys[0]], t.cout, t.cin, sw)
             for u in reversed(st['convs']):
                 self._conv_bwd(u, s)
             if sync is not None:
@@ -844,9 +828,9 @@ class _Engine:
             # eval-mode BatchNorm (running statistics): g_z = [y>0] scale g needs no reduction -- ONE pass writes it and the rows of
             # sum g, sum g y, sum g_z; the parameter gradients are formed off the critical chain, on the second stream, where this unit's
             # weight gradient and its fold fix-up (which read the conv-bias gradient) follow in stream order
-            _hbm('bn_bwd', self.esize * B * u.h * u.width * u.cout * (13 if gp is not None else 12) // 4,
-                 'clamd_bn_bwd_eval', ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
-                 ptr(v[0]), ptr(v[1]), ptr(u.gz), u.cout_p, ptr(u.eval_rows), u.eval_nrows, B, u.h, u.width, u.cout_p, u.cout, dc, s)
+            convops.bn_bwd_eval(_hbm_run('bn_bwd', self.esize * B * u.h * u.width * u.cout * (13 if gp is not None else 12) // 4),
+                                ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
+                                ptr(v[0]), ptr(v[1]), ptr(u.gz), u.cout_p, ptr(u.eval_rows), u.eval_nrows, B, u.h, u.width, u.cout_p, u.cout, dc, s)
             bnops.bwd_eval_finalize(u.eval_rows, u.eval_nrows, 3, v, False, dgamma, dbeta, dbias, u.cout_p, u.cout, streams.param_grad_stream())
         else:
             if not u.bn_train:
@@ -855,27 +839,27 @@ class _Engine:
                 bnops.bwd_eval_finalize(u.sums, u.sum_rows, self.NS, v, True, dgamma, dbeta, None if two else dbias, u.cout_p, u.cout, s)
             else:
                 if not u.fused_reduce:     # otherwise the five sums were accumulated by the epilogue of the kernel that wrote `ga`
-                    _hbm('bn_bwd', 0,                      # algorithmically free: one backward pass reads g and y once (the apply pass below is charged for it)
-                         'clamd_bn_bwd_reduce', ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
-                         ptr(v[0]), ptr(v[1]), ptr(u.sums), u.sum_rows, B, u.h, u.width, u.cout_p, dc, tp, s)
+                    # algorithmically free: one backward pass reads g and y once (the apply pass below is charged for it)
+                    convops.bn_bwd_reduce(_hbm_run('bn_bwd', 0), ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
+                                          ptr(v[0]), ptr(v[1]), ptr(u.sums), u.sum_rows, B, u.h, u.width, u.cout_p, dc, tp, s)
                 bnops.bwd_finalize(u.sums, u.sum_rows, self.NS, u.gamma, v, dgamma, dbeta, None if two else dbias, u.cout_p, u.cout, count, s,
                                    (u.sync_tot, u.sync_red) if u.bn_sync else None, self.bn_group)
             if two:
                 assert gp is None
-                _hbm('bn_bwd', self.esize * B * u.h * u.width * u.cout * 3,
-                     'clamd_bn_bwd_apply_sums', ptr(ga), ga_ldc, ptr(u.y), u.y_ldc, ptr(v[4]), ptr(u.gz), u.cout_p, ptr(u.gz_rows), u.gz_nrows,
-                     B, u.h, u.width, u.cout_p, dc, s)
+                convops.bn_bwd_apply_sums(_hbm_run('bn_bwd', self.esize * B * u.h * u.width * u.cout * 3),
+                                          ptr(ga), ga_ldc, ptr(u.y), u.y_ldc, ptr(v[4]), ptr(u.gz), u.cout_p, ptr(u.gz_rows), u.gz_nrows,
+                                          B, u.h, u.width, u.cout_p, dc, s)
             else:
-                _hbm('bn_bwd', self.esize * B * u.h * u.width * u.cout * (13 if gp is not None else 12) // 4,
-                     'clamd_bn_bwd_apply', ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
-                     ptr(v[0]), ptr(v[1]), ptr(v[4]), ptr(u.gz), u.cout_p, B, u.h, u.width, u.cout_p, dc, s)
+                convops.bn_bwd_apply(_hbm_run('bn_bwd', self.esize * B * u.h * u.width * u.cout * (13 if gp is not None else 12) // 4),
+                                     ptr(ga), ga_ldc, ptr(gp), gp_ldc, ptr(u.y), u.y_ldc,
+                                     ptr(v[0]), ptr(v[1]), ptr(v[4]), ptr(u.gz), u.cout_p, B, u.h, u.width, u.cout_p, dc, s)
         c_seg0, c_seg0p = u.cin_segs[0] if len(u.cin_segs) == 2 else (u.cin, u.cin_p)
         flops, nbytes = 2.0 * B * u.h * u.width * 9 * u.cin * u.cout, self._conv_bytes(u)
         gz_arg, yt = ptr(u.gz), self.yt       # a pre-transformed weight gradient transforms gz into yt itself, in front of its GEMM ...
         if u.g.pre:                           # ... unless the third stream does: then the GEMM takes no gz and reads the buffer it was given
             sx, buf = streams.wgrad_transform_stream((self.yt, self.yt2))
             if sx is not None:
-                call(u.g.wg_xform, gz_arg, u.cout_p, ptr(buf), B, u.h, u.width, u.cout_p, sx)
+                convops.wgrad_transform(call, u.g, gz_arg, u.cout_p, ptr(buf), B, u.h, u.width, u.cout_p, sx)
                 streams.wgrad_transformed()
                 gz_arg, yt = None, buf
         # The weight gradient may start once the data gradient of the same unit has FINISHED (the second stream's wait is
@@ -891,41 +875,26 @@ class _Engine:
         sw = streams.param_grad_stream() if early else None
         if u.d is not None:
             tag, gi = u.tag['dgrad'], u.g_in
-            if u.d.pre:
-                _timed('wino_transform', 0.0, u.d.x_bytes * B * u.h * u.width * u.cout_p, tag, u.d.xform, ptr(u.gz), u.cout_p, None, None, ptr(self.vg),
-                       B, u.h, u.width, u.cout_p, s)
-                _timed('igemm_conv3x3', flops, nbytes, tag, u.d.conv, ptr(self.vg), ptr(u.wd), None, ptr(gi), gi.shape[-1], None, 0,
-                       B, u.h, u.width, u.cout_p, u.cin_p, 0, tp, s)
-            elif u.d.wino:
-                _timed('igemm_conv3x3', flops, nbytes, tag, u.d.conv, ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(gi), gi.shape[-1], None, 0,
-                       B, u.h, u.width, u.cout_p, u.cin_p, 0, tp, s)
-            else:
-                _timed('igemm_conv3x3', flops, nbytes, tag, u.d.conv, ptr(u.gz), u.cout_p, ptr(u.wd), None, ptr(gi), gi.shape[-1], None,
-                       *_sums_into(u.consumer), B, u.h, u.width, u.cout_p, u.cin_p, 0, 1 if 9 * u.cin_p > B * u.h * u.width else 0, dc, tp, s)
+            if u.d.pre:       # the transformed gradient is used once and not kept
+                convops.wino_transform(partial(_timed, 'wino_transform', 0.0, u.d.x_bytes * B * u.h * u.width * u.cout_p, tag), u.d,
+                                       ptr(u.gz), u.cout_p, None, None, ptr(self.vg), B, u.h, u.width, u.cout_p, s)
+            convops.conv3x3(partial(_timed, 'igemm_conv3x3', flops, nbytes, tag), u.d, ptr(u.gz), u.cout_p, ptr(self.vg), ptr(u.wd), None,
+                            ptr(gi), gi.shape[-1], None, 0, _sums_into(u.consumer), B, u.h, u.width, u.cout_p, u.cin_p, 0, dc, tp, s)
         if sw is None:
             sw = streams.param_grad_stream()
         if two:      # off the critical chain: the fixed-order sum of the apply pass's rows, in front of this unit's weight gradient
             call('clamd_rows_sum', ptr(u.gz_rows), u.gz_nrows, dbias, u.cout_p, u.cout, sw)
-        if u.g.taps == 1:     # im2col: a pointwise weight gradient
-            _hbm('enc1.0', self.esize * B * u.h * u.width * (u.cout + u.cin_p),
-                 u.g.wgrad, _lib.WGRAD_PW, ptr(u.gz), u.cout_p, ptr(u.xin), u.xin_ldc, ptr(self.ws), self.ws_bytes,
-                 g[u.keys[0]], B, u.h, u.width, u.cout_p, u.cin_p, u.cout, 9 * u.cin, u.cout, u.cout_p, 9 * u.cin, u.cin_p, dc, tp, sw)
-            return
-        tag = u.tag['wgrad']
-        xin, xin_ldc = (u.fold_a.y, u.fold_a.cout_p) if u.fold_on else (u.xin, u.xin_ldc)      # a fold candidate reads the raw tensor
-        if u.g.pre:
-            if gz_arg is None:
-                streams.wgrad_after_transform()
-            _timed('wgrad_conv3x3', flops, nbytes, tag, u.g.wgrad, gz_arg, u.cout_p, ptr(u.vx), ptr(yt), ptr(self.ws), self.ws_bytes,
-                   g[u.keys[0]], B, u.h, u.width, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, tp, sw)
-            if gz_arg is None:
-                streams.wgrad_operand_read()
-        elif u.g.wino:
-            _timed('wgrad_conv3x3', flops, nbytes, tag, u.g.wgrad, gz_arg, u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
-                   g[u.keys[0]], B, u.h, u.width, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, tp, sw)
+        if u.g.taps == 1:     # im2col: a pointwise weight gradient, HBM-bound and timed as such
+            run = _hbm_run('enc1.0', self.esize * B * u.h * u.width * (u.cout + u.cin_p))
         else:
-            _timed('wgrad_conv3x3', flops, nbytes, tag, u.g.wgrad, _lib.WGRAD_CONV3, gz_arg, u.cout_p, ptr(xin), xin_ldc, ptr(self.ws), self.ws_bytes,
-                   g[u.keys[0]], B, u.h, u.width, u.cout_p, u.cin_p, u.cout, u.cin, u.cout, u.cout_p, c_seg0, c_seg0p, dc, tp, sw)
+            run = partial(_timed, 'wgrad_conv3x3', flops, nbytes, u.tag['wgrad'])
+        xin, xin_ldc = (u.fold_a.y, u.fold_a.cout_p) if u.fold_on else (u.xin, u.xin_ldc)      # a fold candidate reads the raw tensor
+        if gz_arg is None:
+            streams.wgrad_after_transform()
+        convops.wgrad3x3(run, u.g, gz_arg, u.cout_p, ptr(xin), xin_ldc, ptr(u.vx), ptr(yt), ptr(self.ws), self.ws_bytes, g[u.keys[0]],
+                         B, u.h, u.width, u.cout_p, u.cin_p, u.cout, u.cin, c_seg0, c_seg0p, dc, tp, sw)
+        if gz_arg is None:
+            streams.wgrad_operand_read()
         if u.fold_on:
             # the weight gradient ran on the producer's conv+ReLU output r instead of x = scale * r + shift: dW = scale * dWr + shift * S, S from
             # the border sums of gz and the conv-bias gradient bn_bwd_finalize wrote above (bnfold.hip); behind it, in place

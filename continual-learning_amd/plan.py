@@ -1,6 +1,6 @@
 """Kernel plan of the UNet engine: which kernel runs each 3x3 convolution unit in each direction, and where each unit's BatchNorm
 is applied and reduced.  Host-only: no tensors, no device (the 2^32-byte descriptor limits ask libclamd's size functions, which
-answer on any machine).  ALGOS is the one place that maps a kernel family to its entry points, packed filters and sizes."""
+answer on any machine).  ALGOS is the one place that maps a kernel family to its entry points, argument layout, packed filters and sizes."""
 from collections import namedtuple
 from typing import NamedTuple, Optional
 
@@ -9,6 +9,7 @@ from .ops import cpad
 
 
 class Algo(NamedTuple):
+    layout: str                    # argument layout of its launches: 'pointwise' | 'direct' | 'wino' | 'pre' (convops.py assembles them)
     conv: str                      # forward / data-gradient launch
     wgrad: str                     # weight-gradient launch
     taps: int                      # packed filter taps: 1 pointwise (PackTable.head), 9 direct (PackTable.conv3x3), 16/24/36 Winograd planes
@@ -28,20 +29,20 @@ class Algo(NamedTuple):
 
 
 ALGOS = {
-    'im2col': Algo('clamd_conv1x1', 'clamd_wgrad', 1, _lib.OP_CONV1X1, 1.0,
+    'im2col': Algo('pointwise', 'clamd_conv1x1', 'clamd_wgrad', 1, _lib.OP_CONV1X1, 1.0,
                    lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_PW, B, H, W, rp, cp, dc)),
-    'igemm': Algo('clamd_conv3x3', 'clamd_wgrad', 9, _lib.OP_CONV3X3, 1.0,
+    'igemm': Algo('direct', 'clamd_conv3x3', 'clamd_wgrad', 9, _lib.OP_CONV3X3, 1.0,
                   lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_workspace_bytes(_lib.WGRAD_CONV3, B, H, W, rp, cp, dc), border_bias=None, bn_sums=True),
-    'f22': Algo('clamd_conv3x3_winograd', 'clamd_wgrad_winograd', 16, _lib.OP_CONV3X3_WINOGRAD, 16 / 36,
+    'f22': Algo('wino', 'clamd_conv3x3_winograd', 'clamd_wgrad_winograd', 16, _lib.OP_CONV3X3_WINOGRAD, 16 / 36,
                 lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_winograd_workspace_bytes(rp, cp)),
-    'f24': Algo('clamd_conv3x3_winograd24', 'clamd_wgrad_winograd24', 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72,
+    'f24': Algo('wino', 'clamd_conv3x3_winograd24', 'clamd_wgrad_winograd24', 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72,
                 lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_winograd24_workspace_bytes(rp, cp), border_bias=True),
-    'f24_direct': Algo('clamd_conv3x3_winograd24_direct_filters', None, 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72, None, border_bias=True),
-    'f24_pre': Algo('clamd_conv3x3_winograd24_pre', 'clamd_wgrad_winograd24_pre', 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72,
+    'f24_direct': Algo('wino', 'clamd_conv3x3_winograd24_direct_filters', None, 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72, None, border_bias=True),
+    'f24_pre': Algo('pre', 'clamd_conv3x3_winograd24_pre', 'clamd_wgrad_winograd24_pre', 24, _lib.OP_CONV3X3_WINOGRAD24, 24 / 72,
                     lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_winograd24_pre_workspace_bytes(B, H, W, rp, cp),
                     xform='clamd_winograd24_transform_input', x_elems='clamd_winograd24_input_elems', x_bytes=16,
                     wg_xform='clamd_wgrad_winograd24_pre_transform', wg_elems='clamd_wgrad_winograd24_pre_operand_elems'),
-    'f44_pre': Algo('clamd_conv3x3_winograd44_pre', 'clamd_wgrad_winograd44_pre', 36, _lib.OP_CONV3X3_WINOGRAD44, 36 / 144,
+    'f44_pre': Algo('pre', 'clamd_conv3x3_winograd44_pre', 'clamd_wgrad_winograd44_pre', 36, _lib.OP_CONV3X3_WINOGRAD44, 36 / 144,
                     lambda lib, B, H, W, rp, cp, dc: lib.clamd_wgrad_winograd44_pre_workspace_bytes(B, H, W, rp, cp),
                     xform='clamd_winograd44_transform_input', x_elems='clamd_winograd44_input_elems', x_bytes=13,
                     wg_xform='clamd_wgrad_winograd44_pre_transform', wg_elems='clamd_wgrad_winograd44_pre_operand_elems'),
