@@ -146,6 +146,8 @@ SIGNATURES = {
     'clamd_sgd_step_tracked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     'clamd_sizeof_path_tensor': (_I, []),
     'clamd_path_importance': (_I, [_P, _P, _I, _D, _D, _P]),
+    'clamd_sizeof_grad_tensor': (_I, []),
+    'clamd_grad_norm_clip': (_I, [_P, _I, _P, _I, _P, _D, _P, _P, _P, _P, _P]),
     'clamd_argmax_confusion': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'clamd_voc_prepare': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'clamd_label_to_rgb': (_I, [_P, _P, _LL, _LL, _P]),

@@ -1,5 +1,5 @@
 // The multi-tensor passes: fused Adam (plain and with elastic weight consolidation), fused SGD, both with or without the path integral of
-// Synaptic Intelligence, the importance accumulation and the path integral's task boundary.  All
+// Synaptic Intelligence, the importance accumulation, the path integral's task boundary and the gradient norm of clipping.  All
 // walk one job list of (tensor, ADAM_CHUNK-element chunk), one 256-thread workgroup per job, over a device table of per-tensor rows; they
 // share the job list, the pull towards an anchor, the fixed-order penalty sums and the host-side checks below.
 //
@@ -324,6 +324,103 @@ __global__ void __launch_bounds__(256) path_importance_kernel(const PathTensor* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ gradient norm and clip coefficient
+// Clipping by the global norm without a second pass over the gradients: one pass reads every gradient once (4 B / parameter) and leaves one
+// sum of squares per job, the finalize kernel turns them into the norm, torch.nn.utils.clip_grad_norm_'s coefficient and a second hyper
+// buffer whose slot 4 is grad_scale * coefficient; the unchanged step kernels are then launched on that buffer.
+struct GradTensor { const float* g; long long n; int first_chunk; int nchunks; };
+static_assert(sizeof(GradTensor) == 24, "the host side builds 24-byte rows");
+
+// partials[block] = the sum of g[i]^2 over this job's chunk.  The chunk is shifted by the gradient's own `head` as in sgd_chunk (chunk 0
+// peels it), the last partial group goes element-wise into the lanes of a zeroed vector, and a lane issues all its loads before the first
+// use.  No float atomics: a lane's squares in index order, the shuffle tree, then the four waves in a fixed order, as block_sums.
+__global__ void __launch_bounds__(256) grad_sqnorm_kernel(const GradTensor* __restrict__ tensors, const AdamChunk* __restrict__ chunks,
+                                                          float* __restrict__ partials) {
+    constexpr int GROUPS = ADAM_CHUNK / 1024;
+    __shared__ float wsum[4];
+    const AdamChunk c = chunks[blockIdx.x];
+    const GradTensor t = tensors[c.tensor];
+    const int head = chunk_head(t.g);
+    float h = 0.f;
+    if (c.chunk == 0 && (int)threadIdx.x < head && (long long)threadIdx.x < t.n) h = t.g[threadIdx.x];
+    const long long base = (long long)c.chunk * ADAM_CHUNK + head;
+    f32x4_a4 g[GROUPS];
+#pragma unroll
+    for (int k = 0; k < GROUPS; ++k) {
+        const long long i = base + 4 * (k * 256 + (int)threadIdx.x);
+        if (i + 4 <= t.n) {
+            g[k] = *(const f32x4_a4*)(t.g + i);
+        } else {
+            g[k] = f32x4_a4{0.f, 0.f, 0.f, 0.f};
+            if (i < t.n) g[k].x = t.g[i];
+            if (i + 1 < t.n) g[k].y = t.g[i + 1];
+            if (i + 2 < t.n) g[k].z = t.g[i + 2];
+        }
+    }
+    float s = h * h;
+#pragma unroll
+    for (int k = 0; k < GROUPS; ++k) {
+        s += g[k].x * g[k].x;
+        s += g[k].y * g[k].y;
+        s += g[k].z * g[k].z;
+        s += g[k].w * g[k].w;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// One workgroup of CLIP_WAVES waves.  Wave w takes tensors w, w + CLIP_WAVES, ...: lane l adds the tensor's partials l, l + 64, ... in fp64,
+// the shuffle tree gives the tensor's sum, and the wave adds its tensors' sums in that order; thread 0 then adds the waves' totals pairwise
+// in a fixed tree.  clip_out: [0] norm = sqrt(total) * |grad_scale|, [1] coef = min(1, max_norm / (norm + 1e-6)) with NaN kept (fmin would
+// return 1), [2] fp32(grad_scale) * coef, [3] 1 when the norm is not finite; hyper_eff = hyper with slot 4 = clip_out[2].
+constexpr int CLIP_WAVES = 16;
+__global__ void __launch_bounds__(64 * CLIP_WAVES) grad_clip_final_kernel(const GradTensor* __restrict__ tensors, int ntensors,
+                                                                          const float* __restrict__ partials, int nchunks,
+                                                                          const float* __restrict__ hyper, double max_norm,
+                                                                          float* __restrict__ clip_out, float* __restrict__ tensor_norms,
+                                                                          float* __restrict__ hyper_eff) {
+    __shared__ double wtot[CLIP_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float gsf = hyper[4];
+    const double gs = fabs((double)gsf);
+    double total = 0.0;
+    for (int ti = wave; ti < ntensors; ti += CLIP_WAVES) {
+        const GradTensor t = tensors[ti];
+        const int first = t.first_chunk < 0 ? 0 : t.first_chunk;
+        const int end = t.first_chunk + t.nchunks < nchunks ? t.first_chunk + t.nchunks : nchunks;      // never past the partials
+        double s = 0.0;
+        for (int i = first + lane; i < end; i += 64) s += (double)partials[i];
+        s = wave_sum_f64(s);
+        if (lane == 0 && tensor_norms) tensor_norms[ti] = (float)(sqrt(s) * gs);
+        total += s;
+    }
+    if (lane == 0) wtot[wave] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int o = CLIP_WAVES / 2; o > 0; o >>= 1)
+            for (int i = 0; i < o; ++i) wtot[i] += wtot[i + o];
+        const double norm = sqrt(wtot[0]) * gs;
+        double c = max_norm / (norm + 1e-6);
+        c = c > 1.0 ? 1.0 : c;                  // NaN stays NaN
+        const float coef = (float)c;
+        const float eff = gsf * coef;
+        clip_out[0] = (float)norm;
+        clip_out[1] = coef;
+        clip_out[2] = eff;
+        clip_out[3] = isfinite(norm) ? 0.f : 1.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) hyper_eff[j] = j == 4 ? eff : hyper[j];
+    }
+}
+
 }  // namespace clamd
 
 using namespace clamd;
@@ -474,6 +571,21 @@ int clamd_importance_accum(const void* tensors_dev, const void* chunks_dev, int 
         hipLaunchKernelGGL(importance_accum_kernel<false>, dim3(nchunks), dim3(256), 0, s, (const ImportanceTensor*)tensors_dev,
                            (const AdamChunk*)chunks_dev, (float)decay, (float)scale);
     return clamd_check_launch("importance_accum");
+}
+
+int clamd_sizeof_grad_tensor(void) { return (int)sizeof(GradTensor); }
+
+int clamd_grad_norm_clip(const void* tensors_dev, int ntensors, const void* chunks_dev, int nchunks, const float* hyper_dev, double max_norm,
+                         float* partials, float* clip_out, float* tensor_norms, float* hyper_eff, void* stream) {
+    if (int e = check_jobs("grad_norm_clip", tensors_dev, chunks_dev, nchunks)) return e;
+    if (ntensors <= 0) return clamd_fail("grad_norm_clip: no tensors");
+    if (!hyper_dev || !partials || !clip_out || !hyper_eff) return clamd_fail("grad_norm_clip: null hyper / partials / clip_out / hyper_eff buffer");
+    if (!(max_norm > 0.0)) return clamd_fail("grad_norm_clip: max_norm must be > 0 (infinity: measure only)");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nchunks), dim3(256), 0, s, (const GradTensor*)tensors_dev, (const AdamChunk*)chunks_dev, partials);
+    hipLaunchKernelGGL(grad_clip_final_kernel, dim3(1), dim3(64 * CLIP_WAVES), 0, s, (const GradTensor*)tensors_dev, ntensors, partials, nchunks,
+                       hyper_dev, max_norm, clip_out, tensor_norms, hyper_eff);
+    return clamd_check_launch("grad_norm_clip");
 }
 
 }  // extern "C"

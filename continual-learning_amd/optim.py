@@ -17,6 +17,9 @@ Optional path integral of Synaptic Intelligence (build-defined too): ``set_path_
 omega += -(grad * grad_scale) * (theta_new - theta_old) inside the same kernel (``clamd_adam_step_tracked`` / ``clamd_sgd_step_tracked``,
 +8 B / parameter); without it the step launches what it always did.
 
+Optional clipping by the global gradient norm: ``set_grad_clip(max_norm)`` puts one norm pass (``clamd_grad_norm_clip``, 4 B / parameter) in
+front of the step and hands the coefficient to the unchanged step kernel through the gradient scale; nothing is read back.
+
 ``FusedSGD`` is the second optimiser: torch.optim.SGD with momentum, Nesterov and weight decay in one launch of ``clamd_sgd_step``.  Both
 are a ``_FusedOptimizer``, which owns everything they do alike: the step protocol, the device tables, the two anchor terms, head growth
 and checkpoints.  A subclass says how one table row is filled, which eight hyper-parameters it uploads, how its state is laid out in flat
@@ -27,6 +30,9 @@ import torch
 
 from . import _lib
 from ._lib import ptr
+
+
+_GRAD_TENSOR_DT = np.dtype([('g', 'u8'), ('n', 'i8'), ('first_chunk', 'i4'), ('nchunks', 'i4')])      # clamd_grad_norm_clip's rows
 
 
 class _FusedOptimizer(torch.optim.Optimizer):
@@ -52,6 +58,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._ewcacc = None
         self._path = None             # per-parameter path integrals (Synaptic Intelligence): the step launches the tracked entry point
         self._path_dev = None
+        self._clip = None             # max_norm of clipping by the global gradient norm; None: off, nothing below is allocated
+        self._clip_tab = self._clip_part = self._clip_out = self._hyper_eff = self._tensor_norms = None
 
     # -- the step ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -79,6 +87,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
             self._build_table(params, dev)
             self._table = key
         self.sync_hyper()
+        if self._clip is not None:
+            from . import unet as U
+            U._hbm('clip', 4 * self._numel,       # every gradient read once
+                   'clamd_grad_norm_clip', ptr(self._clip_tab), len(params), ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), self._clip,
+                   ptr(self._clip_part), ptr(self._clip_out), ptr(self._tensor_norms), ptr(self._hyper_eff), _lib.stream_ptr())
         self._launch()
         return loss
 
@@ -98,6 +111,25 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 if w.device != p.device:
                     raise RuntimeError(f'{self._NAME}: path integral {i} is on {w.device}, its parameter on {p.device}')
             self._path_dev = torch.tensor([w.data_ptr() for w in self._path], dtype=torch.int64).to(dev)
+        self._clip_tab = self._clip_part = self._tensor_norms = None
+        if self._clip is not None:
+            lib = _lib.load()
+            assert lib.clamd_sizeof_grad_tensor() == _GRAD_TENSOR_DT.itemsize
+            chunk = lib.clamd_adam_chunk_elems()
+            counts = [(n + chunk - 1) // chunk for n in numels]          # a row's jobs are consecutive in job_table's list
+            firsts = np.cumsum([0] + counts)
+            assert int(firsts[-1]) == self._nchunks
+            table = np.array([(p.grad.data_ptr(), n, int(f), k) for p, n, f, k in zip(params, numels, firsts, counts)], dtype=_GRAD_TENSOR_DT)
+            self._clip_tab = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
+            self._clip_part = torch.zeros(self._nchunks, dtype=torch.float32, device=dev)
+            self._tensor_norms = torch.zeros(len(params), dtype=torch.float32, device=dev)
+            if self._clip_out is None or self._clip_out.device != dev:     # kept across rebuilds: a caller may hold the views below
+                self._clip_out = torch.zeros(4, dtype=torch.float32, device=dev)
+                self._hyper_eff = torch.zeros(8, dtype=torch.float32, device=dev)
+
+    def _step_hyper(self):
+        """The hyper buffer the step kernel reads: with clipping the copy whose gradient scale carries the coefficient."""
+        return self._hyper if self._clip is None else self._hyper_eff
 
     def sync_hyper(self):
         """Upload the eight hyper-parameters (learning rate, ..., gradient scale, L2 and consolidation weights) to device memory if they
@@ -259,6 +291,67 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._path = [w.detach() for w in omega]
         self._table = None
 
+    # -- clipping by the global gradient norm -------------------------------------------------------------------
+    def set_grad_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) inside the step, without rewriting a gradient: after the hooks and
+        sync_hyper, one pass reads every gradient once (``clamd_grad_norm_clip``, 4 B / parameter), a finalize kernel forms
+        coef = min(1, max_norm / (norm + 1e-6)) on the device, and the unchanged step kernel runs on a second hyper buffer whose gradient
+        scale is grad_scale * coef.  Nothing is read back; the step stays bit-reproducible and can be captured in a graph (which keeps the
+        max_norm it was captured with).  max_norm: > 0; float('inf') measures without clipping (coef == 1 exactly); None switches clipping
+        off: the step then launches exactly what it launched before and nothing is allocated.
+        - The norm is that of the gradient the step consumes: after grad_scale, i.e. after DDP's 1/world (ddp.GradSync).  Every rank computes
+          it from identical all-reduced gradients (GradSync.wait is a pre_step_hook and has run), so no further collective is needed.
+        - Weight decay and the L2 / consolidation pulls are added after clipping, as torch.optim does with weight decay.
+        - The path integral (set_path_integral) sees the clipped gradient, as it would after an in-place clip_grad_norm_.
+        - A non-finite norm propagates as in torch with error_if_nonfinite=False (a NaN norm gives a NaN coefficient and NaN parameters; an
+          infinite one coefficient 0) and sets ``grad_nonfinite``.
+        Device tensors of the LAST step while clipping is on: ``grad_norm``, ``clip_coef``, ``effective_grad_scale``, ``grad_nonfinite``
+        (fp32[1] each) and ``tensor_grad_norms`` (fp32[ntensors], parameter order)."""
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not max_norm > 0.0:
+                raise ValueError(f'{self._NAME}.set_grad_clip: max_norm must be > 0 (inf: measure only; None: off), not {max_norm}')
+        self._clip = max_norm
+        if max_norm is None:
+            self._clip_tab = self._clip_part = self._clip_out = self._hyper_eff = self._tensor_norms = None
+        self._table = None
+
+    def _clip_stat(self, i):
+        if self._clip is None or self._clip_out is None:
+            raise RuntimeError(f'{self._NAME}: no step with gradient clipping has run (set_grad_clip)')
+        return self._clip_out[i if isinstance(i, slice) else slice(i, i + 1)]
+
+    @property
+    def clip_state(self):
+        """The four below in one device tensor, fp32[4]: norm, coefficient, effective gradient scale, non-finite flag."""
+        return self._clip_stat(slice(0, 4))
+
+    @property
+    def grad_norm(self):
+        """Global norm of the gradient the last step consumed, grad_scale included (device fp32[1])."""
+        return self._clip_stat(0)
+
+    @property
+    def clip_coef(self):
+        """min(1, max_norm / (grad_norm + 1e-6)) of the last step (device fp32[1])."""
+        return self._clip_stat(1)
+
+    @property
+    def effective_grad_scale(self):
+        """fp32(grad_scale) * clip_coef: the gradient scale the last step's kernel read (device fp32[1])."""
+        return self._clip_stat(2)
+
+    @property
+    def grad_nonfinite(self):
+        """1 when the last step's norm was infinite or NaN, else 0 (device fp32[1])."""
+        return self._clip_stat(3)
+
+    @property
+    def tensor_grad_norms(self):
+        """Per-parameter norms of the last step, grad_scale included, in parameter order (device fp32[ntensors])."""
+        self._clip_stat(0)
+        return self._tensor_norms
+
     def consolidation_penalty(self):
         """(lam / 2) * sum importance * (theta - theta_old)^2 as accumulated by the LAST step (device scalar)."""
         if self._ewcacc is None:
@@ -329,15 +422,15 @@ class FusedAdam(_FusedOptimizer):
             # the plain step's 28 B, the path integral read and written, the anchor and the importance read
             U._hbm('adam', (36 + (8 if ewc else 4 if self._anchor is not None else 0)) * self._numel,
                    'clamd_adam_step_tracked', ptr(self._tensors_dev), ptr(self._importance_dev) if ewc else None, ptr(self._path_dev),
-                   ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._step_dev), ptr(self._derived),
+                   ptr(self._chunks_dev), self._nchunks, ptr(self._step_hyper()), ptr(self._step_dev), ptr(self._derived),
                    ptr(self._ewcacc) if ewc else None, l2acc, _lib.stream_ptr())
         elif ewc:
             U._hbm('adam', 36 * self._numel,      # p, g, m, v, old, importance read; p, m, v written
                    'clamd_adam_step_consolidated', ptr(self._tensors_dev), ptr(self._importance_dev), ptr(self._chunks_dev), self._nchunks,
-                   ptr(self._hyper), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc), l2acc, _lib.stream_ptr())
+                   ptr(self._step_hyper()), ptr(self._step_dev), ptr(self._derived), ptr(self._ewcacc), l2acc, _lib.stream_ptr())
         else:
             U._hbm('adam', 28 * self._numel,      # p, g, m, v read; p, m, v written
-                   'clamd_adam_step', ptr(self._tensors_dev), ptr(self._chunks_dev), self._nchunks, ptr(self._hyper),
+                   'clamd_adam_step', ptr(self._tensors_dev), ptr(self._chunks_dev), self._nchunks, ptr(self._step_hyper()),
                    ptr(self._step_dev), ptr(self._derived), l2acc, _lib.stream_ptr())
         self._step_host += 1                # host-side mirror of the device counter (shared by all param states)
 
@@ -430,7 +523,7 @@ class FusedSGD(_FusedOptimizer):
         ewc = self._importance is not None
         # p, g read and p written; buf read and written; the anchor and the importance read
         per_param = 12 + (8 if self._with_momentum else 0) + (4 if self._anchor is not None else 0) + (4 if ewc else 0)
-        tail = (ptr(self._chunks_dev), self._nchunks, ptr(self._hyper), ptr(self._ewcacc) if ewc else None,
+        tail = (ptr(self._chunks_dev), self._nchunks, ptr(self._step_hyper()), ptr(self._ewcacc) if ewc else None,
                 ptr(self._l2acc) if self._l2_on else None, _lib.stream_ptr())
         if self._path is not None:      # the path integral read and written on top
             U._hbm('sgd', (per_param + 8) * self._numel, 'clamd_sgd_step_tracked', ptr(self._tensors_dev),

@@ -15,7 +15,8 @@ code below reads plain ``cfg.name``.  The build-defined switches are off by defa
 (syncbn.py), ``augment`` (every training batch, replayed rows included, rescaled, cropped or padded and flipped in one launch
 before the forward pass, augment.py), ``loss='ce_dice'`` (loss.DiceCrossEntropyLoss as the step's criterion: each rank's Dice sums cover
 its own batch, and ``estimate_importance`` keeps the plain log-likelihood), ``path_integral`` (consolidate.PathIntegral: Synaptic
-Intelligence's path integral, tracked inside every optimiser step from the first one).
+Intelligence's path integral, tracked inside every optimiser step from the first one), ``max_grad_norm`` (optim.set_grad_clip: the
+global gradient norm clipped inside the optimiser step; nnU-Net trains with 12).
 Continual learning (config 4): ``Trainer.begin_task2`` is the task boundary; its docstring numbers the stages once and places every
 feature at its stage.  What a feature adds to the trainer is declared once, at the top of the class.
 """
@@ -46,7 +47,7 @@ def default_config(**kw):
                w_image_size=256, num_classes=21, conv_dim=64, compute_dtype='fp32', stats_every=10, sync_bn=False,
                augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0,
                optimizer='adam', momentum=0.9, nesterov=True, weight_decay=1e-4, decay_norm_and_bias=True, lr_schedule='epoch',
-               max_iters=None, path_integral=False, si_xi=0.1,
+               max_iters=None, path_integral=False, si_xi=0.1, max_grad_norm=None,
                loss='ce', dice_weight=1.0, dice_smooth=1e-5, dice_include_background=True, dice_present_only=True, dice_per_image=False)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
@@ -167,6 +168,11 @@ class Trainer:
                                        seed=int(cfg.augment_seed) + syncbn.rank()) if cfg.augment else None      # each rank draws its own
 
     def _make_optimizer(self):
+        optim = self._new_optimizer()
+        optim.set_grad_clip(self.cfg.max_grad_norm)      # None: off, the step launches what it always did
+        return optim
+
+    def _new_optimizer(self):
         cfg = self.cfg
         if cfg.optimizer == 'adam':
             return FusedAdam(self.model.parameters(), lr=cfg.lr, betas=[cfg.beta1, cfg.beta2])
@@ -552,6 +558,8 @@ class Trainer:
                 self.scheduler.step()                    # reference does exactly that (trainer.py:147)
         conf = None
         losses = []
+        clipping = self.cfg.max_grad_norm is not None
+        clips = []                                       # (iteration, device copy of the optimiser's norm, coefficient, scale, non-finite flag)
         for i, (images, masks) in enumerate(self.train_data_loader):
             inputs = images.to(self.device, non_blocking=True)
             labels = masks.to(self.device, non_blocking=True)
@@ -564,11 +572,19 @@ class Trainer:
                 c, _ = argmax_confusion(out, labels, self.cfg.num_classes)
                 conf = c if conf is None else conf + c
                 losses.append(loss.detach())
+                if clipping:
+                    clips.append((i, self.optim.clip_state.clone()))
         stats = {}
         if conf is not None:
             oa, pc, miu, mx = metrics_from_confusion(conf)
             stats = dict(loss=float(torch.stack(losses).mean()), pixel_acc=float(oa), class_acc=float(pc),
                          mean_iu=float(miu), max_class_acc=float(mx), lr=self.optim.param_groups[0]['lr'])
+            if clipping:      # read here, with the other statistics: the step itself reads nothing back
+                seen = torch.stack([c for _, c in clips]).cpu()
+                for (i, _), row in zip(clips, seen):
+                    if float(row[3]) != 0.0:
+                        raise ValueError(f'epoch {epoch}, iteration {i}: the gradient norm is not finite ({float(row[0])})')
+                stats.update(grad_norm=float(seen[:, 0].mean()), clipped=float((seen[:, 1] < 1).float().mean()))
         return stats
 
     def train_val(self, epochs=None):

@@ -640,6 +640,25 @@ int clamd_sgd_step_tracked(const void* tensors_dev, const void* importance_dev, 
  * so bit-reproducible. */
 int clamd_sizeof_path_tensor(void);
 int clamd_path_importance(const void* tensors_dev, const void* chunks_dev, int nchunks, double decay, double xi, void* stream);
+/* Clipping by the global gradient norm (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite off) without rewriting a gradient:
+ * one pass reads every gradient once and the steps above are then launched on hyper_eff, whose grad_scale carries the coefficient.
+ * tensors_dev: ntensors rows of clamd_sizeof_grad_tensor() = 24 bytes {const float* g; long long n; int first_chunk; int nchunks}, where
+ * [first_chunk, first_chunk + nchunks) are the row's jobs in chunks_dev, the (tensor, chunk) job list of clamd_adam_step (chunks of
+ * clamd_adam_chunk_elems() elements, a tensor's chunks consecutive).  hyper_dev: the fp32[8] of the step that follows; gs = hyper_dev[4].
+ * Launch 1 (one workgroup per job, 4 B / parameter): partials[job] = sum of g[i]^2 over the job's chunk (nchunks floats).
+ * Launch 2 (one workgroup): per tensor the sum of its partials, then the sum of those, both in fp64 and in a fixed order, and
+ *   tensor_norms[t] (optional, ntensors floats) = fp32(sqrt(sum_t) * |gs|)
+ *   clip_out[0] = fp32(norm), norm = sqrt(total) * |gs|: the norm of the gradient the step consumes
+ *   clip_out[1] = coef = fp32(min(1, max_norm / (norm + 1e-6))), a NaN norm giving a NaN coefficient
+ *   clip_out[2] = fp32(gs) * coef, one fp32 product
+ *   clip_out[3] = 1 when norm is infinite or NaN, else 0
+ *   hyper_eff[0..7] = hyper_dev[0..7] with slot 4 replaced by clip_out[2].
+ * max_norm > 0; infinity measures without clipping (coef == 1 exactly for a finite norm).  The gradients are only read, with 4-byte
+ * alignment only (16-byte loads from g's first 16-byte boundary); nothing outside [0, n) of a row is touched.  No float atomics:
+ * bit-reproducible.  Enqueue only: no allocation, no synchronisation, nothing read back, no process state. */
+int clamd_sizeof_grad_tensor(void);
+int clamd_grad_norm_clip(const void* tensors_dev, int ntensors, const void* chunks_dev, int nchunks, const float* hyper_dev, double max_norm,
+                         float* partials, float* clip_out, float* tensor_norms, float* hyper_eff, void* stream);
 /* argmax over classes + confusion matrix (trainer.py:183-188, metrics.py:32-38). */
 int clamd_argmax_confusion(const float* logits, const long long* labels, long long* pred, unsigned long long* conf,
                            int B, int K, int Kc, int H, int W, void* stream);
