@@ -5,7 +5,7 @@ root is the import shim).  Everything compute-related goes through libclamd.so (
 """
 from . import _lib, ops, synth  # noqa: F401
 from .unet import UNet, cpad, stage_table  # noqa: F401
-from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy, DiceCrossEntropyLoss  # noqa: F401
+from .loss import CrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy, DiceCrossEntropyLoss, class_weights  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .consolidate import Consolidation, PathIntegral  # noqa: F401
 from .pseudo import PseudoLabeler, thresholds_from_histogram  # noqa: F401
@@ -16,5 +16,5 @@ from .metrics import argmax_confusion, eval_metrics, metrics_from_confusion  # n
 from .trainer import Trainer, default_config  # noqa: F401
 from . import augment, consolidate, data, ddp, pod, pseudo, replay, syncbn  # noqa: F401
 
-__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'DiceCrossEntropyLoss', 'FusedAdam', 'FusedSGD', 'Consolidation', 'PathIntegral', 'PseudoLabeler', 'thresholds_from_histogram', 'LocalPODLoss', 'ReplayMemory', 'class_pixel_counts', 'replay', 'RandomScaleCrop', 'augment_batch', 'params_from_draws', 'augment', 'Trainer', 'default_config',
+__all__ = ['UNet', 'CrossEntropyLoss', 'DistillationCrossEntropy', 'UnbiasedDistillationCrossEntropy', 'DiceCrossEntropyLoss', 'class_weights', 'FusedAdam', 'FusedSGD', 'Consolidation', 'PathIntegral', 'PseudoLabeler', 'thresholds_from_histogram', 'LocalPODLoss', 'ReplayMemory', 'class_pixel_counts', 'replay', 'RandomScaleCrop', 'augment_batch', 'params_from_draws', 'augment', 'Trainer', 'default_config',
            'argmax_confusion', 'eval_metrics', 'metrics_from_confusion', 'data', 'ddp', 'synth']

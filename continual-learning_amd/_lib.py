@@ -128,6 +128,8 @@ SIGNATURES = {
     'clamd_ce_unbiased_fwd_bwd': (_I, [_P, _P, _P, _I, _I, _D, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),
     'clamd_ce_dice_workspace_bytes': (_SZ, [_I, _I, _I, _I, _I]),
     'clamd_ce_dice_fwd_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _D, _D, _I, _I, _I, _D, _P]),
+    'clamd_ce_class_workspace_bytes': (_SZ, []),
+    'clamd_ce_class_fwd_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _D, _D, _P]),
     'clamd_pseudo_entropy_hist': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     'clamd_pseudo_label': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _D, _I, _I, _I, _LL, _P]),
     'clamd_ce_fwd_bwd_weighted': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _SZ, _I, _I, _I, _I, _LL, _D, _P]),

@@ -5,6 +5,7 @@
 //   clamd_ce_fwd_bwd_counted    the training-step form: four pixels per thread, d logits optionally a second time in NHWC
 //   clamd_ce_fwd_bwd_weighted   the same with the image's factor nu_b on every pixel's term
 //   clamd_ce_unbiased_fwd_bwd   unbiased cross-entropy + unbiased distillation
+//   clamd_ce_class_fwd_bwd      class weights, label smoothing or the focal term (+ the image's factor); its own per-class count in front
 // Every entry point: [count ->] one loss kernel (a {ce, kd} partial pair per workgroup) -> ce_finalize_kernel.
 #include <math.h>
 #include <stdio.h>
@@ -558,6 +559,212 @@ __global__ void ce_finalize_kernel(const float* __restrict__ partial, int nblock
     }
 }
 
+// ---- class weights, label smoothing, focal term (clamd_ce_class_fwd_bwd; the definition is in include/clamd.h) ------------------------
+// The family's shape with a per-class count in front: class_count_rows_kernel (one partial row {n_0 .. n_31, valid, bad} per workgroup) ->
+// class_totals_kernel (one workgroup: the rows added, D = sum_k w_k n_k and W = sum_k w_k in fp64 in ascending k) -> ce4c_kernel (ce4_kernel's
+// shape; a {nll, smo} partial pair per workgroup) -> cec_finalize_kernel.  Behind the CE workspace, in 32-bit words: the totals block
+// {n_k[32], D (a double), W (a float), spare}, then the CE_COUNT_BLOCKS partial rows.
+constexpr int CEC_KP = 32;
+constexpr int CEC_ROW_WORDS = CEC_KP + 2, CEC_ROW_VALID = CEC_KP, CEC_ROW_BAD = CEC_KP + 1;
+constexpr int CEC_TOT_D = CEC_KP, CEC_TOT_W = CEC_KP + 2, CEC_TOT_WORDS = CEC_KP + 4;
+constexpr int CEC_WS_TOT = CE_WS_WORDS;
+constexpr int CEC_WS_ROWS = CEC_WS_TOT + CEC_TOT_WORDS;
+constexpr int CEC_WS_WORDS = CEC_WS_ROWS + CE_COUNT_BLOCKS * CEC_ROW_WORDS;
+static_assert((CEC_WS_TOT + CEC_TOT_D) % 2 == 0, "D is a double: 8-byte aligned inside an 8-byte aligned workspace");
+
+// The histogram of a workgroup's labels in LDS (integer atomics: any order, the same sums), left as one row with plain stores.  NPX = 4:
+// 32-byte label loads (the pixel count a multiple of 4, the labels 32-byte aligned).
+template <int NPX>
+__global__ void __launch_bounds__(256) class_count_rows_kernel(const long long* __restrict__ labels, long long n, long long ignore_index, int K,
+                                                               unsigned int* rows /* [CE_COUNT_BLOCKS][CEC_ROW_WORDS] */) {
+    __shared__ unsigned int lh[CEC_KP + 1];                     // n_k, then the bad labels
+    if (threadIdx.x <= CEC_KP) lh[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long nq = n / NPX;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += (long long)gridDim.x * 256) {
+        long long lab[4];
+        ce_ld_labels<NPX>(labels, NPX * i, lab);
+        CE_PX {
+            const long long l = lab[c];
+            if (l != ignore_index) atomicAdd(&lh[(l >= 0 && l < K) ? (int)l : CEC_KP], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned int* row = rows + blockIdx.x * CEC_ROW_WORDS;
+    if (threadIdx.x < CEC_KP) row[threadIdx.x] = lh[threadIdx.x];
+    else if (threadIdx.x == CEC_KP) {
+        unsigned int nv = 0;
+        for (int k = 0; k < CEC_KP; ++k) nv += lh[k];
+        row[CEC_ROW_VALID] = nv;
+        row[CEC_ROW_BAD] = lh[CEC_KP];
+    }
+}
+
+// One workgroup: thread (slice s = t / 34, column c = t % 34) adds rows s, s + 7, ... (integers); thread c < 34 adds the 7 slices.  Then D
+// and W by one thread, in fp64, k ascending.  totals = {valid, bad} where loss._forward and the other criteria keep them.
+constexpr int CEC_SLICES = 256 / CEC_ROW_WORDS;                 // 7
+__global__ void __launch_bounds__(256) class_totals_kernel(const unsigned int* __restrict__ rows, const float* __restrict__ class_weight, int K,
+                                                           unsigned int* totals, unsigned int* tot /* the totals block */) {
+    __shared__ unsigned int part[CEC_SLICES][CEC_ROW_WORDS];
+    __shared__ unsigned int col[CEC_ROW_WORDS];
+    const int t = threadIdx.x, s = t / CEC_ROW_WORDS, c = t - s * CEC_ROW_WORDS;
+    if (s < CEC_SLICES) {
+        unsigned int a = 0;
+        for (int r = s; r < CE_COUNT_BLOCKS; r += CEC_SLICES) a += rows[r * CEC_ROW_WORDS + c];
+        part[s][c] = a;
+    }
+    __syncthreads();
+    if (t < CEC_ROW_WORDS) {
+        unsigned int a = 0;
+        for (int j = 0; j < CEC_SLICES; ++j) a += part[j][t];
+        col[t] = a;
+        if (t < CEC_KP) tot[t] = a;
+        else totals[t - CEC_KP] = a;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double D = 0.0, Wd = 0.0;
+        for (int k = 0; k < K; ++k) { D += (double)class_weight[k] * (double)col[k]; Wd += (double)class_weight[k]; }
+        *reinterpret_cast<double*>(tot + CEC_TOT_D) = D;
+        reinterpret_cast<float*>(tot)[CEC_TOT_W] = (float)Wd;
+        tot[CEC_TOT_W + 1] = 0u;
+    }
+}
+
+// ce4_kernel with the class weight of the pixel's label in its coefficient and, by MODE, one more term:
+//   a = gs * nu_b * w_y (gs = grad_scale / (float)D; nu_b = 1.0f without image weights), d logits_k = e_k * (a' / se) - [k = y] a' with
+//   CEC_WEIGHT   a' = a.  Every w_k == 1.0f: each operation is ce4_kernel's in ce4_kernel's order (the same bits, weighted or not)
+//   CEC_SMOOTH   a' = a * (1 - eps), plus  e_k * (b W / se) - w_k b,  b = gs * nu_b * eps / K;  the second partial column is the sum of
+//                nu_b * sum_k w_k (-log p_k) = nu_b * (sum_k w_k (max - z_k) + W log se): positive terms, no W * lse - sum w z cancellation
+//   CEC_FOCAL    a' = a * f,  f = q^gamma (1 + gamma p_y t / q);  q = (sum_{k != y} e_k) / se, never 1 - p_y;  t = -log1p(-q) for q < 1/2 and
+//                log se - (z_y - max) above (the difference first: t to an ulp of t, not of max);  t / q = 1 at q == 0
+// w_k is wave-uniform: read with constant indices inside the unrolled class loops (scalar loads), w_y picked by picked's select chain.
+enum { CEC_WEIGHT = 0, CEC_SMOOTH = 1, CEC_FOCAL = 2 };
+template <int KMAX, int NPX, typename NT, int MODE>
+__global__ void __launch_bounds__(256) ce4c_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                   const float* __restrict__ class_weight, const float* __restrict__ image_weight,
+                                                   float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
+                                                   long long ignore_index, float grad_scale, float keep /* 1 - eps */, float spread /* eps / K */,
+                                                   float gamma, NT* dl_nhwc, int dl_ldc, const float* __restrict__ tot) {
+    __shared__ float red[2][4];
+    const long long nq = (long long)B * HW / NPX;
+    const double Dd = *reinterpret_cast<const double*>(tot + CEC_TOT_D);
+    const float Wsum = tot[CEC_TOT_W];
+    const float gs = Dd > 0.0 ? grad_scale / (float)Dd : 0.f;      // D == 0: every gradient exactly 0
+    float ce_sum = 0.f, sm_sum = 0.f;
+    constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;
+    __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < nq; base += (long long)gridDim.x * blockDim.x) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < nq;                                    // the trip count is block-uniform (the exchange has barriers)
+        if (!XCH && !live) continue;
+        const long long pix = NPX * (live ? i : nq - 1), b = pix / HW, p = pix - b * HW;
+        float nu = 1.f;
+        if (image_weight) nu = image_weight[b];
+        const float gw = gs * nu;
+        const float* z = logits + b * K * HW + p;
+        float4 v[KMAX];
+        float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                v[k] = ce_ldpx<NPX>(z + k * HW);
+                CE_PX ce_at(mx, c) = fmaxf(ce_at(mx, c), ce_at(v[k], c));
+            }
+        long long lab[4];
+        ce_ld_labels<NPX>(labels, pix, lab);
+        float4 se = make_float4(0.f, 0.f, 0.f, 0.f), picked = se, wy = se, ey = se, sq = se, swz = se;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                const float wk = class_weight[k];
+                CE_PX ce_at(picked, c) = lab[c] == k ? ce_at(v[k], c) : ce_at(picked, c);
+                CE_PX ce_at(wy, c) = lab[c] == k ? wk : ce_at(wy, c);
+                if constexpr (MODE == CEC_SMOOTH) CE_PX ce_at(swz, c) = fmaf(wk, ce_at(mx, c) - ce_at(v[k], c), ce_at(swz, c));
+                CE_PX ce_at(v[k], c) = expf(ce_at(v[k], c) - ce_at(mx, c));
+                CE_PX ce_at(se, c) += ce_at(v[k], c);
+                if constexpr (MODE == CEC_FOCAL) CE_PX {
+                    ce_at(ey, c) = lab[c] == k ? ce_at(v[k], c) : ce_at(ey, c);
+                    ce_at(sq, c) += lab[c] == k ? 0.f : ce_at(v[k], c);
+                }
+            }
+        bool ok[NPX];
+        CE_PX ok[c] = lab[c] != ignore_index && lab[c] >= 0 && lab[c] < K;
+        float r[NPX], h[NPX], rs[NPX], hs[NPX];
+        CE_PX {
+            const float wn = nu * ce_at(wy, c);
+            float a = gw * ce_at(wy, c);                             // the pixel's coefficient gs * nu_b * w_y
+            if constexpr (MODE == CEC_FOCAL) {
+                const float q = ce_at(sq, c) / ce_at(se, c), py = ce_at(ey, c) / ce_at(se, c);
+                const float t = q < 0.5f ? -log1pf(-q) : logf(ce_at(se, c)) - (ce_at(picked, c) - ce_at(mx, c));
+                const float qg = powf(q, gamma);
+                a *= qg * fmaf(gamma * py, q > 0.f ? t / q : 1.f, 1.f);
+                if (live && ok[c]) ce_sum += wn * (qg * t);
+            } else {
+                if (live && ok[c]) {
+                    const float t = ce_at(mx, c) + logf(ce_at(se, c)) - ce_at(picked, c);
+                    ce_sum += wn * t;
+                }
+            }
+            if constexpr (MODE == CEC_SMOOTH) {
+                a *= keep;
+                if (live && ok[c]) sm_sum += nu * fmaf(Wsum, logf(ce_at(se, c)), ce_at(swz, c));
+                const float bsm = gw * spread;
+                rs[c] = ok[c] ? bsm * Wsum / ce_at(se, c) : 0.f;
+                hs[c] = ok[c] ? bsm : 0.f;
+            }
+            r[c] = ok[c] ? a / ce_at(se, c) : 0.f;
+            h[c] = ok[c] ? a : 0.f;
+        }
+        float* d = dlogits + b * K * HW + p;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+                CE_PX ce_at(g, c) = ce_at(v[k], c) * r[c] - (lab[c] == k ? h[c] : 0.f);
+                if constexpr (MODE == CEC_SMOOTH) {
+                    const float wk = class_weight[k];
+                    CE_PX ce_at(g, c) += fmaf(ce_at(v[k], c), rs[c], -(wk * hs[c]));
+                }
+                if (live) {
+                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
+                    else d[k * HW] = g.x;
+                }
+                if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
+            }
+        if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, base, nq, xbuf);
+        else ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
+    }
+    ce_sum = wave_sum(ce_sum);
+    if constexpr (MODE == CEC_SMOOTH) sm_sum = wave_sum(sm_sum);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce_sum; red[1][threadIdx.x >> 6] = sm_sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+// out3 = {loss, keep * nll / D, spread * smo / D} from the nblocks partial pairs, ce_finalize_kernel's fixed-order fp64 sums; D == 0: zeros
+__global__ void __launch_bounds__(256) cec_finalize_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ tot,
+                                                           double keep, double spread, float* out3) {
+    __shared__ double red[2][256];
+    double a = 0, b = 0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double D = *reinterpret_cast<const double*>(tot + CEC_TOT_D);
+        const float nll = D > 0.0 ? (float)(keep * (red[0][0] / D)) : 0.f;
+        const float smo = D > 0.0 ? (float)(spread * (red[1][0] / D)) : 0.f;
+        out3[0] = nll + smo; out3[1] = nll; out3[2] = smo;
+    }
+}
+
 // ---- cross-entropy + soft Dice (build-defined; the definitions are restated in include/clamd.h) --------------------------------------
 // Dice is not per-pixel: its gradient at a pixel depends on the per-class sums I = sum p_k [y = k], P = sum p_k, Y = sum [y = k] over the
 // pixel's group (the batch, or its image).  Three passes, every reduction in a fixed order:
@@ -1078,6 +1285,48 @@ int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, cons
     // the kernel leaves sum_px of c_old * kd_px: the finalize multiplies by 1 / npix and by its `lam` argument
     ce_finalize(p, old_logits ? (float)(lam / (double)c_old) : 0.f, loss3);
     return clamd_check_launch("ce_unbiased_fwd_bwd");
+}
+
+size_t clamd_ce_class_workspace_bytes(void) { return (size_t)CEC_WS_WORDS * 4; }
+
+int clamd_ce_class_fwd_bwd(const float* logits, const long long* labels, const float* class_weight, const float* image_weight, float* dlogits,
+                           void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W,
+                           long long ignore_index, double label_smoothing, double focal_gamma, double grad_scale, void* stream) {
+    const char* who = "ce_class";
+    if (!class_weight || ((size_t)class_weight % 4)) return ce_fail(who, "class_weight (K floats) is required and must be 4-byte aligned");
+    if ((size_t)image_weight % 4) return ce_fail(who, "misaligned image_weight");
+    if (!(label_smoothing >= 0.0 && label_smoothing < 1.0)) return ce_fail(who, "label_smoothing must be in [0, 1)");
+    if (!(focal_gamma >= 0.0) || !isfinite(focal_gamma)) return ce_fail(who, "focal_gamma must be finite and >= 0");
+    if (label_smoothing > 0.0 && focal_gamma > 0.0) return ce_fail(who, "label_smoothing and focal_gamma are both non-zero: the combination is not defined");
+    if (workspace && (ws_bytes < clamd_ce_class_workspace_bytes() || ((size_t)workspace % 8)))
+        return ce_fail(who, "workspace too small (clamd_ce_class_workspace_bytes) or not 8-byte aligned");
+    CePlan p;
+    if (int e = ce_plan(&p, who, true, logits, labels, nullptr, dlogits, dl_nhwc, dl_ldc, dl_dtype, loss3, workspace, ws_bytes, B, K, H, W, stream)) return e;
+    unsigned int* tot = (unsigned int*)workspace + CEC_WS_TOT;
+    unsigned int* crows = (unsigned int*)workspace + CEC_WS_ROWS;
+    if (p.npix % 4 == 0 && ((size_t)labels % 32) == 0)
+        hipLaunchKernelGGL(class_count_rows_kernel<4>, dim3(CE_COUNT_BLOCKS), dim3(256), 0, p.s, labels, p.npix, ignore_index, K, crows);
+    else
+        hipLaunchKernelGGL(class_count_rows_kernel<1>, dim3(CE_COUNT_BLOCKS), dim3(256), 0, p.s, labels, p.npix, ignore_index, K, crows);
+    hipLaunchKernelGGL(class_totals_kernel, dim3(1), dim3(256), 0, p.s, crows, class_weight, K, p.totals, tot);
+    const double keep = 1.0 - label_smoothing, spread = label_smoothing / (double)K;
+    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
+        using NT = typename decltype(nt)::type;
+        auto launch = [&](auto kmax, auto npx, auto mode) {
+            hipLaunchKernelGGL((ce4c_kernel<decltype(kmax)::value, decltype(npx)::value, NT, decltype(mode)::value>), dim3(p.grid), dim3(256), 0, p.s,
+                               logits, labels, class_weight, image_weight, dlogits, p.partial, B, K, p.HW, ignore_index, (float)grad_scale,
+                               (float)keep, (float)spread, (float)focal_gamma, (NT*)dl_nhwc, dl_ldc, (const float*)tot);
+        };
+        auto by_mode = [&](auto kmax, auto npx) {
+            if (focal_gamma > 0.0) launch(kmax, npx, ce_int<CEC_FOCAL>{});
+            else if (label_smoothing > 0.0) launch(kmax, npx, ce_int<CEC_SMOOTH>{});
+            else launch(kmax, npx, ce_int<CEC_WEIGHT>{});
+        };
+        if (!p.four) return by_mode(ce_int<32>{}, ce_int<1>{});
+        ce_for_kmax(K, [&](auto kmax) { by_mode(kmax, ce_int<4>{}); });
+    });
+    hipLaunchKernelGGL(cec_finalize_kernel, dim3(1), dim3(256), 0, p.s, p.partial, p.grid, (const float*)tot, keep, spread, loss3);
+    return clamd_check_launch("ce_class_fwd_bwd");
 }
 
 }  // extern "C"

@@ -14,6 +14,9 @@ cross-entropy and unbiased distillation of Cermelli et al. (CVPR 2020) as includ
 ``CrossEntropyLoss()(logits, labels, image_weight)`` is the pseudo-label step's loss (build-defined, pseudo.py): every pixel's term times its
 image's weight, on ``clamd_ce_fwd_bwd_weighted``; without the weight nothing changes.
 
+``CrossEntropyLoss(weight=, label_smoothing=, focal_gamma=)`` is the generalised per-pixel loss (torch's class weights and label smoothing;
+the focal term build-defined) on ``clamd_ce_class_fwd_bwd``; ``class_weights`` derives the weights from per-image class pixel counts.
+
 ``DiceCrossEntropyLoss`` is cross-entropy plus soft Dice (build-defined, the compound loss of nnU-Net / MONAI's DiceCELoss), on
 ``clamd_ce_dice_fwd_bwd``: a sums pass, a coefficient pass and a gradient pass, every reduction in a fixed order.
 """
@@ -126,17 +129,118 @@ class _CEFn(torch.autograd.Function):
 
 
 class CrossEntropyLoss(nn.Module):
-    def __init__(self, ignore_index=-100):
+    """``nn.CrossEntropyLoss(weight=, ignore_index=, label_smoothing=)`` with mean reduction, plus ``focal_gamma`` (build-defined: the focal
+    modulation q^gamma of Lin et al. with q = 1 - p_y; not together with label smoothing).  With the three keyword arguments at their
+    defaults the forward is the plain loss on the entry points it always used; any of them set takes ``clamd_ce_class_fwd_bwd`` (the
+    definition is in include/clamd.h).  ``weight``: K finite numbers >= 0, kept as a non-persistent fp32 buffer (``.to(device)`` moves it;
+    ``set_weight`` replaces it); None with smoothing or the focal term means unit weights.  The weighted mean divides by the sum of the valid
+    pixels' class weights, as torch does; where that sum is 0 the loss and every gradient are 0 (torch: NaN).  After a forward: ``parts`` =
+    device {loss, (1 - eps) nll / D, (eps / K) smo / D}, ``bad_labels`` = device int32[1]."""
+
+    def __init__(self, ignore_index=-100, *, weight=None, label_smoothing=0.0, focal_gamma=0.0):
         super().__init__()
         self.ignore_index = ignore_index
+        self.label_smoothing, self.focal_gamma = check_smoothing_and_gamma(label_smoothing, focal_gamma)
+        self.register_buffer('weight', None, persistent=False)
+        self.set_weight(weight)
         self.bad_labels = None        # after a forward: device int32[1], labels that are neither ignore_index nor a class
+        self.parts = None
+        self._unit = None             # the unit weights of smoothing / focal without `weight` (forward)
+
+    def set_weight(self, weight):
+        """Replaces the class weights (None: none); checked on the host: one dimension, finite, >= 0.  The length is checked against the
+        logits at the next forward."""
+        if weight is not None:
+            dev = self.weight.device if self.weight is not None else getattr(weight, 'device', None)
+            weight = check_class_weight(weight).to(dev or 'cpu')
+        self.weight = weight
+
+    @property
+    def generalised(self):
+        return self.weight is not None or self.label_smoothing > 0.0 or self.focal_gamma > 0.0
 
     def forward(self, logits, labels, image_weight=None):
         """image_weight (fp32 [B] on the device, e.g. PseudoLabeler's nu): every pixel's term and gradient times its image's weight, the mean
-        still over the unweighted count of valid pixels (clamd_ce_fwd_bwd_weighted; build-defined).  None: the plain loss."""
+        still over the unweighted count of valid pixels (clamd_ce_fwd_bwd_weighted; build-defined) or, with class weights, over their
+        unweighted sum D.  None: the plain loss."""
+        if self.generalised:
+            K = logits.shape[1]
+            w = self.weight
+            if w is None:             # unit weights: one vector per (K, device), kept -- no allocation or fill launch per step
+                w = self._unit
+                if w is None or w.numel() != K or w.device != logits.device:
+                    w = self._unit = torch.ones(K, dtype=torch.float32, device=logits.device)
+            elif w.numel() != K:
+                raise ValueError(f'CrossEntropyLoss: weight has {w.numel()} entries, the logits have {K} classes')
+            nu = None if image_weight is None else image_weight.detach()
+            return _ClassCEFn.apply(logits, labels, w, nu, self.label_smoothing, self.focal_gamma, self.ignore_index, self)
         if image_weight is not None:
             return _WCEFn.apply(logits, labels, image_weight.detach(), self.ignore_index, self)
         return _CEFn.apply(logits, labels, None, 0, 1.0, 0.0, self.ignore_index, self)
+
+
+def check_smoothing_and_gamma(label_smoothing, focal_gamma):
+    """-> (float, float); ValueError outside [0, 1) / [0, inf) or with both non-zero."""
+    eps, gamma = float(label_smoothing), float(focal_gamma)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f'label_smoothing must be in [0, 1), got {label_smoothing!r}')
+    if not (gamma >= 0.0 and gamma != float('inf')):
+        raise ValueError(f'focal_gamma must be finite and >= 0, got {focal_gamma!r}')
+    if eps > 0.0 and gamma > 0.0:
+        raise ValueError('label_smoothing and focal_gamma are both non-zero: the combination is not defined (clamd_ce_class_fwd_bwd)')
+    return eps, gamma
+
+
+MIN_POSITIVE_WEIGHT = 1e-30      # the smallest positive class weight (include/clamd.h)
+
+
+def check_class_weight(weight, num_classes=None):
+    """-> a detached fp32 [K] tensor of `weight` (a tensor or a sequence of numbers); ValueError unless one-dimensional, non-empty, finite,
+    each entry 0 or >= MIN_POSITIVE_WEIGHT, and (when given) of length num_classes.  Reads the values: call it when the weights are set, not per step."""
+    w = torch.as_tensor(weight).detach().to(torch.float32)
+    if w.dim() != 1 or w.numel() == 0:
+        raise ValueError(f'class weights must be a non-empty vector, got shape {tuple(w.shape)}')
+    if num_classes is not None and w.numel() != int(num_classes):
+        raise ValueError(f'class weights must have {int(num_classes)} entries (one per class), got {w.numel()}')
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError('class weights must be finite and >= 0')
+    if bool(((w > 0) & (w < MIN_POSITIVE_WEIGHT)).any()):      # 1 / (float)D must stay finite: D >= the smallest positive weight
+        raise ValueError(f'a class weight must be 0 or at least {MIN_POSITIVE_WEIGHT:g} (include/clamd.h: grad_scale / D is formed in fp32)')
+    return w.clone()
+
+
+def class_weights(counts, scheme, normalize=False):
+    """Class weights from per-image class pixel counts: `counts` an integer [N, K] tensor (``replay.class_pixel_counts`` over a loader,
+    concatenated).  -> fp32 [K] on the CPU, computed in float64.
+      'median_frequency'  (Eigen & Fergus, ICCV 2015)  freq_k = n_k / (pixels of the images that contain k),  w_k = median(freq) / freq_k
+      'inverse_log'       (ENet, Paszke et al. 2016)   w_k = 1 / ln(1.02 + n_k / sum n)
+    n_k = the class's pixels over all images; the median is over the classes that occur; a class that never occurs gets 1.0.
+    normalize: rescaled to mean 1 over the classes that occur."""
+    c = torch.as_tensor(counts)
+    if c.dim() != 2 or c.is_floating_point() or c.is_complex() or c.dtype == torch.bool:
+        raise ValueError(f'counts must be an integer [N, K] tensor, got {c.dtype} {tuple(c.shape)}')
+    c = c.detach().cpu().to(torch.int64)
+    if bool((c < 0).any()):
+        raise ValueError('counts must be >= 0')
+    n = c.sum(0).double()
+    present = n > 0
+    w = torch.ones(c.shape[1], dtype=torch.float64)
+    if bool(present.any()):
+        if scheme == 'median_frequency':
+            per_image = c.sum(1, keepdim=True)                                   # the image's labelled pixels
+            support = (per_image * (c > 0)).sum(0).double()                      # pixels of the images that contain the class
+            freq = n[present] / support[present]
+            fs = freq.sort().values                                              # the median of an even number: the middle pair's mean
+            w[present] = 0.5 * (fs[(fs.numel() - 1) // 2] + fs[fs.numel() // 2]) / freq
+        elif scheme == 'inverse_log':
+            w[present] = 1.0 / torch.log(1.02 + n[present] / n.sum())
+        else:
+            raise ValueError(f"scheme must be 'median_frequency' or 'inverse_log', not {scheme!r}")
+        if normalize:
+            w[present] = w[present] / w[present].mean()
+    elif scheme not in ('median_frequency', 'inverse_log'):
+        raise ValueError(f"scheme must be 'median_frequency' or 'inverse_log', not {scheme!r}")
+    return w.float()
 
 
 class DistillationCrossEntropy(nn.Module):
@@ -182,6 +286,32 @@ class _WCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return _CEFn.backward(ctx, g)[:5]
+
+
+class _ClassCEFn(torch.autograd.Function):
+    """clamd_ce_class_fwd_bwd (it counts for itself); the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weight, image_weight, label_smoothing, focal_gamma, ignore_index, holder):
+        def middle(counted, logits, *_):
+            B, K = logits.shape[:2]
+            if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
+                raise ValueError(f'class weights must be float32 [{K}], got {class_weight.dtype} {tuple(class_weight.shape)}')
+            nu = None
+            if image_weight is not None:
+                if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
+                    raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
+                nu = image_weight.contiguous()
+            # algorithmic bytes: the plain loss's plus the counting pass's second read of the labels (the K + B weights do not count)
+            cw = class_weight.contiguous()
+            counted('clamd_ce_class_fwd_bwd', (ptr(cw), ptr(nu)), px_bytes=8, count=False,
+                    tail=(float(label_smoothing), float(focal_gamma)))
+        return _forward(ctx, holder, logits, labels, ignore_index, (class_weight, image_weight), middle,
+                        lambda lib, B, K, H, W: lib.clamd_ce_class_workspace_bytes())
+
+    @staticmethod
+    def backward(ctx, g):
+        return _CEFn.backward(ctx, g)
 
 
 class UnbiasedDistillationCrossEntropy(nn.Module):

@@ -14,7 +14,9 @@ code below reads plain ``cfg.name``.  The build-defined switches are off by defa
 ``optimizer='sgd'`` (FusedSGD with momentum, nesterov, weight_decay), ``lr_schedule='iteration'`` (make_scheduler), ``sync_bn``
 (syncbn.py), ``augment`` (every training batch, replayed rows included, rescaled, cropped or padded and flipped in one launch
 before the forward pass, augment.py), ``loss='ce_dice'`` (loss.DiceCrossEntropyLoss as the step's criterion: each rank's Dice sums cover
-its own batch, and ``estimate_importance`` keeps the plain log-likelihood), ``path_integral`` (consolidate.PathIntegral: Synaptic
+its own batch, and ``estimate_importance`` keeps the plain log-likelihood), ``class_weights`` / ``label_smoothing`` / ``focal_gamma``
+(loss.CrossEntropyLoss with them as the step's criterion; ``set_class_weights`` sets the weights later, grow_head extends them with ones,
+a checkpoint carries them; each rank divides by its own weight sum), ``path_integral`` (consolidate.PathIntegral: Synaptic
 Intelligence's path integral, tracked inside every optimiser step from the first one), ``max_grad_norm`` (optim.set_grad_clip: the
 global gradient norm clipped inside the optimiser step; nnU-Net trains with 12).
 Continual learning (config 4): ``Trainer.begin_task2`` is the task boundary; its docstring numbers the stages once and places every
@@ -29,13 +31,14 @@ import torch
 import torch.nn as nn
 from torch.optim.lr_scheduler import LambdaLR
 
-from .loss import CrossEntropyLoss, DiceCrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy
+from .loss import (CrossEntropyLoss, DiceCrossEntropyLoss, DistillationCrossEntropy, UnbiasedDistillationCrossEntropy, check_class_weight,
+                   check_smoothing_and_gamma, class_weights)
 from .metrics import argmax_confusion, metrics_from_confusion
 from .optim import FusedAdam, FusedSGD
 from .consolidate import Consolidation, PathIntegral
 from .pseudo import PseudoLabeler
 from .pod import LocalPODLoss
-from .replay import ReplayMemory
+from .replay import ReplayMemory, class_pixel_counts
 from .augment import RandomScaleCrop
 from . import syncbn
 from .unet import UNet
@@ -48,7 +51,8 @@ def default_config(**kw):
                augment=False, augment_scale=(0.5, 2.0), augment_flip=True, augment_seed=0,
                optimizer='adam', momentum=0.9, nesterov=True, weight_decay=1e-4, decay_norm_and_bias=True, lr_schedule='epoch',
                max_iters=None, path_integral=False, si_xi=0.1, max_grad_norm=None,
-               loss='ce', dice_weight=1.0, dice_smooth=1e-5, dice_include_background=True, dice_present_only=True, dice_per_image=False)
+               loss='ce', dice_weight=1.0, dice_smooth=1e-5, dice_include_background=True, dice_present_only=True, dice_per_image=False,
+               class_weights=None, label_smoothing=0.0, focal_gamma=0.0)
     cfg.update(kw)
     return SimpleNamespace(**cfg)
 
@@ -164,8 +168,48 @@ class Trainer:
                                                cfg.dice_per_image).to(self.device)
         elif cfg.loss != 'ce':
             raise ValueError(f"loss must be 'ce' or 'ce_dice', not {cfg.loss!r}")
+        eps, gamma = check_smoothing_and_gamma(cfg.label_smoothing, cfg.focal_gamma)
+        weights = None if cfg.class_weights is None else check_class_weight(cfg.class_weights, cfg.num_classes)
+        if weights is not None or eps > 0 or gamma > 0:      # a criterion of its own: likelihood_loss stays the plain one
+            if cfg.loss == 'ce_dice':
+                raise ValueError("loss='ce_dice' with class_weights, label_smoothing or focal_gamma: DiceCrossEntropyLoss's cross-entropy term "
+                                 "is the plain one (use loss='ce')")
+            self.c_loss = CrossEntropyLoss(weight=weights, label_smoothing=eps, focal_gamma=gamma).to(self.device)
         self.augment = RandomScaleCrop(scale=cfg.augment_scale, flip=cfg.augment_flip, ignore_index=self.c_loss.ignore_index,
                                        seed=int(cfg.augment_seed) + syncbn.rank()) if cfg.augment else None      # each rank draws its own
+
+    def class_criterion_active(self):
+        """Whether the step's criterion is the generalised cross-entropy (class weights, label smoothing or the focal term)."""
+        return isinstance(self.c_loss, CrossEntropyLoss) and self.c_loss.generalised
+
+    @property
+    def class_weight(self):
+        """The active class weights (a device fp32 [num_classes] tensor) or None."""
+        return self.c_loss.weight if isinstance(self.c_loss, CrossEntropyLoss) else None
+
+    def set_class_weights(self, weights_or_scheme, loader=None):
+        """The step's class weights: a vector of num_classes finite numbers >= 0, or a scheme of loss.class_weights ('median_frequency',
+        'inverse_log') with a loader of (images, masks) batches whose masks are counted on the device (replay.class_pixel_counts), or None
+        for none.  May be called again, e.g. after grow_head with the new task's loader.  -> the weights (fp32 on the device) or None."""
+        if self.cfg.loss != 'ce':
+            raise ValueError("set_class_weights needs loss='ce': DiceCrossEntropyLoss's cross-entropy term is the plain one")
+        if weights_or_scheme is not None and self.distill is not None:      # the step would run self.distill and never read them
+            raise ValueError('set_class_weights after begin_task2(distill_lambda > 0 or unbiased=True): the step runs '
+                             f'{type(self.distill).__name__}, which has no class weights (begin_task2 refuses the combination as well)')
+        K = self.cfg.num_classes
+        if isinstance(weights_or_scheme, str):
+            if loader is None:
+                raise ValueError(f'set_class_weights({weights_or_scheme!r}) needs a loader to count the classes on')
+            counts = [class_pixel_counts(masks.to(self.device, non_blocking=True), K, self.c_loss.ignore_index) for _, masks in loader]
+            if not counts:
+                raise ValueError('set_class_weights: the loader gave no batch')
+            weights = class_weights(torch.cat(counts).cpu(), weights_or_scheme)
+        else:
+            weights = None if weights_or_scheme is None else check_class_weight(weights_or_scheme, K)
+        if self.c_loss is self.likelihood_loss:      # the step gets a criterion of its own: estimate_importance keeps the plain one
+            self.c_loss = CrossEntropyLoss(self.c_loss.ignore_index).to(self.device)
+        self.c_loss.set_weight(None if weights is None else weights.to(self.device))
+        return self.c_loss.weight
 
     def _make_optimizer(self):
         optim = self._new_optimizer()
@@ -324,6 +368,13 @@ class Trainer:
         if pseudo_label and pseudo_adaptive and distill_lambda > 0:
             raise ValueError('pseudo_adaptive=True with distill_lambda > 0: DistillationCrossEntropy has no per-image weight '
                              '(use distill_lambda=0, or pseudo_adaptive=False)')
+        if self.class_criterion_active():
+            if unbiased:
+                raise ValueError('class_weights, label_smoothing or focal_gamma with unbiased=True: UnbiasedDistillationCrossEntropy has none '
+                                 'of them (its kernel is another one; pseudo_label=True and pod_lambda > 0 combine with them)')
+            if distill_lambda > 0:
+                raise ValueError('class_weights, label_smoothing or focal_gamma with distill_lambda > 0: DistillationCrossEntropy has none '
+                                 'of them (use distill_lambda=0, with pod_lambda > 0 for distillation)')
         if self.cfg.loss == 'ce_dice':
             if unbiased:
                 raise ValueError("loss='ce_dice' with unbiased=True: the Dice term is not defined inside the unbiased criterion "
@@ -402,6 +453,9 @@ class Trainer:
         if self.consolidation is not None and self.ewc_lambda > 0:
             self._install_consolidation(self.optim.l2_lambda)
         self.cfg.num_classes = m.num_classes
+        w = self.class_weight
+        if w is not None:             # the new classes weigh 1.0 until set_class_weights is called again
+            self.c_loss.set_weight(torch.cat([w, w.new_ones(m.num_classes - w.numel())]))
 
     # ---- checkpoints: same file name and keys as trainer.py:68-102, but the model never leaves the GPU: the reference
     # does network.cpu() ... network.cuda() (124 MB each way every epoch, trainer.py:75,80-81,258); here a side stream copies the state out.
@@ -430,6 +484,8 @@ class Trainer:
                 snap['path_state'] = _host_copy(self.path.state_dict())
             if self.replay is not None:
                 snap['replay_state'] = dict(_host_copy(self.replay.state_dict()), batch=self.replay_batch, boundary=self.replay_boundary)
+            if self.class_weight is not None:        # the active class weights (cfg.class_weights, set_class_weights, grow_head)
+                snap['class_weight_state'] = {'weight': _host_copy(self.class_weight.detach().clone())}
             snap['_event'] = torch.cuda.Event()
             snap['_event'].record(st)
         snap['scheduler_state'] = self.scheduler.state_dict()
@@ -441,7 +497,7 @@ class Trainer:
         """trainer.py:68-81: '<epoch_label>_net_<network_label>.pth' with keys epoch/model_state/optimizer_state/scheduler_state (loadable by
         the reference's load_network and by torch.optim.Adam) and snapshot()'s optional keys, which the reference ignores: consolidation_state
         (anchor, importance, n_batches, gamma; lambda), path_state (omega, start, xi), replay_state (ReplayMemory.state_dict(); batch,
-        boundary) and augment_state (RandomScaleCrop.state_dict())."""
+        boundary), augment_state (RandomScaleCrop.state_dict()) and class_weight_state (weight: the active class weights)."""
         snap = self.snapshot(epoch)
         snap.pop('_event').synchronize()
         snap['model_state'] = {k: v.clone() for k, v in snap['model_state'].items()}   # pinned buffers are reused
@@ -464,7 +520,18 @@ class Trainer:
         self.load_path_state(ck.get('path_state'))
         self.load_replay_state(ck.get('replay_state'))
         self.load_augment_state(ck.get('augment_state'))
+        self.load_class_weight_state(ck.get('class_weight_state'))
         return True
+
+    def load_class_weight_state(self, state):
+        """Restores what snapshot() stored under 'class_weight_state' (None, e.g. a checkpoint without the key: nothing changes)."""
+        if state is None:
+            return
+        n = int(state['weight'].numel())
+        if n != self.cfg.num_classes:
+            raise ValueError(f'the checkpoint carries class weights for {n} classes, this trainer has {self.cfg.num_classes}: it was written '
+                             f'after grow_head -- build the Trainer with num_classes={n}, or grow its head, before load_network')
+        self.set_class_weights(state['weight'])
 
     def load_path_state(self, state):
         """Restores what snapshot() stored under 'path_state' (None, e.g. a checkpoint without the key: nothing changes -- a path integral

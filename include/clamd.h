@@ -438,6 +438,40 @@ int clamd_ce_dice_fwd_bwd(const float* logits, const long long* labels, float* d
                           float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W, long long ignore_index,
                           double w_ce, double w_dice, double smooth, int first_class, int present_only, int per_image,
                           double grad_scale, void* stream);
+/* ---- class weights, label smoothing and the focal term (loss.hip) ---------------------------------------------
+ * The generalised per-pixel cross-entropy: torch's F.cross_entropy(weight=, label_smoothing=, ignore_index=) and, build-defined, the focal
+ * modulation of Lin et al. (ICCV 2017) with its exponent applied to q = 1 - p_y.
+ * Logits z fp32 NCHW [B,K,H,W], labels y int64 [B,H,W], 1 <= K <= 32; class weights w fp32 [K], finite, each 0 or >= 1e-30 (grad_scale / D is
+ * formed in fp32: a smaller positive D would overflow it; not checked here: a read-back would be needed; loss.py checks them when they are set); image weights nu fp32 [B], NULL = 1; eps = label_smoothing in [0, 1);
+ * gamma = focal_gamma >= 0; eps > 0 and gamma > 0 together are rejected.
+ *   valid pixel   y != ignore_index and y in [0, K); another non-ignore label is counted as a bad label, as by the clamd_ce_* entry points
+ *   p = softmax(z),  p_y the target's probability,  q = sum_{k != y} p_k (summed, never 1 - p_y),  t = -log p_y,  W = sum_k w_k
+ *   D     = sum_valid w_y                                 torch's denominator; NOT multiplied by nu, as clamd_ce_fwd_bwd_weighted keeps N
+ *   nll   = sum_valid nu_b w_y q^gamma t
+ *   smo   = sum_valid nu_b sum_k w_k (-log p_k)           a pixel whose own class weight is 0 keeps its smoothing term, as in torch
+ *   loss  = ((1 - eps) nll + (eps / K) smo) / D;          loss3 = {loss, (1 - eps) nll / D, (eps / K) smo / D}, loss their fp32 sum
+ *   f     = 1 (gamma == 0);  q^gamma (1 + gamma p_y t / q) (gamma > 0; t / q -> 1 as q -> 0)
+ *   d loss / d z_k = grad_scale * nu_b / D * [ (1 - eps) w_y f (p_k - [k = y]) + (eps / K) (W p_k - w_k) ]     exactly 0 on invalid pixels
+ * D == 0 (nothing valid, or every valid pixel on a class of weight 0): loss3 = {0, 0, 0} and every gradient exactly 0.  torch returns NaN
+ * there; this library's convention is the max(N, 1) of the other criteria.
+ * Four launches: a per-class count (one partial row {n_0 .. n_31, valid, bad} per workgroup: an integer histogram in LDS, plain stores), a
+ * one-workgroup totals pass (the rows added; D = sum_k (double)w_k n_k and W in ascending k), the loss / gradient pass (clamd_ce_fwd_bwd_counted's
+ * shape: four pixels per thread with 16-byte logit and 32-byte label accesses when H * W % 4 == 0 and logits / dlogits are 16-byte, labels
+ * 32-byte aligned, else a one-pixel variant of the same arithmetic; dl_nhwc / dl_ldc / dl_dtype as there) and a finalize (both partial
+ * columns in fp64 in a fixed order).  Enqueue only, counts for itself: no allocation, no synchronisation, no memset, no float atomics
+ * (bit-reproducible), graph-capturable.
+ * With every w_k == 1.0f, eps == 0 and gamma == 0 the results (d logits, the NHWC copy, loss3) equal clamd_ce_count +
+ * clamd_ce_fwd_bwd_counted's bit for bit without image weights and clamd_ce_fwd_bwd_weighted's with them: the pixel's coefficient is
+ * a = (grad_scale / (float)D) nu_b w_y, the gradient e_k (a / sum e) - [k = y] a.
+ * Workspace: clamd_ce_class_workspace_bytes() bytes, 8-byte aligned; its first clamd_ce_workspace_bytes() bytes are laid out as the CE
+ * workspace (clamd_ce_bad_label_count_offset() finds the bad-label counter, the valid count sits in the word before it).
+ * Rejected before any launch: a null or misaligned class_weight; a misaligned image_weight; eps outside [0, 1); gamma negative or not
+ * finite; eps and gamma both non-zero; a workspace that is too small or unaligned; everything clamd_ce_fwd_bwd_counted rejects but the
+ * size and alignment that select the one-pixel variant. */
+size_t clamd_ce_class_workspace_bytes(void);
+int clamd_ce_class_fwd_bwd(const float* logits, const long long* labels, const float* class_weight, const float* image_weight, float* dlogits,
+                           void* dl_nhwc, int dl_ldc, int dl_dtype, float* loss3, void* workspace, size_t ws_bytes, int B, int K, int H, int W,
+                           long long ignore_index, double label_smoothing, double focal_gamma, double grad_scale, void* stream);
 /* ---- pseudo-labelling of the old classes (pseudo.hip; its loss clamd_ce_fwd_bwd_weighted: loss.hip) -----------
  * Build-defined, parity unpinned (the reference has no continual-learning code): the classification half of PLOP (Douillard et al.,
  * CVPR 2021, section 3.2).  In a task-2 batch every pixel of an old class is labelled 0; the frozen old model labels the background
