@@ -68,7 +68,6 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
                                                  float inv_temp, float lam, float* __restrict__ dlogits,
                                                  float* __restrict__ partial, const unsigned int* __restrict__ count_rows,
                                                  int B, int K, long long HW, long long ignore_index, float grad_scale) {
-    __shared__ float red[2][4];
     __shared__ unsigned int cnt_tmp[4];
     const long long npix = (long long)B * HW;
     const float inv_valid = 1.f / (float)max(ce_count_total(count_rows, 0, cnt_tmp), 1u);
@@ -135,15 +134,7 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
         for (int k = 0; k < KMAX; ++k)
             if (k < K) d[k * HW] = g[k] * grad_scale;
     }
-    ce_sum = wave_sum(ce_sum);
-    kd_sum = wave_sum(kd_sum);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = ce_sum; red[1][wave] = kd_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    ce_block_pair<true>(wave_sum(ce_sum), wave_sum(kd_sum), partial);
 }
 
 struct ce_no_nhwc {};
@@ -240,7 +231,6 @@ __global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logi
                                                   float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
                                                   long long ignore_index, float grad_scale, NT* dl_nhwc, int dl_ldc,
                                                   const unsigned int* __restrict__ count_rows) {
-    __shared__ float red[4];
     __shared__ unsigned int cnt_tmp[4];
     const long long nq = (long long)B * HW / NPX;
     const unsigned int nv = ce_count_total(count_rows, 0, cnt_tmp);
@@ -291,10 +281,7 @@ __global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logi
             if (k < K) {
                 float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
                 CE_PX ce_at(g, c) = ce_at(v[k], c) * r[c] - (lab[c] == k ? h[c] : 0.f);
-                if (live) {
-                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
-                    else d[k * HW] = g.x;
-                }
+                if (live) ce_stpx<NPX>(d + k * HW, g);
                 if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
             }
         if constexpr (NPX == 1) ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
@@ -352,13 +339,7 @@ __global__ void __launch_bounds__(256) ce4_kernel(const float* __restrict__ logi
                 }
         }
     }
-    ce_sum = wave_sum(ce_sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ce_sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0] + red[1] + red[2] + red[3];
-        partial[2 * blockIdx.x + 1] = 0.f;
-    }
+    ce_block_pair<false>(wave_sum(ce_sum), 0.f, partial);
 }
 
 // The class-incremental step (build-defined, parity unpinned: the reference has no continual-learning code; the definitions are the "MiB"
@@ -383,7 +364,6 @@ __global__ void __launch_bounds__(256) ce4u_kernel(const float* __restrict__ log
                                                    const unsigned int* __restrict__ count_rows) {
     constexpr bool KD = KOLD > 0;
     constexpr float NEG = -INFINITY, TINY = 1e-18f;
-    __shared__ float red[2][4];
     __shared__ unsigned int cnt_tmp[4];
     const long long nq = (long long)B * HW / NPX;
     const unsigned int nv = ce_count_total(count_rows, 0, cnt_tmp);
@@ -518,40 +498,24 @@ __global__ void __launch_bounds__(256) ce4u_kernel(const float* __restrict__ log
                         ce_at(g, c) = t;
                     }
                 }
-                if (live) {
-                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
-                    else d[k * HW] = g.x;
-                }
+                if (live) ce_stpx<NPX>(d + k * HW, g);
                 if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
             }
         if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, base, nq, xbuf);
         else ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
     }
-    ce_sum = wave_sum(ce_sum);
-    kd_sum = wave_sum(kd_sum);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce_sum; red[1][threadIdx.x >> 6] = kd_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    ce_block_pair<true>(wave_sum(ce_sum), wave_sum(kd_sum), partial);
 }
 
 // out3 = {total, ce, kd} from the nblocks partial pairs (summed in double, in a fixed order); totals = {valid, bad} from the count rows
 __global__ void ce_finalize_kernel(const float* __restrict__ partial, int nblocks, unsigned int* totals,
                                    float inv_npix, float lam, float* out3, const unsigned int* __restrict__ count_rows) {
-    __shared__ double red[2][256];
     __shared__ unsigned int cnt_tmp[2][4];
     const unsigned int nvalid = ce_count_total(count_rows, 0, cnt_tmp[0]), nbad = ce_count_total(count_rows, 1, cnt_tmp[1]);
     if (threadIdx.x == 0) { totals[0] = nvalid; totals[1] = nbad; }
     double a = 0, b = 0;
     for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
+    const ce_tree_row* red = ce_tree_pair(a, b);
     if (threadIdx.x == 0) {
         const float ce = (float)(red[0][0] / (double)max(nvalid, 1u));
         const float kd = (float)(red[1][0] * inv_npix * lam);
@@ -601,7 +565,7 @@ __global__ void __launch_bounds__(256) class_count_rows_kernel(const long long* 
 }
 
 // One workgroup: thread (slice s = t / 34, column c = t % 34) adds rows s, s + 7, ... (integers); thread c < 34 adds the 7 slices.  Then D
-// and W by one thread, in fp64, k ascending.  totals = {valid, bad} where loss._forward and the other criteria keep them.
+// and W by one thread, in fp64, k ascending.  totals = {valid, bad} where loss._LossFn and the other criteria keep them.
 constexpr int CEC_SLICES = 256 / CEC_ROW_WORDS;                 // 7
 __global__ void __launch_bounds__(256) class_totals_kernel(const unsigned int* __restrict__ rows, const float* __restrict__ class_weight, int K,
                                                            unsigned int* totals, unsigned int* tot /* the totals block */) {
@@ -646,7 +610,6 @@ __global__ void __launch_bounds__(256) ce4c_kernel(const float* __restrict__ log
                                                    float* __restrict__ dlogits, float* __restrict__ partial, int B, int K, long long HW,
                                                    long long ignore_index, float grad_scale, float keep /* 1 - eps */, float spread /* eps / K */,
                                                    float gamma, NT* dl_nhwc, int dl_ldc, const float* __restrict__ tot) {
-    __shared__ float red[2][4];
     const long long nq = (long long)B * HW / NPX;
     const double Dd = *reinterpret_cast<const double*>(tot + CEC_TOT_D);
     const float Wsum = tot[CEC_TOT_W];
@@ -726,10 +689,7 @@ __global__ void __launch_bounds__(256) ce4c_kernel(const float* __restrict__ log
                     const float wk = class_weight[k];
                     CE_PX ce_at(g, c) += fmaf(ce_at(v[k], c), rs[c], -(wk * hs[c]));
                 }
-                if (live) {
-                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
-                    else d[k * HW] = g.x;
-                }
+                if (live) ce_stpx<NPX>(d + k * HW, g);
                 if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
             }
         if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, base, nq, xbuf);
@@ -737,26 +697,15 @@ __global__ void __launch_bounds__(256) ce4c_kernel(const float* __restrict__ log
     }
     ce_sum = wave_sum(ce_sum);
     if constexpr (MODE == CEC_SMOOTH) sm_sum = wave_sum(sm_sum);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce_sum; red[1][threadIdx.x >> 6] = sm_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    ce_block_pair<true>(ce_sum, sm_sum, partial);      // two columns in every mode: the LDS of the kernel as it was (four zeros add to 0.f)
 }
 
 // out3 = {loss, keep * nll / D, spread * smo / D} from the nblocks partial pairs, ce_finalize_kernel's fixed-order fp64 sums; D == 0: zeros
 __global__ void __launch_bounds__(256) cec_finalize_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ tot,
                                                            double keep, double spread, float* out3) {
-    __shared__ double red[2][256];
     double a = 0, b = 0;
     for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
+    const ce_tree_row* red = ce_tree_pair(a, b);
     if (threadIdx.x == 0) {
         const double D = *reinterpret_cast<const double*>(tot + CEC_TOT_D);
         const float nll = D > 0.0 ? (float)(keep * (red[0][0] / D)) : 0.f;
@@ -951,7 +900,6 @@ __global__ void __launch_bounds__(256) dice_grad_kernel(const float* __restrict_
                                                         int K, long long HW, long long ignore_index, float grad_scale, float w_ce,
                                                         NT* dl_nhwc, int dl_ldc) {
     PASS_PRIO();
-    __shared__ float red[4];
     __shared__ float ta[DICE_KP];
     constexpr bool XCH = NPX == 4 && __is_same(NT, bf16_t) && CE_EXCHANGE;
     __shared__ uint4 xbuf[XCH ? 4 : 1][XCH ? 1024 : 1];
@@ -1013,38 +961,23 @@ __global__ void __launch_bounds__(256) dice_grad_kernel(const float* __restrict_
                     const float gk = ck[k] + (hit ? ay[c] : 0.f);
                     ce_at(g, c) = ce_at(v[k], c) * fmaf(rd[c], gk - dot[c], rce[c]) - (hit ? h[c] : 0.f);
                 }
-                if (live) {
-                    if constexpr (NPX == 4) *reinterpret_cast<float4*>(d + k * HW) = g;
-                    else d[k * HW] = g.x;
-                }
+                if (live) ce_stpx<NPX>(d + k * HW, g);
                 if constexpr (!__is_same(NT, ce_no_nhwc)) v[k] = g;
             }
         // the NHWC copy: `base` and the bound are this image's -- the exchange must not reach into the next image from the tail's dead lanes
         if constexpr (NPX == 4) ce_store_nhwc4<KMAX, NT, XCH>(v, K, dl_nhwc, dl_ldc, pix, q0 + lbase, q0 + nq, xbuf);
         else ce_store_nhwc1<KMAX, NT>(v, K, dl_nhwc, dl_ldc, pix);
     }
-    ce_sum = wave_sum(ce_sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ce_sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x + 0] = red[0] + red[1] + red[2] + red[3];
-        partial[2 * blockIdx.x + 1] = 0.f;
-    }
+    ce_block_pair<false>(wave_sum(ce_sum), 0.f, partial);
 }
 
 // loss3 = {ce + dice, ce = w_ce * mean CE, dice = w_dice * mean_g gterm}: the CE partials and the group terms added in fp64 in a fixed order
 __global__ void __launch_bounds__(256) dice_finalize_kernel(const float* __restrict__ partial, int nblocks, const unsigned int* __restrict__ totals,
                                                             const double* __restrict__ gterm, int G, double w_ce, double w_dice, float* out3) {
-    __shared__ double red[2][256];
     double a = 0, b = 0;
     for (int i = threadIdx.x; i < nblocks; i += 256) a += partial[2 * i];
     for (int i = threadIdx.x; i < G; i += 256) b += gterm[i];
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
+    const ce_tree_row* red = ce_tree_pair(a, b);
     if (threadIdx.x == 0) {
         const float ce = (float)(w_ce * (red[0][0] / (double)max(totals[0], 1u)));
         const float dice = (float)(w_dice * (red[1][0] / (double)G));
@@ -1098,17 +1031,25 @@ static int ce_plan(CePlan* p, const char* who, bool four_ok, const float* logits
     return 0;
 }
 
-// f(tag) with the element type of the NHWC copy (ce_plan has checked dl_dtype) and with KMAX, the smallest multiple of 8 that holds K
+// The family's one dispatch: f(nt, kmax, npx) with the element type of the NHWC copy (ce_plan has checked dl_dtype; dl_nhwc null: ce_no_nhwc)
+// and the kernel's shape: (32, 1), one pixel per thread, when !p.four; else (KMAX, 4), KMAX the smallest multiple of 8 that holds K.
+// CE_T / CE_V: a tag's type / value inside f.
 template <typename T> struct ce_type { using type = T; };
 template <int N> using ce_int = std::integral_constant<int, N>;
-template <typename F> static void ce_for_nt(const void* dl_nhwc, int dl_dtype, F f) {
-    if (!dl_nhwc) f(ce_type<ce_no_nhwc>{});
-    else if (dl_dtype == CLAMD_BF16) f(ce_type<bf16_t>{});
-    else if (dl_dtype == CLAMD_F32) f(ce_type<float>{});
-    else f(ce_type<split_t>{});
-}
-template <typename F> static void ce_for_kmax(int K, F f) {
-    if (K <= 8) f(ce_int<8>{}); else if (K <= 16) f(ce_int<16>{}); else if (K <= 24) f(ce_int<24>{}); else f(ce_int<32>{});
+#define CE_T(tag) typename decltype(tag)::type
+#define CE_V(tag) decltype(tag)::value
+template <typename F> static void ce_dispatch(const CePlan& p, int K, const void* dl_nhwc, int dl_dtype, F f) {
+    auto shaped = [&](auto nt) {
+        if (!p.four) f(nt, ce_int<32>{}, ce_int<1>{});
+        else if (K <= 8) f(nt, ce_int<8>{}, ce_int<4>{});
+        else if (K <= 16) f(nt, ce_int<16>{}, ce_int<4>{});
+        else if (K <= 24) f(nt, ce_int<24>{}, ce_int<4>{});
+        else f(nt, ce_int<32>{}, ce_int<4>{});
+    };
+    if (!dl_nhwc) shaped(ce_type<ce_no_nhwc>{});
+    else if (dl_dtype == CLAMD_BF16) shaped(ce_type<bf16_t>{});
+    else if (dl_dtype == CLAMD_F32) shaped(ce_type<float>{});
+    else shaped(ce_type<split_t>{});
 }
 
 // ce4_kernel, plain (WT = ce_no_weight; four pixels only: the callers have no other use) or weighted (WT = const float*)
@@ -1116,16 +1057,10 @@ template <typename WT>
 static void ce_launch(const CePlan& p, const float* logits, const long long* labels, WT weight, float* dlogits, void* dl_nhwc, int dl_ldc,
                       int dl_dtype, int B, int K, long long ignore_index, float grad_scale) {
     constexpr bool WEIGHTED = !__is_same(WT, ce_no_weight);
-    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
-        using NT = typename decltype(nt)::type;
-        auto launch = [&](auto kmax, auto npx) {
-            hipLaunchKernelGGL((ce4_kernel<decltype(kmax)::value, decltype(npx)::value, NT, WEIGHTED>), dim3(p.grid), dim3(256), 0, p.s, logits,
-                               labels, weight, dlogits, p.partial, B, K, p.HW, ignore_index, grad_scale, (NT*)dl_nhwc, dl_ldc, p.rows);
-        };
-        if constexpr (WEIGHTED) {
-            if (!p.four) return launch(ce_int<32>{}, ce_int<1>{});
-        }
-        ce_for_kmax(K, [&](auto kmax) { launch(kmax, ce_int<4>{}); });
+    ce_dispatch(p, K, dl_nhwc, dl_dtype, [&](auto nt, auto kmax, auto npx) {
+        if constexpr (WEIGHTED || CE_V(npx) == 4)
+            hipLaunchKernelGGL((ce4_kernel<CE_V(kmax), CE_V(npx), CE_T(nt), WEIGHTED>), dim3(p.grid), dim3(256), 0, p.s, logits, labels, weight,
+                               dlogits, p.partial, B, K, p.HW, ignore_index, grad_scale, (CE_T(nt)*)dl_nhwc, dl_ldc, p.rows);
     });
 }
 
@@ -1185,23 +1120,16 @@ int clamd_ce_dice_fwd_bwd(const float* logits, const long long* labels, float* d
     float *rows = ws + d.rows, *coef = ws + d.coef;
     double* gterm = (double*)(ws + d.gterm);
     const float gs = (float)grad_scale;
-    auto sums = [&](auto kmax, auto npx) {
-        hipLaunchKernelGGL((dice_sums_kernel<decltype(kmax)::value, decltype(npx)::value>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels, rows,
-                           d.cpi, K, p.HW, ignore_index);
-    };
-    if (p.four) ce_for_kmax(K, [&](auto kmax) { sums(kmax, ce_int<4>{}); });
-    else sums(ce_int<32>{}, ce_int<1>{});
+    ce_dispatch(p, K, nullptr, 0, [&](auto, auto kmax, auto npx) {            // the sums pass writes no copy: no element type
+        hipLaunchKernelGGL((dice_sums_kernel<CE_V(kmax), CE_V(npx)>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels, rows, d.cpi, K, p.HW,
+                           ignore_index);
+    });
     hipLaunchKernelGGL(dice_coef_kernel, dim3(d.G), dim3(32 * DICE_SLICES), 0, p.s, rows, d.nrows, per_image ? d.cpi : d.nrows, d.G, K, w_dice, smooth,
                        first_class, present_only ? 1 : 0, coef, gterm, p.totals);
-    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
-        using NT = typename decltype(nt)::type;
-        auto grad = [&](auto kmax, auto npx) {
-            hipLaunchKernelGGL((dice_grad_kernel<decltype(kmax)::value, decltype(npx)::value, NT>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels,
-                               coef, p.totals, dlogits, p.partial, d.cpi, per_image ? 1 : 0, K, p.HW, ignore_index, gs, (float)w_ce, (NT*)dl_nhwc,
-                               dl_ldc);
-        };
-        if (p.four) ce_for_kmax(K, [&](auto kmax) { grad(kmax, ce_int<4>{}); });
-        else grad(ce_int<32>{}, ce_int<1>{});
+    ce_dispatch(p, K, dl_nhwc, dl_dtype, [&](auto nt, auto kmax, auto npx) {
+        using NT = CE_T(nt);
+        hipLaunchKernelGGL((dice_grad_kernel<CE_V(kmax), CE_V(npx), NT>), dim3(d.nrows), dim3(256), 0, p.s, logits, labels, coef, p.totals, dlogits,
+                           p.partial, d.cpi, per_image ? 1 : 0, K, p.HW, ignore_index, gs, (float)w_ce, (NT*)dl_nhwc, dl_ldc);
     });
     hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, p.s, p.partial, d.nrows, p.totals, gterm, d.G, w_ce, w_dice, loss3);
     return clamd_check_launch("ce_dice_fwd_bwd");
@@ -1268,19 +1196,17 @@ int clamd_ce_unbiased_fwd_bwd(const float* logits, const long long* labels, cons
     // ce4u_kernel<KMAX, KOLD, NPX, NT>: KOLD in {0, 16, 32} sizes the register array of the old model's exponentials (only its first c_old
     // entries are touched); the odd-size path is not tuned: one instantiation per term
     const int ko = !old_logits ? 0 : c_old <= 16 ? 16 : 32;
-    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
-        using NT = typename decltype(nt)::type;
-        auto launch = [&](auto kmax, auto kold, auto npx) {
-            hipLaunchKernelGGL((ce4u_kernel<decltype(kmax)::value, decltype(kold)::value, decltype(npx)::value, NT>), dim3(p.grid), dim3(256), 0, p.s,
-                               logits, labels, old_logits, K_old_total, c_old, kd_scale, dlogits, p.partial, B, K, p.HW, ignore_index,
-                               (float)grad_scale, (NT*)dl_nhwc, dl_ldc, p.rows);
+    ce_dispatch(p, K, dl_nhwc, dl_dtype, [&](auto nt, auto kmax, auto npx) {
+        using NT = CE_T(nt);
+        auto launch = [&](auto kold) {
+            hipLaunchKernelGGL((ce4u_kernel<CE_V(kmax), CE_V(kold), CE_V(npx), NT>), dim3(p.grid), dim3(256), 0, p.s, logits, labels, old_logits,
+                               K_old_total, c_old, kd_scale, dlogits, p.partial, B, K, p.HW, ignore_index, (float)grad_scale, (NT*)dl_nhwc, dl_ldc,
+                               p.rows);
         };
-        if (!p.four) return old_logits ? launch(ce_int<32>{}, ce_int<32>{}, ce_int<1>{}) : launch(ce_int<32>{}, ce_int<0>{}, ce_int<1>{});
-        ce_for_kmax(K, [&](auto kmax) {
-            if (ko == 0) launch(kmax, ce_int<0>{}, ce_int<4>{});
-            else if (ko == 16) launch(kmax, ce_int<16>{}, ce_int<4>{});
-            else if constexpr (decltype(kmax)::value > 16) launch(kmax, ce_int<32>{}, ce_int<4>{});      // c_old > 16 needs K > 16
-        });
+        if (ko == 0) launch(ce_int<0>{});
+        else if constexpr (CE_V(npx) == 1) launch(ce_int<32>{});
+        else if (ko == 16) launch(ce_int<16>{});
+        else if constexpr (CE_V(kmax) > 16) launch(ce_int<32>{});      // c_old > 16 needs K > 16
     });
     // the kernel leaves sum_px of c_old * kd_px: the finalize multiplies by 1 / npix and by its `lam` argument
     ce_finalize(p, old_logits ? (float)(lam / (double)c_old) : 0.f, loss3);
@@ -1310,20 +1236,16 @@ int clamd_ce_class_fwd_bwd(const float* logits, const long long* labels, const f
         hipLaunchKernelGGL(class_count_rows_kernel<1>, dim3(CE_COUNT_BLOCKS), dim3(256), 0, p.s, labels, p.npix, ignore_index, K, crows);
     hipLaunchKernelGGL(class_totals_kernel, dim3(1), dim3(256), 0, p.s, crows, class_weight, K, p.totals, tot);
     const double keep = 1.0 - label_smoothing, spread = label_smoothing / (double)K;
-    ce_for_nt(dl_nhwc, dl_dtype, [&](auto nt) {
-        using NT = typename decltype(nt)::type;
-        auto launch = [&](auto kmax, auto npx, auto mode) {
-            hipLaunchKernelGGL((ce4c_kernel<decltype(kmax)::value, decltype(npx)::value, NT, decltype(mode)::value>), dim3(p.grid), dim3(256), 0, p.s,
-                               logits, labels, class_weight, image_weight, dlogits, p.partial, B, K, p.HW, ignore_index, (float)grad_scale,
-                               (float)keep, (float)spread, (float)focal_gamma, (NT*)dl_nhwc, dl_ldc, (const float*)tot);
+    ce_dispatch(p, K, dl_nhwc, dl_dtype, [&](auto nt, auto kmax, auto npx) {
+        using NT = CE_T(nt);
+        auto launch = [&](auto mode) {
+            hipLaunchKernelGGL((ce4c_kernel<CE_V(kmax), CE_V(npx), NT, CE_V(mode)>), dim3(p.grid), dim3(256), 0, p.s, logits, labels, class_weight,
+                               image_weight, dlogits, p.partial, B, K, p.HW, ignore_index, (float)grad_scale, (float)keep, (float)spread,
+                               (float)focal_gamma, (NT*)dl_nhwc, dl_ldc, (const float*)tot);
         };
-        auto by_mode = [&](auto kmax, auto npx) {
-            if (focal_gamma > 0.0) launch(kmax, npx, ce_int<CEC_FOCAL>{});
-            else if (label_smoothing > 0.0) launch(kmax, npx, ce_int<CEC_SMOOTH>{});
-            else launch(kmax, npx, ce_int<CEC_WEIGHT>{});
-        };
-        if (!p.four) return by_mode(ce_int<32>{}, ce_int<1>{});
-        ce_for_kmax(K, [&](auto kmax) { by_mode(kmax, ce_int<4>{}); });
+        if (focal_gamma > 0.0) launch(ce_int<CEC_FOCAL>{});
+        else if (label_smoothing > 0.0) launch(ce_int<CEC_SMOOTH>{});
+        else launch(ce_int<CEC_WEIGHT>{});
     });
     hipLaunchKernelGGL(cec_finalize_kernel, dim3(1), dim3(256), 0, p.s, p.partial, p.grid, (const float*)tot, keep, spread, loss3);
     return clamd_check_launch("ce_class_fwd_bwd");

@@ -20,6 +20,7 @@ the focal term build-defined) on ``clamd_ce_class_fwd_bwd``; ``class_weights`` d
 ``DiceCrossEntropyLoss`` is cross-entropy plus soft Dice (build-defined, the compound loss of nnU-Net / MONAI's DiceCELoss), on
 ``clamd_ce_dice_fwd_bwd``: a sums pass, a coefficient pass and a gradient pass, every reduction in a fixed order.
 """
+import collections
 import os
 
 import torch
@@ -29,63 +30,39 @@ from . import _lib
 from ._lib import call, ptr
 
 
-# d logits handed to the UNet's backward pass in the head data gradient's own layout (see _forward); =0: the engine converts the NCHW
+# d logits handed to the UNet's backward pass in the head data gradient's own layout (see _LossFn); =0: the engine converts the NCHW
 # gradient as it does for any other loss (A/B measurements)
 HANDOVER = os.environ.get('CLAMD_LOSS_HANDOVER', '1') != '0'
 
+# What a criterion tells _LossFn about its library call  entry(logits, labels, <old>, <vectors>, *lead, d logits, ..., ignore_index, *tail, grad_scale):
+#   old        (old_logits,) where the entry takes the old model's logits and their class count ((None,): called without them); () otherwise
+#   vectors    ((tensor or None, 'image_weight' | 'class weights'), ...): per-image / per-class fp32 factors, checked by _vector
+#   lead, tail the numbers behind those / between ignore_index and grad_scale
+#   px_bytes, px_logits   what the entry reads per pixel beyond the logits and the label: bytes, and further reads of the K logits
+#   count      clamd_ce_count runs in front (False: the entry counts for itself)
+#   ws_bytes   ``ws_bytes(lib, B, K, H, W)``: the size of a workspace larger than the cross-entropy one (which it starts with)
+#   handover   False: clamd_ce_fwd_bwd's argument list -- no NHWC copy of d logits, nothing handed to the UNet
+_Launch = collections.namedtuple('_Launch', 'entry old vectors lead tail px_bytes px_logits count ws_bytes handover',
+                                 defaults=((), (), (), (), 0, 0, True, None, True))
+_PLAIN = _Launch('clamd_ce_fwd_bwd_counted')
 
-def _forward(ctx, holder, logits, labels, ignore_index, others, middle, ws_bytes=None):
-    """What every loss forward shares: the checks, the allocation, and the bookkeeping behind the kernels.  `others`: the further tensors
-    the caller hands to the library.  ``middle(counted, logits, labels, dl, out3, ws, wsb)`` launches the loss: its own call on these
-    buffers, or ``counted(entry, lead, px_bytes)`` -- the training-step form.  ``ws_bytes(lib, B, K, H, W)``: the size of a workspace
-    larger than the cross-entropy one (which it starts with)."""
-    if not all(t.is_cuda for t in (logits, labels) + tuple(others) if t is not None):
-        raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
-    lib = _lib.load()
-    logits_in = logits
-    logits = logits.contiguous().float()
-    labels = labels.contiguous()
-    if labels.dtype != torch.int64:
-        raise TypeError('labels must be int64 (datasets/voc.py:72)')
-    B, K, H, W = logits.shape
-    if tuple(labels.shape) != (B, H, W):
-        raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
-    dl = torch.empty_like(logits)
-    out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
-    wsb = lib.clamd_ce_workspace_bytes() if ws_bytes is None else ws_bytes(lib, B, K, H, W)
-    ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
-    ctx.sink = None
 
-    def counted(entry, lead=(), px_bytes=0, count=True, tail=()):
-        """clamd_ce_count, then `entry`(logits, labels, *lead, d logits, its NHWC copy, ...): the count of valid pixels as partial rows (no
-        memset, no atomics), and, when the logits come from this package's UNet, d logits written a second time in the layout (and dtype) its
-        1x1 head's data gradient reads -- the backward pass then starts without a conversion pass (unet._Engine.backward).
-        px_bytes: what the entry reads per pixel beyond the logits and the label.  count=False: the entry counts for itself; tail: its
-        arguments between ignore_index and grad_scale."""
-        from . import unet as U
-        # (algorithmic bytes, SURVEY 8d: logits read + d logits written + the label; the counting pass reads the labels a second time)
-        if count:
-            U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), B, K, H, W, int(ignore_index), ptr(ws), wsb, _lib.stream_ptr())
-        eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
-        nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
-        U._hbm('loss', B * H * W * (2 * K * 4 + px_bytes + 8 + (ldc * eng.esize if eng is not None else 0)),
-               entry, ptr(logits), ptr(labels), *lead, ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb, B, K, H, W,
-               int(ignore_index), *tail, 1.0, _lib.stream_ptr())
-        if eng is not None:
-            ctx.sink = eng
-            # a STRONG reference: while the engine waits for this gradient its storage cannot be freed and handed to another
-            # tensor of the same shape (a second loss on the same logits would otherwise pass for this one by address)
-            eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)
+def _any_size(old_logits=None, c_old=0, temperature=1.0, lam=0.0):
+    """clamd_ce_fwd_bwd: the temperature-distillation term, odd sizes, misaligned storage"""
+    return _Launch('clamd_ce_fwd_bwd', (old_logits,), lead=(int(c_old), float(temperature), float(lam)), count=False, handover=False)
 
-    middle(counted, logits, labels, dl, out3, ws, wsb)
-    ctx.save_for_backward(dl)
-    ctx.parts = out3
-    # labels outside [0, K) that are not ignore_index: a device counter on the criterion (int(...) synchronises);
-    # torch's CrossEntropyLoss asserts on such labels, here they are left out of the mean and counted
-    off = lib.clamd_ce_bad_label_count_offset() // 4
-    holder.bad_labels = ws[off:off + 1].view(torch.int32)
-    holder.parts = out3
-    return out3[0]
+
+_VECTORS = {'image_weight': (0, ' (one factor per image)'), 'class weights': (1, '')}      # -> (the logits dimension it spans, the message's note)
+
+
+def _vector(t, what, shape):
+    """-> `t` contiguous (None stays None); ValueError unless it is float32 with one entry per image / per class of logits `shape`"""
+    if t is None:
+        return None
+    dim, note = _VECTORS[what]
+    if t.dtype != torch.float32 or tuple(t.shape) != (shape[dim],):
+        raise ValueError(f'{what} must be float32 [{shape[dim]}]{note}, got {t.dtype} {tuple(t.shape)}')
+    return t.contiguous()
 
 
 def _old_logits(old_logits, logits):
@@ -99,20 +76,66 @@ def _old_logits(old_logits, logits):
     return old_logits, old_logits.shape[1]
 
 
-class _CEFn(torch.autograd.Function):
+class _LossFn(torch.autograd.Function):
+    """Every criterion's forward and backward: the checks, the allocation, [clamd_ce_count and] the entry point `launch` names, and the
+    bookkeeping behind the kernels.  `holder`: the criterion; it supplies ignore_index and receives `parts` and `bad_labels`."""
+
     @staticmethod
-    def forward(ctx, logits, labels, old_logits, c_old, temperature, lam, ignore_index, holder):
-        def middle(counted, logits, labels, dl, out3, ws, wsb):
-            B, K, H, W = logits.shape
-            old, kold = _old_logits(old_logits, logits)
-            # the four-pixel kernels read 16 bytes of logits / 32 bytes of labels per lane: an odd storage offset takes the scalar kernel
-            aligned = logits.data_ptr() % 16 == 0 and dl.data_ptr() % 16 == 0 and labels.data_ptr() % 32 == 0
-            if old is None and (H * W) % 4 == 0 and aligned:
-                counted('clamd_ce_fwd_bwd_counted')
-            else:
-                call('clamd_ce_fwd_bwd', ptr(logits), ptr(labels), ptr(old), kold, int(c_old), float(temperature),
-                     float(lam), ptr(dl), ptr(out3), ptr(ws), wsb, B, K, H, W, int(ignore_index), 1.0, _lib.stream_ptr())
-        return _forward(ctx, holder, logits, labels, ignore_index, (old_logits,), middle)
+    def forward(ctx, logits, labels, holder, launch):
+        ignore_index = int(holder.ignore_index)
+        others = launch.old + tuple(t for t, _ in launch.vectors)
+        if not all(t.is_cuda for t in (logits, labels) + others if t is not None):
+            raise RuntimeError('continual-learning_amd loss runs only on GPU tensors: there is no CPU fallback')
+        lib = _lib.load()
+        logits_in = logits
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            raise TypeError('labels must be int64 (datasets/voc.py:72)')
+        B, K, H, W = logits.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise ValueError(f'labels shape {tuple(labels.shape)} does not match logits {tuple(logits.shape)}')
+        dl = torch.empty_like(logits)
+        out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+        wsb = lib.clamd_ce_workspace_bytes() if launch.ws_bytes is None else launch.ws_bytes(lib, B, K, H, W)
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=logits.device)
+        ctx.sink = None
+        # the four-pixel kernels read 16 bytes of logits / 32 bytes of labels per lane: an odd storage offset takes the scalar kernel
+        aligned = logits.data_ptr() % 16 == 0 and dl.data_ptr() % 16 == 0 and labels.data_ptr() % 32 == 0
+        if launch is _PLAIN and not ((H * W) % 4 == 0 and aligned):
+            launch = _any_size()
+        held = [_old_logits(t, logits) for t in launch.old]                       # (tensor, class count); held until the launch
+        vectors = [_vector(t, what, logits.shape) for t, what in launch.vectors]
+        lead = tuple(a for t, kold in held for a in (ptr(t), kold)) + tuple(ptr(t) for t in vectors) + launch.lead
+        shape = (B, K, H, W, ignore_index)
+        if not launch.handover:
+            call(launch.entry, ptr(logits), ptr(labels), *lead, ptr(dl), ptr(out3), ptr(ws), wsb, *shape, *launch.tail, 1.0, _lib.stream_ptr())
+        else:
+            # the training-step form: the count of valid pixels as partial rows (no memset, no atomics), and, when the logits come from this
+            # package's UNet, d logits written a second time in the layout (and dtype) its 1x1 head's data gradient reads -- the backward
+            # pass then starts without a conversion pass (unet._Engine.backward)
+            from . import unet as U
+            # (algorithmic bytes, SURVEY 8d: logits read + d logits written + the label; the counting pass reads the labels a second time)
+            if launch.count:
+                U._hbm('loss', 0, 'clamd_ce_count', ptr(labels), *shape, ptr(ws), wsb, _lib.stream_ptr())
+            eng = U.dlogits_sink(logits_in, B, K, H, W) if HANDOVER else None
+            nh, ldc, dcode = (eng.dl, eng.Kp, eng.dcode) if eng is not None else (None, 0, 0)
+            px = (2 + launch.px_logits) * K * 4 + launch.px_bytes + 8 + (ldc * eng.esize if eng is not None else 0)
+            U._hbm('loss', B * H * W * px, launch.entry, ptr(logits), ptr(labels), *lead, ptr(dl), ptr(nh), ldc, dcode, ptr(out3), ptr(ws), wsb,
+                   *shape, *launch.tail, 1.0, _lib.stream_ptr())
+            if eng is not None:
+                ctx.sink = eng
+                # a STRONG reference: while the engine waits for this gradient its storage cannot be freed and handed to another
+                # tensor of the same shape (a second loss on the same logits would otherwise pass for this one by address)
+                eng.dl_src = (dl, dl.data_ptr(), dl._version, eng.generation)
+        ctx.save_for_backward(dl)
+        ctx.parts = out3
+        # labels outside [0, K) that are not ignore_index: a device counter on the criterion (int(...) synchronises);
+        # torch's CrossEntropyLoss asserts on such labels, here they are left out of the mean and counted
+        off = lib.clamd_ce_bad_label_count_offset() // 4
+        holder.bad_labels = ws[off:off + 1].view(torch.int32)
+        holder.parts = out3
+        return out3[0]
 
     @staticmethod
     def backward(ctx, g):
@@ -125,7 +148,7 @@ class _CEFn(torch.autograd.Function):
             call('clamd_scale_by_device_scalar_nhwc', ptr(eng.dl), eng.dl.numel(), eng.dcode, ptr(g), ptr(dl), dl.numel(), _lib.stream_ptr())
         else:
             call('clamd_scale_by_device_scalar', ptr(dl), dl.numel(), ptr(g), _lib.stream_ptr())
-        return dl, None, None, None, None, None, None, None
+        return dl, None, None, None
 
 
 class CrossEntropyLoss(nn.Module):
@@ -173,10 +196,13 @@ class CrossEntropyLoss(nn.Module):
             elif w.numel() != K:
                 raise ValueError(f'CrossEntropyLoss: weight has {w.numel()} entries, the logits have {K} classes')
             nu = None if image_weight is None else image_weight.detach()
-            return _ClassCEFn.apply(logits, labels, w, nu, self.label_smoothing, self.focal_gamma, self.ignore_index, self)
+            # clamd_ce_class_fwd_bwd counts for itself: the labels a second time (the K + B weights do not count as traffic)
+            return _LossFn.apply(logits, labels, self, _Launch(
+                'clamd_ce_class_fwd_bwd', vectors=((w, 'class weights'), (nu, 'image_weight')), tail=(float(self.label_smoothing), float(self.focal_gamma)),
+                px_bytes=8, count=False, ws_bytes=lambda lib, *shape: lib.clamd_ce_class_workspace_bytes()))
         if image_weight is not None:
-            return _WCEFn.apply(logits, labels, image_weight.detach(), self.ignore_index, self)
-        return _CEFn.apply(logits, labels, None, 0, 1.0, 0.0, self.ignore_index, self)
+            return _LossFn.apply(logits, labels, self, _Launch('clamd_ce_fwd_bwd_weighted', vectors=((image_weight.detach(), 'image_weight'),)))
+        return _LossFn.apply(logits, labels, self, _PLAIN)
 
 
 def check_smoothing_and_gamma(label_smoothing, focal_gamma):
@@ -251,67 +277,7 @@ class DistillationCrossEntropy(nn.Module):
         self.c_old, self.temperature, self.lam, self.ignore_index = c_old, temperature, lam, ignore_index
 
     def forward(self, logits, labels, old_logits):
-        return _CEFn.apply(logits, labels, old_logits.detach(), self.c_old, self.temperature, self.lam, self.ignore_index, self)
-
-
-class _UCEFn(torch.autograd.Function):
-    """clamd_ce_count + clamd_ce_unbiased_fwd_bwd; the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, old_logits, c_old, lam, ignore_index, holder):
-        def middle(counted, logits, *_):
-            old, kold = _old_logits(old_logits, logits)
-            # algorithmic bytes: the c_old old-model logits on top of the plain loss's
-            counted('clamd_ce_unbiased_fwd_bwd', (ptr(old), kold, int(c_old), float(lam)), 4 * c_old if old is not None and lam != 0 else 0)
-        return _forward(ctx, holder, logits, labels, ignore_index, (old_logits,), middle)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _CEFn.backward(ctx, g)[:7]
-
-
-class _WCEFn(torch.autograd.Function):
-    """clamd_ce_count + clamd_ce_fwd_bwd_weighted; the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, image_weight, ignore_index, holder):
-        def middle(counted, logits, *_):
-            B = logits.shape[0]
-            if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
-                raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
-            nu = image_weight.contiguous()
-            counted('clamd_ce_fwd_bwd_weighted', (ptr(nu),))      # algorithmic bytes: the plain loss's (the B weights do not count)
-        return _forward(ctx, holder, logits, labels, ignore_index, (image_weight,), middle)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _CEFn.backward(ctx, g)[:5]
-
-
-class _ClassCEFn(torch.autograd.Function):
-    """clamd_ce_class_fwd_bwd (it counts for itself); the hand-over of d logits to the UNet's backward pass and the backward as _CEFn."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, class_weight, image_weight, label_smoothing, focal_gamma, ignore_index, holder):
-        def middle(counted, logits, *_):
-            B, K = logits.shape[:2]
-            if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
-                raise ValueError(f'class weights must be float32 [{K}], got {class_weight.dtype} {tuple(class_weight.shape)}')
-            nu = None
-            if image_weight is not None:
-                if image_weight.dtype != torch.float32 or tuple(image_weight.shape) != (B,):
-                    raise ValueError(f'image_weight must be float32 [{B}] (one factor per image), got {image_weight.dtype} {tuple(image_weight.shape)}')
-                nu = image_weight.contiguous()
-            # algorithmic bytes: the plain loss's plus the counting pass's second read of the labels (the K + B weights do not count)
-            cw = class_weight.contiguous()
-            counted('clamd_ce_class_fwd_bwd', (ptr(cw), ptr(nu)), px_bytes=8, count=False,
-                    tail=(float(label_smoothing), float(focal_gamma)))
-        return _forward(ctx, holder, logits, labels, ignore_index, (class_weight, image_weight), middle,
-                        lambda lib, B, K, H, W: lib.clamd_ce_class_workspace_bytes())
-
-    @staticmethod
-    def backward(ctx, g):
-        return _CEFn.backward(ctx, g)
+        return _LossFn.apply(logits, labels, self, _any_size(old_logits.detach(), self.c_old, self.temperature, self.lam))
 
 
 class UnbiasedDistillationCrossEntropy(nn.Module):
@@ -329,31 +295,10 @@ class UnbiasedDistillationCrossEntropy(nn.Module):
         self.parts = None
 
     def forward(self, logits, labels, old_logits=None):
-        return _UCEFn.apply(logits, labels, None if old_logits is None else old_logits.detach(), self.c_old, self.lam, self.ignore_index, self)
-
-
-class _DiceCEFn(torch.autograd.Function):
-    """clamd_ce_dice_fwd_bwd (it counts the valid pixels itself); the hand-over of d logits to the UNet's backward pass and the backward as
-    _CEFn."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, w_ce, w_dice, smooth, first_class, present_only, per_image, ignore_index, holder):
-        def middle(counted, logits, *_):
-            K = logits.shape[1]
-            # algorithmic bytes: the logits and the label a second time on top of the plain loss's
-            counted('clamd_ce_dice_fwd_bwd', px_bytes=4 * K + 8, count=False,
-                    tail=(float(w_ce), float(w_dice), float(smooth), int(first_class), int(present_only), int(per_image)))
-
-        def ws_bytes(lib, B, K, H, W):
-            n = lib.clamd_ce_dice_workspace_bytes(B, K, H, W, int(per_image))
-            if n == 0:
-                raise ValueError(f'DiceCrossEntropyLoss: logits {(B, K, H, W)}: needs 1 <= K <= 32 classes and at most 2048 images')
-            return n
-        return _forward(ctx, holder, logits, labels, ignore_index, (), middle, ws_bytes)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _CEFn.backward(ctx, g) + (None, None)
+        old = None if old_logits is None else old_logits.detach()
+        # algorithmic bytes: the c_old old-model logits on top of the plain loss's
+        return _LossFn.apply(logits, labels, self, _Launch('clamd_ce_unbiased_fwd_bwd', (old,), lead=(self.c_old, self.lam),
+                                                           px_bytes=4 * self.c_old if old is not None and self.lam != 0 else 0))
 
 
 class DiceCrossEntropyLoss(nn.Module):
@@ -379,5 +324,12 @@ class DiceCrossEntropyLoss(nn.Module):
         self.parts = None
 
     def forward(self, logits, labels):
-        return _DiceCEFn.apply(logits, labels, self.ce_weight, self.dice_weight, self.smooth, 0 if self.include_background else 1,
-                               self.present_only, self.per_image, self.ignore_index, self)
+        def ws_bytes(lib, B, K, H, W):
+            n = lib.clamd_ce_dice_workspace_bytes(B, K, H, W, int(self.per_image))
+            if n == 0:
+                raise ValueError(f'DiceCrossEntropyLoss: logits {(B, K, H, W)}: needs 1 <= K <= 32 classes and at most 2048 images')
+            return n
+        # clamd_ce_dice_fwd_bwd counts for itself; algorithmic bytes: the logits and the label a second time on top of the plain loss's
+        return _LossFn.apply(logits, labels, self, _Launch(
+            'clamd_ce_dice_fwd_bwd', tail=(self.ce_weight, self.dice_weight, self.smooth, 0 if self.include_background else 1, int(self.present_only),
+                                           int(self.per_image)), px_bytes=8, px_logits=1, count=False, ws_bytes=ws_bytes))

@@ -653,6 +653,144 @@ def _check_direct_conv_refusals(lib, tref, bad_tune, ops):
         refused('clamd_stat_rows', _ROWS, sr, n + 'out of range', op=ops['conv3x3'], B=big, tune=t)
 
 
+_CE = 'logits labels old_logits K_old_total c_old temperature lam dlogits loss3 ws ws_bytes B K H W ignore_index grad_scale stream'.split()
+_CE_COUNT = 'labels B K H W ignore_index ws ws_bytes stream'.split()
+_CE_COUNTED = 'logits labels dlogits dl_nhwc dl_ldc dl_dtype loss3 ws ws_bytes B K H W ignore_index grad_scale stream'.split()
+_CE_WEIGHTED = 'logits labels image_weight dlogits dl_nhwc dl_ldc dl_dtype loss3 ws ws_bytes B K H W ignore_index grad_scale stream'.split()
+_CE_UNBIASED = ('logits labels old_logits K_old_total c_old lam dlogits dl_nhwc dl_ldc dl_dtype loss3 ws ws_bytes B K H W ignore_index grad_scale '
+                'stream').split()
+_CE_CLASS = ('logits labels class_weight image_weight dlogits dl_nhwc dl_ldc dl_dtype loss3 ws ws_bytes B K H W ignore_index label_smoothing '
+             'focal_gamma grad_scale stream').split()
+_CE_DICE = ('logits labels dlogits dl_nhwc dl_ldc dl_dtype loss3 ws ws_bytes B K H W ignore_index w_ce w_dice smooth first_class present_only '
+            'per_image grad_scale stream').split()
+
+
+def test_loss_entry_points_refuse_with_pinned_messages(C):
+    """Every refusal of the seven per-pixel loss entry points (loss.hip) that returns before any launch, with the WHOLE message and status
+    -1; consecutive checks are also violated together and the earlier one answers.  The two workspace queries and the counter's offset are
+    pinned as numbers.  Nothing here passes validation: no pointer is dereferenced and nothing is launched."""
+    lib = C._lib.load()
+    refused, chain = _refusal_tools(lib)
+    p, odd = 0x1000, 0x1010                                 # 64-byte aligned / 16-byte aligned only
+    F32, SPLIT, NODT = 0, 2, 9
+    ce_ws, class_ws = 18448, 53408
+    assert lib.clamd_ce_workspace_bytes() == ce_ws and lib.clamd_ce_class_workspace_bytes() == class_ws
+    assert lib.clamd_ce_bad_label_count_offset() == 16388
+    # the Dice workspace: the CE workspace, B * min(ceil(HW / 256), 2048 // B) rows of 100 words, 64 words and a double per group
+    dice_ws = lib.clamd_ce_dice_workspace_bytes
+    assert [dice_ws(2, 5, 8, 12, g) for g in (0, 1)] == [ce_ws + 4 * (2 * 100 + 64 + 2), ce_ws + 4 * (2 * 100 + 2 * 64 + 4)]
+    assert dice_ws(9, 21, 484, 484, 1) == ce_ws + 4 * (9 * 227 * 100 + 9 * 64 + 18) and dice_ws(2048, 32, 1, 1, 0) == ce_ws + 4 * (2048 * 100 + 66)
+    assert [dice_ws(*a) for a in ((2049, 5, 8, 12, 0), (2, 0, 8, 12, 0), (2, 33, 8, 12, 0), (0, 5, 8, 12, 0), (2, 5, 0, 12, 0), (2, 5, 8, 0, 1))] == [0] * 6
+
+    split = 'bf16x3 tensors need a 64-byte aligned base and a pitch that is a multiple of 16 channels'
+    small = 'ce: workspace too small'
+
+    def plan(who, nhwc=True, ws_step=True):
+        """ce_plan's checks in their order"""
+        steps = [(who + ': null pointer or empty shape', dict(B=0)), (who + ': number of classes must be in [1, 32]', dict(K=33))]
+        if ws_step:
+            steps.append((small, dict(ws_bytes=ce_ws - 1)))
+        steps.append((who + ': misaligned tensor', dict(labels=0x1004)))
+        if nhwc:
+            steps += [(who + ': the NHWC copy needs a pitch >= 32 channels, a multiple of 8, and a 16-byte aligned base', dict(dl_nhwc=p, dl_ldc=24)),
+                      (who + ': bad dtype', dict(dl_nhwc=p, dl_dtype=NODT)),
+                      (split, dict(dl_nhwc=odd, dl_dtype=SPLIT))]
+        return steps
+
+    def plan_singles(name, order, base, who, nhwc=True, k0=None):
+        for k in ('logits', 'labels', 'dlogits', 'loss3', 'ws'):
+            refused(name, order, base, who + ': null pointer or empty shape', **{k: None})
+        for kw in (dict(H=0), dict(W=-1), dict(B=-3)):
+            refused(name, order, base, who + ': null pointer or empty shape', **kw)
+        refused(name, order, base, k0 or who + ': number of classes must be in [1, 32]', K=0)
+        for kw in (dict(logits=0x1002), dict(dlogits=0x1001)):
+            refused(name, order, base, who + ': misaligned tensor', **kw)
+        if nhwc:
+            for kw in (dict(dl_ldc=36), dict(dl_nhwc=0x1008)):
+                refused(name, order, base, who + ': the NHWC copy needs a pitch >= 32 channels, a multiple of 8, and a 16-byte aligned base',
+                        **{'dl_nhwc': p, **kw})
+            refused(name, order, base, split, dl_nhwc=p, dl_dtype=SPLIT, dl_ldc=40)
+
+    shape = dict(B=2, K=5, H=8, W=12, ignore_index=-100, grad_scale=1.0, stream=None)
+    common = dict(shape, logits=p, labels=p, dlogits=p, loss3=p, ws=p, ws_bytes=1 << 26)
+    nhwc = dict(common, dl_nhwc=None, dl_ldc=32, dl_dtype=F32)
+
+    ce = dict(common, old_logits=None, K_old_total=0, c_old=0, temperature=2.0, lam=1.0)
+    chain('clamd_ce_fwd_bwd', _CE, ce, plan('ce', nhwc=False) + [('ce: bad c_old', dict(old_logits=p, c_old=0))])
+    plan_singles('clamd_ce_fwd_bwd', _CE, ce, 'ce', nhwc=False)
+    refused('clamd_ce_fwd_bwd', _CE, ce, 'ce: misaligned tensor', old_logits=0x1002, c_old=1, K_old_total=5)
+    for kw in (dict(c_old=6, K_old_total=8), dict(c_old=3, K_old_total=2)):
+        refused('clamd_ce_fwd_bwd', _CE, ce, 'ce: bad c_old', old_logits=p, **kw)
+
+    cnt = dict(shape, labels=p, ws=p, ws_bytes=1 << 26)
+    chain('clamd_ce_count', _CE_COUNT, cnt, [('ce_count: bad arguments', dict(K=0)), (small, dict(ws_bytes=ce_ws - 1))])
+    for kw in (dict(K=33), dict(labels=None), dict(B=0), dict(H=0), dict(W=0)):
+        refused('clamd_ce_count', _CE_COUNT, cnt, 'ce_count: bad arguments', **kw)
+
+    who = 'ce_fwd_bwd_counted'
+    four = who + ': needs H * W % 4 == 0 and 16-byte aligned logits / 32-byte aligned labels (use clamd_ce_fwd_bwd)'
+    chain('clamd_ce_fwd_bwd_counted', _CE_COUNTED, nhwc, plan(who) + [(four, dict(H=7, W=9))])
+    plan_singles('clamd_ce_fwd_bwd_counted', _CE_COUNTED, nhwc, who)
+    for kw in (dict(logits=0x1004), dict(dlogits=0x1008), dict(labels=0x1010)):
+        refused('clamd_ce_fwd_bwd_counted', _CE_COUNTED, nhwc, four, **kw)
+
+    who = 'ce_weighted'
+    need = who + ': image_weight (B floats) is required (clamd_ce_fwd_bwd_counted is the unweighted loss)'
+    wce = dict(nhwc, image_weight=p)
+    chain('clamd_ce_fwd_bwd_weighted', _CE_WEIGHTED, wce, [(need, dict(image_weight=None))] + plan(who))
+    refused('clamd_ce_fwd_bwd_weighted', _CE_WEIGHTED, wce, need, image_weight=0x1002)
+    plan_singles('clamd_ce_fwd_bwd_weighted', _CE_WEIGHTED, wce, who)
+
+    who = 'ce_unbiased'
+    exceeds = dict(old_logits=p, K_old_total=1, c_old=2)
+    uce = dict(nhwc, old_logits=None, K_old_total=0, c_old=1, lam=1.0)
+    chain('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, [
+        (who + ': c_old must be in [1, K]', dict(c_old=0)),
+        (who + ': lam must be >= 0', dict(lam=-1.0)),
+        (who + ": c_old exceeds the old model's class count K_old_total", exceeds)] + plan(who))
+    refused('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who + ': c_old must be in [1, K]', c_old=6)
+    refused('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who + ': lam must be >= 0', lam=float('nan'))
+    # lam == 0 drops the old model before its checks: neither its class count nor its alignment is looked at
+    refused('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who + ': null pointer or empty shape', lam=0.0, B=0, **exceeds)
+    refused('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who + ': null pointer or empty shape', lam=0.0, B=0, old_logits=0x1002)
+    refused('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who + ': misaligned tensor', old_logits=0x1002, K_old_total=5)
+    plan_singles('clamd_ce_unbiased_fwd_bwd', _CE_UNBIASED, uce, who, k0=who + ': c_old must be in [1, K]')      # c_old = 1 > K answers first
+
+    who = 'ce_class'
+    cls_ws = who + ': workspace too small (clamd_ce_class_workspace_bytes) or not 8-byte aligned'
+    cce = dict(nhwc, class_weight=p, image_weight=None, label_smoothing=0.0, focal_gamma=0.0)
+    chain('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, [
+        (who + ': class_weight (K floats) is required and must be 4-byte aligned', dict(class_weight=None)),
+        (who + ': misaligned image_weight', dict(image_weight=0x1002)),
+        (who + ': label_smoothing must be in [0, 1)', dict(label_smoothing=1.0)),
+        (who + ': focal_gamma must be finite and >= 0', dict(focal_gamma=-1.0)),
+        (who + ': label_smoothing and focal_gamma are both non-zero: the combination is not defined', dict(label_smoothing=0.1, focal_gamma=0.5)),
+        (cls_ws, dict(ws_bytes=class_ws - 1))] + plan(who, ws_step=False))
+    refused('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, who + ': class_weight (K floats) is required and must be 4-byte aligned', class_weight=0x1002)
+    for v in (-0.1, float('nan')):
+        refused('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, who + ': label_smoothing must be in [0, 1)', label_smoothing=v)
+    for v in (float('inf'), float('nan')):
+        refused('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, who + ': focal_gamma must be finite and >= 0', focal_gamma=v)
+    refused('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, cls_ws, ws=0x1004)
+    plan_singles('clamd_ce_class_fwd_bwd', _CE_CLASS, cce, who)
+
+    who = 'ce_dice'
+    dice_small = who + ': workspace too small (clamd_ce_dice_workspace_bytes)'
+    dce = dict(nhwc, w_ce=1.0, w_dice=1.0, smooth=1e-5, first_class=0, present_only=1, per_image=0)
+    chain('clamd_ce_dice_fwd_bwd', _CE_DICE, dce, [
+        (who + ': first_class must be 0 or 1', dict(first_class=2)),
+        (who + ': w_ce, w_dice and smooth must be finite and >= 0', dict(w_ce=-1.0)),
+        (dice_small, dict(ws_bytes=ce_ws - 1))] + plan(who, ws_step=False) + [
+        (who + ': more than 2048 images: every image needs a partial row of its own and the coefficient pass adds at most 2048', dict(B=2049)),
+        (dice_small, dict(ws_bytes=dice_ws(2, 5, 8, 12, 0) - 1)),
+        (who + ': workspace must be 16-byte aligned', dict(ws=0x1008))])
+    refused('clamd_ce_dice_fwd_bwd', _CE_DICE, dce, who + ': first_class must be 0 or 1', first_class=-1)
+    for kw in (dict(w_dice=float('inf')), dict(smooth=float('nan')), dict(w_dice=-0.5), dict(smooth=-1e-9), dict(w_ce=float('inf'))):
+        refused('clamd_ce_dice_fwd_bwd', _CE_DICE, dce, who + ': w_ce, w_dice and smooth must be finite and >= 0', **kw)
+    refused('clamd_ce_dice_fwd_bwd', _CE_DICE, dce, dice_small, per_image=1, ws_bytes=dice_ws(2, 5, 8, 12, 1) - 1)
+    plan_singles('clamd_ce_dice_fwd_bwd', _CE_DICE, dce, who)
+
+
 def test_abi_rejects_bad_arguments_before_any_launch(C):
     """Error behaviour of the C ABI: argument validation happens on the host before anything is
     enqueued, the entry point returns a negative status, clamd_last_error() names the problem and the Python side raises
